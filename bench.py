@@ -1,6 +1,7 @@
 """Benchmark of the PME/P3M hot path on MI355X.
 
     python bench.py --gpus N --steps K --warmup W [--workload water|ionic|dispersion] [--preset cfg2|cfg3|cfg4|cfg5]
+                    [--dump-outputs DIR] [--full]
 
 One *step* = one energy + forces evaluation of one frame (or ``--frames-per-gpu`` frames) per GPU, the reference's
 protocol: ``d = pair_distances(...)`` -> ``V = calculator(...)`` -> ``E = sum(q*V)`` ->
@@ -16,10 +17,16 @@ after the last step).  Every rank binds itself to a disjoint set of host cores o
 over ranks; ``weak_efficiency`` = rank 0's time with the other ranks idle / the time with all ranks busy, same invocation.
 
 Timing protocol: >= ``--prewarm-ms`` of untimed replays (clock ramp), the W warm-up steps, then ``--blocks`` blocks of EXACTLY K
-steps, each bracketed by barrier + synchronize.  ``ms_per_step`` / ``value`` are the MEDIAN block's (the contract's one timed
-region; round 4 reported the first block, which was the fastest one in every run); ``ms_per_step_first_block`` is the first.
+steps, each bracketed by barrier + synchronize: ONE block by default, so that K is the number of timed steps (five with
+``--full``).  ``ms_per_step`` / ``value`` are the MEDIAN block's (the contract's one timed region; round 4 reported the first
+block, which was the fastest one in every run); ``ms_per_step_first_block`` is the first.
 
-Rank 0 prints ONE JSON line: metric = atom-steps/s over all ranks, plus
+A plain run does only that: set up, warm up, time, write the outputs (``--dump-outputs DIR``: rank 0's frame energies and
+forces of the last timed step as ``DIR/energy.npy`` / ``DIR/forces.npy``, in the workload's precision) and print the line.
+Everything else the benchmark measures or checks runs with ``--full`` only: with more than one rank the one-rank reference
+block of ``weak_efficiency`` and one timed block per other exchange protocol, and on rank 0 the blocks below.
+
+Rank 0 prints ONE JSON line: metric = atom-steps/s over all ranks, plus (``--full``)
   roofline     -- HBM roofline of the dominant kernel, timed live with HIP events on the launch stream
   roofline_valu -- the same launch against the VALU issue rate (pair-row instruction-lanes / peak)
   cpu_baseline -- the PyTorch-CPU oracle ("port" of the reference's ATen op sequence) timed on this host's cores
@@ -96,7 +103,15 @@ def parse_args(argv=None):
     ap.add_argument("--exchange-sweep", default="basic", choices=["basic", "full"],
                     help="which other protocols get their one timed block: basic = none, per-step, final (blocking collectives on the "
                          "compute stream, the primitive the log's own exchange uses); full = also log / pipelined (asynchronous)")
-    ap.add_argument("--blocks", type=int, default=5, help="timed blocks of --steps steps (the median block is the reported value)")
+    ap.add_argument("--blocks", type=int, default=None,
+                    help="timed blocks of --steps steps (the median block is the reported value); default 1, with --full 5")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything the headline figure does not need: the secondary blocks of rank 0 (instrumented "
+                         "per-kernel pass, rooflines, accuracy, list refresh, drop-in, contract, frames, second order, CPU "
+                         "baseline, host), and with several ranks weak_efficiency and the other exchange protocols")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the timed path computed in its last step (rank 0's frame energies "
+                         "and forces) as DIR/<name>.npy")
     ap.add_argument("--prewarm-ms", type=float, default=30.0, help="untimed replays before the warm-up steps (clock ramp)")
     ap.add_argument("--no-list-refresh", action="store_true")
     ap.add_argument("--neighbors", default="list", choices=["list", "stream"],
@@ -111,6 +126,8 @@ def parse_args(argv=None):
     if args.preset is not None:
         for k, v in PRESETS[args.preset].items():
             setattr(args, k, v)
+    if args.blocks is None:
+        args.blocks = 5 if args.full else 1
     return args
 
 
@@ -941,6 +958,26 @@ def list_refresh_timing(frame, frozen_list_ms: float):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 * 2**20
+
+
+def write_outputs(directory: str, arrays: dict):
+    """``--dump-outputs``: one ``<name>.npy`` per array (float32 / float64 as computed).  Above DUMP_LIMIT_BYTES the forces are cut
+    to a fixed, seeded sample of atoms (the same for every build), whose indices go to ``forces_atom_index.npy``."""
+    os.makedirs(directory, exist_ok=True)
+    arrays = dict(arrays)
+    forces = arrays.get("forces")
+    if forces is not None and sum(a.nbytes for a in arrays.values()) > DUMP_LIMIT_BYTES:
+        per_atom = forces.nbytes // forces.shape[1]
+        room = DUMP_LIMIT_BYTES - sum(a.nbytes for k, a in arrays.items() if k != "forces")
+        n_keep = max(1, min(forces.shape[1], room // (per_atom + 8)))
+        idx = np.sort(np.random.default_rng(2024).choice(forces.shape[1], n_keep, replace=False))
+        arrays["forces"] = np.ascontiguousarray(forces[:, idx])
+        arrays["forces_atom_index"] = idx.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, f"{name}.npy"), a)
+
+
 # ----------------------------------------------------------------------------------------------------------------------
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
@@ -997,6 +1034,13 @@ def main(argv=None):
     def sync():
         if not stub:
             torch.cuda.synchronize()
+
+    def close():
+        if distributed:
+            # every rank is past its last collective before any rank tears its connections down (a rank that exits while a
+            # peer still reads from it can abort that peer)
+            dist.barrier()
+            dist.destroy_process_group()
 
     n_frames = max(1, args.frames_per_gpu)
     if stub:
@@ -1189,7 +1233,8 @@ def main(argv=None):
     E = run_steps(args.warmup)
     dbg("warm-up done")
     t_alone = None
-    if distributed and world > 1 and exchange_mode != "in-graph":  # (an in-graph collective cannot run on one rank alone)
+    # (an in-graph collective cannot run on one rank alone)
+    if args.full and distributed and world > 1 and exchange_mode != "in-graph":
         t_alone, _ = timed_block(args.steps, only_rank0=True)
     block_times = []
     for b in range(max(1, args.blocks)):
@@ -1197,11 +1242,24 @@ def main(argv=None):
         E = Eb if Eb is not None else E
         block_times.append(dt_own)
     dbg("timed loops done")
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from its last step, copied out before anything else runs: the graphs' own
+        # output buffers, or the eager step's results (forces = -dE/dpositions)
+        dumped = {"energy": torch.stack([e.detach().reshape(()) for e in E])}
+        if not stub:
+            if batch is not None:
+                dumped["forces"] = torch.stack(batch.forces)
+            elif graphed is not None:
+                dumped["forces"] = torch.stack([g.forces for g in graphed])
+            else:
+                dumped["forces"] = torch.stack([f.pos.grad for f in frames])
+        dumped = {k: v.detach().cpu().numpy() for k, v in dumped.items()}
     dom_family = "" if stub else dominant_kernel_family()  # (asked NOW: the secondary blocks below launch other variants)
     log_entries = logged["entries"]  # (of the last timed block)
     # the other exchange protocols, one block each, same invocation (reported under parallelism.other_exchange_modes; never `value`)
     other_modes, other_times = [], []
-    if distributed and not args.no_exchange_sweep and exchange_mode != "in-graph":
+    if args.full and distributed and not args.no_exchange_sweep and exchange_mode != "in-graph":
         sweep = ("none", "log", "per-step", "pipelined", "final") if args.exchange_sweep == "full" else ("none", "per-step", "final")
         for m in sweep:
             if m == exchange_mode or (m == "log" and exchange_mode == "in-graph"):
@@ -1236,7 +1294,7 @@ def main(argv=None):
     blocks_ms = [1e3 * v / args.steps for v in per_block]
     value = world * n_frames * w.n_atoms * args.steps / elapsed
     weak_efficiency = None
-    if t_alone is not None or (distributed and world > 1):
+    if t_alone is not None or (args.full and distributed and world > 1):
         t1 = float(gathered[0, -1])
         weak_efficiency = {
             "value": t1 / elapsed if elapsed > 0 else None,
@@ -1284,6 +1342,8 @@ def main(argv=None):
     }
     ms_per_step_median = float(np.median(blocks_ms))
 
+    if dumped is not None:
+        write_outputs(args.dump_outputs, dumped)
     if stub:
         if rank == 0:
             print(json.dumps({
@@ -1297,8 +1357,58 @@ def main(argv=None):
                 "ms_per_step_median": ms_per_step_median, "ms_per_step_first_block": ms_per_step_first_block, "timing": timing,
                 "weak_efficiency": weak_efficiency,
             }))
-        if distributed:
-            dist.destroy_process_group()
+        close()
+        return
+
+    line = None
+    if rank == 0:
+        n_parts = plane_parts(w, s) if args.neighbors == "list" else 0
+        if "plane" not in dom_family:  # what RAN decides (mipme_last_cosched_kernel), not what the geometry would allow
+            n_parts = 0
+        # a frame batch (GraphedFrameBatch) keeps its plane workgroups at <= 128 per launch (csrc/bricks.hip frames_forward_t)
+        label_parts = n_parts
+        while batch is not None and label_parts > 1 and label_parts * w.n_mesh * n_frames > 128:
+            label_parts -= 1
+        line = {
+            "metric": "atom-steps/sec (energy+forces)",
+            "value": value,
+            "unit": "atom-steps/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": ms_per_step,
+            "ms_per_step_median": ms_per_step_median,
+            "ms_per_step_first_block": ms_per_step_first_block,
+            "value_median": world * n_frames * w.n_atoms / (ms_per_step_median * 1e-3),
+            "timing": timing,
+            "weak_efficiency": weak_efficiency,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": w.dtype,
+            "data": "synthetic",
+            "config": {
+                "workload": f"{w.name}: {w.n_atoms} atoms, {w.n_pairs} half pairs (rc={w.cutoff} A), "
+                            f"{w.scheme} order {w.order}, {w.n_mesh}^3 mesh, "
+                            f"{'Coulomb' if w.exponent == 1 else '1/r^%d' % w.exponent}, {w.dtype}, energy+forces via autograd",
+                "preset": args.preset,
+                "frames_per_gpu": n_frames,
+                "neighbors": args.neighbors,
+                "spread": (f"plane spread, {label_parts} workgroup(s) per x plane -- per band of rows where a plane's tile does not fit "
+                           "the launch's LDS (128 x 128: z transform in the tile, y columns as a launch of their own) -- (charges "
+                           "into the forward plane transform's LDS tiles; no forward plane launch)" if n_parts > 0 else "owner-computes bricks + forward plane launch"),
+                "launch": ("HIP graph replay of the captured step"
+                           + (", all frames in one launch per kernel (GraphedFrameBatch)" if batch is not None
+                              else ", one stream per frame" if streams is not None else ""))
+                          if launch == "graph" else "eager kernel launches",
+                "parallelism": f"{world * n_frames} independent frame(s), {n_frames} per GPU, {world} rank(s)",
+            },
+            "parallelism": parallelism,
+        }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(line))
+        close()
         return
 
     # ---- instrumented pass: per-call HIP-event timings on the launch stream (does not affect `value`) ----
@@ -1347,13 +1457,6 @@ def main(argv=None):
 
     if rank == 0:
         # (the per-kernel stage times below are those of ONE frame's step whatever the number of frames per GPU)
-        n_parts = plane_parts(w, s) if args.neighbors == "list" else 0
-        if "plane" not in dom_family:  # what RAN decides (mipme_last_cosched_kernel), not what the geometry would allow
-            n_parts = 0
-        # a frame batch (GraphedFrameBatch) keeps its plane workgroups at <= 128 per launch (csrc/bricks.hip frames_forward_t)
-        label_parts = n_parts
-        while batch is not None and label_parts > 1 and label_parts * w.n_mesh * n_frames > 128:
-            label_parts -= 1
         step_bytes, per_kernel = algorithmic_bytes(w, s, fused=ops.FUSE_DISTANCES, store_distances=args.store_distances,
                                                    parts=n_parts)
         kernels = {k: v for k, v in prof.items() if k in per_kernel}
@@ -1385,41 +1488,8 @@ def main(argv=None):
             for k, v in sorted(kernels.items(), key=lambda kv: -kv[1])
         }
         moved = sum(per_kernel[k] * stage_calls.get(k, 1.0) for k in kernels)
-        out = {
-            "metric": "atom-steps/sec (energy+forces)",
-            "value": value,
-            "unit": "atom-steps/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": ms_per_step,
-            "ms_per_step_median": ms_per_step_median,
-            "ms_per_step_first_block": ms_per_step_first_block,
-            "value_median": world * n_frames * w.n_atoms / (ms_per_step_median * 1e-3),
-            "timing": timing,
-            "weak_efficiency": weak_efficiency,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": w.dtype,
-            "data": "synthetic",
-            "config": {
-                "workload": f"{w.name}: {w.n_atoms} atoms, {w.n_pairs} half pairs (rc={w.cutoff} A), "
-                            f"{w.scheme} order {w.order}, {w.n_mesh}^3 mesh, "
-                            f"{'Coulomb' if w.exponent == 1 else '1/r^%d' % w.exponent}, {w.dtype}, energy+forces via autograd",
-                "preset": args.preset,
-                "frames_per_gpu": n_frames,
-                "neighbors": args.neighbors,
-                "spread": (f"plane spread, {label_parts} workgroup(s) per x plane -- per band of rows where a plane's tile does not fit "
-                           "the launch's LDS (128 x 128: z transform in the tile, y columns as a launch of their own) -- (charges "
-                           "into the forward plane transform's LDS tiles; no forward plane launch)" if n_parts > 0 else "owner-computes bricks + forward plane launch"),
-                "launch": ("HIP graph replay of the captured step"
-                           + (", all frames in one launch per kernel (GraphedFrameBatch)" if batch is not None
-                              else ", one stream per frame" if streams is not None else ""))
-                          if launch == "graph" else "eager kernel launches",
-                "parallelism": f"{world * n_frames} independent frame(s), {n_frames} per GPU, {world} rank(s)",
-            },
-            "parallelism": parallelism,
+        out = line
+        out.update({
             "host": host_identification(),
             "roofline": {
                 "bound": "hbm",
@@ -1456,7 +1526,7 @@ def main(argv=None):
             "abi_call_ms": prof,
             "energy": float(E[0].item()),
             "accuracy": accuracy,
-        }
+        })
         if world == 1 and n_frames == 1 and not args.no_list_refresh:
             try:
                 out["list_refresh"] = list_refresh_timing(frame, ms_per_step_median)
@@ -1485,8 +1555,7 @@ def main(argv=None):
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(w)
         print(json.dumps(out))
-    if distributed:
-        dist.destroy_process_group()
+    close()
 
 
 if __name__ == "__main__":

@@ -10,6 +10,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -44,7 +45,7 @@ def test_exchange_modes_gather_the_same_energies():
     sums = {}
     for mode in ("log", "per-step", "pipelined", "final"):
         out = _run("--gpus", "2", "--steps", "4", "--warmup", "1", "--frames-per-gpu", "2", "--blocks", "2", "--exchange", mode,
-                   "--exchange-sweep", "full")
+                   "--exchange-sweep", "full", "--full")
         assert out["parallelism"]["exchange"] == mode and out["energies_gathered"] == 4
         assert out["timing"]["blocks"] == 2 and len(out["timing"]["blocks_ms_per_step"]) == 2
         # (the reported timed region is the median block -- the lower one of two --, the first block is reported next to it)
@@ -61,7 +62,7 @@ def test_exchange_modes_gather_the_same_energies():
             assert out["parallelism"]["log_entries_gathered"] == 16
     assert sums["per-step"] == pytest.approx(sums["final"], rel=1e-12) == pytest.approx(sums["pipelined"], rel=1e-12)
     assert sums["log"] == pytest.approx(sums["final"], rel=1e-12)
-    out = _run("--gpus", "2", "--steps", "2", "--warmup", "1", "--no-exchange-sweep")
+    out = _run("--gpus", "2", "--steps", "2", "--warmup", "1", "--no-exchange-sweep", "--full")
     assert out["parallelism"]["exchange"] == "log"  # the default with more than one rank
     assert out["parallelism"]["other_exchange_modes_ms_per_step"] == {}
 
@@ -70,7 +71,7 @@ def test_eight_ranks_cfg4_preset():
     """BASELINE.json configs[3] as the driver will launch it on an 8-GPU node -- ``bench.py --gpus 8 --preset cfg4`` -- on eight CPU
     ranks (gloo, stub evaluator): rank binding, the one exchange of the 8 x 2 x 8 logged frame energies inside the timed region and
     ``weak_efficiency`` are all exercised; only the evaluator and the fabric differ from the real run."""
-    out = _run("--gpus", "8", "--preset", "cfg4", "--steps", "2", "--warmup", "1", "--blocks", "1")
+    out = _run("--gpus", "8", "--preset", "cfg4", "--steps", "2", "--warmup", "1", "--blocks", "1", "--full")
     assert out["n_gpus"] == 8 and out["parallelism"]["n_ranks"] == 8
     assert out["energies_gathered"] == 64 and out["config"]["frames_per_gpu"] == 8
     assert out["parallelism"]["exchange"] == "log" and out["parallelism"]["log_entries_gathered"] == 8 * 2 * 8
@@ -79,6 +80,22 @@ def test_eight_ranks_cfg4_preset():
     assert len(out["parallelism"]["per_rank_ms_per_step"]) == 8
     assert sorted(r["rank"] for r in out["parallelism"]["ranks"]) == list(range(8))
     assert out["weak_efficiency"]["value"] > 0
+
+
+def test_plain_run_times_exactly_the_steps_and_dumps_outputs(tmp_path):
+    """Without --full: ONE timed block of exactly --steps steps, none of the secondary blocks, and --dump-outputs writes the last
+    timed step's frame energies (rank 0's) as float64 .npy files, the same from run to run."""
+    dumps = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        out = _run("--gpus", "2", "--steps", "3", "--warmup", "1", "--frames-per-gpu", "2", "--dump-outputs", str(d))
+        assert out["steps"] == 3 and out["timing"]["blocks"] == 1 and len(out["timing"]["blocks_ms_per_step"]) == 1
+        assert out["ms_per_step"] == pytest.approx(out["timing"]["blocks_ms_per_step"][0], rel=1e-4)
+        assert out["weak_efficiency"] is None and out["parallelism"]["other_exchange_modes_ms_per_step"] == {}
+        e = np.load(d / "energy.npy")
+        assert e.dtype == np.float64 and e.shape == (2,)
+        dumps.append(e)
+    assert np.array_equal(dumps[0], dumps[1])
 
 
 def test_single_rank_default():

@@ -1,7 +1,8 @@
 # A/B of two builds of the library on ONE box: torch-pme_amd/libmipme_<name>.so (tools/build_variant.sh, or a build of another
 # tree copied there) against the in-tree libmipme.so.   bash tools/ab_lib.sh old   [PRESETS="cfg3 cfg5" REPS=2]
 NAME=$1
-mkdir -p gpurun_out/ab
+AB=${AB_DIR:-bench_out/ab}
+mkdir -p $AB
 M=$PWD/torch-pme_amd/libmipme_$NAME.so
 py() { python -c "
 import json,sys
@@ -11,7 +12,7 @@ print(sys.argv[2], round(d['ms_per_step'],5), round(d['ms_per_step_median'],5), 
 " $1 $2; }
 for preset in ${PRESETS:-cfg3 cfg5 cfg4 cfg2}; do
   for rep in $(seq 1 ${REPS:-2}); do
-    MIPME_LIB=$M python bench.py --preset $preset --no-drop-in --no-cpu-baseline --no-list-refresh > gpurun_out/ab/${preset}_${NAME}_$rep.json 2>/dev/null; py gpurun_out/ab/${preset}_${NAME}_$rep.json ${preset}_${NAME}
-    python bench.py --preset $preset --no-drop-in --no-cpu-baseline --no-list-refresh > gpurun_out/ab/${preset}_head_$rep.json 2>/dev/null; py gpurun_out/ab/${preset}_head_$rep.json ${preset}_head
+    MIPME_LIB=$M python bench.py --full --preset $preset --no-drop-in --no-cpu-baseline --no-list-refresh > $AB/${preset}_${NAME}_$rep.json 2>/dev/null; py $AB/${preset}_${NAME}_$rep.json ${preset}_${NAME}
+    python bench.py --full --preset $preset --no-drop-in --no-cpu-baseline --no-list-refresh > $AB/${preset}_head_$rep.json 2>/dev/null; py $AB/${preset}_head_$rep.json ${preset}_head
   done
 done

@@ -1,6 +1,7 @@
 # Several builds of the library on ONE box:  bash tools/ab_multi.sh old idx brk   (torch-pme_amd/libmipme_<name>.so each, then the
 # in-tree libmipme.so as "head"); PRESETS / REPS as in tools/ab_lib.sh
-mkdir -p gpurun_out/ab
+AB=${AB_DIR:-bench_out/ab}
+mkdir -p $AB
 py() { python -c "
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
@@ -11,7 +12,7 @@ for preset in ${PRESETS:-cfg3 cfg2}; do
   for rep in $(seq 1 ${REPS:-2}); do
     for name in "$@" head; do
       if [ $name = head ]; then L=$PWD/torch-pme_amd/libmipme.so; else L=$PWD/torch-pme_amd/libmipme_$name.so; fi
-      MIPME_LIB=$L python bench.py --preset $preset --no-drop-in --no-cpu-baseline --no-list-refresh ${BENCH_ARGS:-} > gpurun_out/ab/${preset}_${name}_$rep.json 2>/dev/null; py gpurun_out/ab/${preset}_${name}_$rep.json ${preset}_${name}
+      MIPME_LIB=$L python bench.py --full --preset $preset --no-drop-in --no-cpu-baseline --no-list-refresh ${BENCH_ARGS:-} > $AB/${preset}_${name}_$rep.json 2>/dev/null; py $AB/${preset}_${name}_$rep.json ${preset}_${name}
     done
   done
 done

@@ -1,4 +1,5 @@
-mkdir -p gpurun_out/ab
+AB=${AB_DIR:-bench_out/ab}
+mkdir -p $AB
 M=$PWD/torch-pme_amd/libmipme_masked.so
 py() { python -c "
 import json,sys
@@ -9,8 +10,8 @@ print(sys.argv[2], round(d['ms_per_step'],5), round(d['ms_per_step_median'],5), 
 for args in "" "--preset cfg5" "--preset cfg4" "--preset cfg2"; do
   tag=$(echo "$args" | tr -d ' -')
   for rep in 1 2; do
-    MIPME_LIB=$M python bench.py $args --no-drop-in --no-cpu-baseline --no-list-refresh > gpurun_out/ab/s_${tag}_old_$rep.json 2>/dev/null; py gpurun_out/ab/s_${tag}_old_$rep.json "${tag:-cfg3}_old"
-    python bench.py $args --no-drop-in --no-cpu-baseline --no-list-refresh > gpurun_out/ab/s_${tag}_new_$rep.json 2>/dev/null; py gpurun_out/ab/s_${tag}_new_$rep.json "${tag:-cfg3}_new"
+    MIPME_LIB=$M python bench.py --full $args --no-drop-in --no-cpu-baseline --no-list-refresh > $AB/s_${tag}_old_$rep.json 2>/dev/null; py $AB/s_${tag}_old_$rep.json "${tag:-cfg3}_old"
+    python bench.py --full $args --no-drop-in --no-cpu-baseline --no-list-refresh > $AB/s_${tag}_new_$rep.json 2>/dev/null; py $AB/s_${tag}_new_$rep.json "${tag:-cfg3}_new"
   done
 done
 echo rows alone; MIPME_LIB=$M python tools/time_rows.py 2>&1 | grep "4-byte"; python tools/time_rows.py 2>&1 | grep "4-byte"

@@ -8,7 +8,7 @@ mkdir -p gpurun_out
 run() {
   echo "== N=$N $*"
   env MIPME_FORCE_DIST=1 MIPME_BENCH_DEBUG=1 HSA_ENABLE_IPC_MODE_LEGACY=0 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N \
-      --master-addr 127.0.0.1 --master-port $((29600 + RANDOM % 300)) bench.py --gpus $N --steps 100 --warmup 10 --no-cpu-baseline \
+      --master-addr 127.0.0.1 --master-port $((29600 + RANDOM % 300)) bench.py --gpus $N --steps 100 --warmup 10 --full --no-cpu-baseline \
       --no-drop-in "$@" 2>gpurun_out/dist_tmp.err | grep '^{' | python -c "
 import json,sys
 t=sys.stdin.read()

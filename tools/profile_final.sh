@@ -11,23 +11,23 @@ cd $ROOT
 bash tools/profile_gpu.sh ${TAG} --steps 200 --warmup 10
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_WAIT_INST_ANY SQ_WAIT_ANY \
-  -d $OUT/${TAG}_sq -o s -- python $ROOT/bench.py --no-cpu-baseline --no-drop-in --steps 5 --warmup 2 > /dev/null 2> $OUT/${TAG}_sq.err
+  -d $OUT/${TAG}_sq -o s -- python $ROOT/bench.py --full --no-cpu-baseline --no-drop-in --steps 5 --warmup 2 > /dev/null 2> $OUT/${TAG}_sq.err
 cd $ROOT
 python tools/rocpd_summary.py $(find $OUT/${TAG}_sq -name '*.db') > $OUT/${TAG}_sq_counters.txt
 rm -rf $OUT/${TAG}_sq
 bash tools/calib_gpu.sh ${TAG}
-python bench.py --steps 500 --warmup 20 > $OUT/${TAG}_bench_default.json 2> $OUT/${TAG}_bench_default.err
-python bench.py --preset cfg2 --steps 300 --warmup 20 --no-drop-in > $OUT/${TAG}_bench_ionic_cfg2.json 2>> $OUT/${TAG}_bench_default.err
-python bench.py --preset cfg4 --steps 200 --warmup 20 --no-drop-in --no-cpu-baseline > $OUT/${TAG}_bench_cfg4_8frames_1gpu.json 2>> $OUT/${TAG}_bench_default.err
-python bench.py --preset cfg4 --frame-batch streams --steps 200 --warmup 20 --no-drop-in --no-cpu-baseline > $OUT/${TAG}_bench_cfg4_streams.json 2>> $OUT/${TAG}_bench_default.err
-python bench.py --preset cfg5 --steps 100 --warmup 10 --no-drop-in > $OUT/${TAG}_bench_dispersion_cfg5.json 2>> $OUT/${TAG}_bench_default.err
-python bench.py --launch eager --steps 200 --warmup 20 --no-drop-in --no-cpu-baseline > $OUT/${TAG}_bench_eager.json 2>> $OUT/${TAG}_bench_default.err
+python bench.py --full --steps 500 --warmup 20 > $OUT/${TAG}_bench_default.json 2> $OUT/${TAG}_bench_default.err
+python bench.py --full --preset cfg2 --steps 300 --warmup 20 --no-drop-in > $OUT/${TAG}_bench_ionic_cfg2.json 2>> $OUT/${TAG}_bench_default.err
+python bench.py --full --preset cfg4 --steps 200 --warmup 20 --no-drop-in --no-cpu-baseline > $OUT/${TAG}_bench_cfg4_8frames_1gpu.json 2>> $OUT/${TAG}_bench_default.err
+python bench.py --full --preset cfg4 --frame-batch streams --steps 200 --warmup 20 --no-drop-in --no-cpu-baseline > $OUT/${TAG}_bench_cfg4_streams.json 2>> $OUT/${TAG}_bench_default.err
+python bench.py --full --preset cfg5 --steps 100 --warmup 10 --no-drop-in > $OUT/${TAG}_bench_dispersion_cfg5.json 2>> $OUT/${TAG}_bench_default.err
+python bench.py --full --launch eager --steps 200 --warmup 20 --no-drop-in --no-cpu-baseline > $OUT/${TAG}_bench_eager.json 2>> $OUT/${TAG}_bench_default.err
 python tools/size_sweep.py > $OUT/${TAG}_size_sweep.txt 2>&1
 python tools/frames_probe.py > $OUT/${TAG}_frames_probe.txt 2>&1
 python tools/time_stress.py > $OUT/${TAG}_stress.txt 2>&1
 ls -la $OUT | grep ${TAG}
 # round 3: device neighbour stream + live-bin step
-python bench.py --neighbors stream --steps 500 --warmup 20 --no-drop-in --no-cpu-baseline > $OUT/${TAG}_bench_stream.json 2>> $OUT/${TAG}_bench_default.err
+python bench.py --full --neighbors stream --steps 500 --warmup 20 --no-drop-in --no-cpu-baseline > $OUT/${TAG}_bench_stream.json 2>> $OUT/${TAG}_bench_default.err
 python tools/time_refresh.py > $OUT/${TAG}_refresh.txt 2>&1
 (cd /tmp && rocprofv3 --kernel-trace --stats -d $OUT/${TAG}_live -o l -- python $ROOT/tools/prof_live.py > /dev/null 2>&1)
 python tools/rocpd_summary.py $(find $OUT/${TAG}_live -name '*.db') > $OUT/${TAG}_kernel_stats_live_step.txt
@@ -40,7 +40,7 @@ python tools/prof_size.py 56 256 > /dev/null 2>&1 || true
 ls -la $OUT | grep ${TAG}
 # kernel traces of the fp64 configurations and of the reference call sequence
 for cfg in cfg2 cfg4; do
-  (cd /tmp && rocprofv3 --kernel-trace --stats -d $OUT/${TAG}_$cfg -o t -- python $ROOT/bench.py --preset $cfg --steps 100 --warmup 10 --no-drop-in --no-cpu-baseline > /dev/null 2>&1)
+  (cd /tmp && rocprofv3 --kernel-trace --stats -d $OUT/${TAG}_$cfg -o t -- python $ROOT/bench.py --full --preset $cfg --steps 100 --warmup 10 --no-drop-in --no-cpu-baseline > /dev/null 2>&1)
   python tools/rocpd_summary.py $(find $OUT/${TAG}_$cfg -name '*.db') > $OUT/${TAG}_kernel_stats_$cfg.txt
   rm -rf $OUT/${TAG}_$cfg
 done
@@ -72,7 +72,7 @@ ls -la $OUT | grep ${TAG}
 bash tools/profile_gpu.sh ${TAG}_cfg5 --preset cfg5 --steps 50 --warmup 5
 cd /tmp
 rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_WAIT_INST_ANY SQ_WAIT_ANY \
-  -d $OUT/${TAG}_sq5 -o s -- python $ROOT/bench.py --preset cfg5 --no-cpu-baseline --no-drop-in --steps 5 --warmup 2 > /dev/null 2> $OUT/${TAG}_sq5.err
+  -d $OUT/${TAG}_sq5 -o s -- python $ROOT/bench.py --full --preset cfg5 --no-cpu-baseline --no-drop-in --steps 5 --warmup 2 > /dev/null 2> $OUT/${TAG}_sq5.err
 cd $ROOT
 python tools/rocpd_summary.py $(find $OUT/${TAG}_sq5 -name '*.db') > $OUT/${TAG}_sq_counters_cfg5.txt
 rm -rf $OUT/${TAG}_sq5

@@ -1,7 +1,7 @@
 #!/bin/bash
 # cfg5 (262 144 atoms, 128^3, 1/r^6): planes spread in BANDS of 32 rows co-scheduled with the pair sum (+ a y-column launch)
 # against the owner-computes bricks + forward plane launch (MIPME_PLANE_BANDS=0), same box, interleaved
-FLAGS="--preset cfg5 --steps 100 --warmup 10 --no-cpu-baseline --no-drop-in --no-contract --no-frames-block --no-second-order --no-list-refresh"
+FLAGS="--full --preset cfg5 --steps 100 --warmup 10 --no-cpu-baseline --no-drop-in --no-contract --no-frames-block --no-second-order --no-list-refresh"
 py() { python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])

@@ -2,7 +2,7 @@
 # Eager call sequences (drop_in block of bench.py) of two trees on ONE box, interleaved: has the host path of round 6 regressed
 # against round 5's, or do the boxes differ?   bash tools/r06/ab_eager.sh <other tree>   (e.g. a worktree of 9236903 copied in)
 OTHER=$1
-FLAGS="--steps 200 --warmup 20 --no-cpu-baseline --no-contract --no-frames-block --no-second-order --no-list-refresh"
+FLAGS="--full --steps 200 --warmup 20 --no-cpu-baseline --no-contract --no-frames-block --no-second-order --no-list-refresh"
 py() { python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); di=d['drop_in']

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Where do the 3 % between `python bench.py` and the same step under torch.distributed.run (one rank, nccl) come from?
 # Same box, back to back: plain / bound to cores / process group without the launcher / launcher with and without binding.
-FLAGS="--steps 500 --warmup 20 --no-cpu-baseline --no-drop-in --no-contract --no-frames-block --no-second-order --no-list-refresh --no-exchange-sweep"
+FLAGS="--full --steps 500 --warmup 20 --no-cpu-baseline --no-drop-in --no-contract --no-frames-block --no-second-order --no-list-refresh --no-exchange-sweep"
 ms() { grep '^{' | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(round(d['ms_per_step'],5), [round(x,5) for x in d['timing']['blocks_ms_per_step']], d['parallelism']['exchange'], (d['parallelism']['ranks'][0] or {}).get('affinity'))"; }
 for rep in 1 2; do
 echo "plain            $(python bench.py $FLAGS 2>/dev/null | ms)"
