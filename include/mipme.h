@@ -677,6 +677,54 @@ int mipme_ewald_backward(void* stream, int dtype, int64_t n_atoms, int n_channel
                          const void* s_cos, const void* s_sin, const void* t_cos, const void* t_sin,
                          void* grad_positions, void* grad_kvectors, int64_t n_batch);
 
+/* ---- point dipoles: CalculatorDipole, calculators/calculator_dipole.py; PotentialDipole, potentials/potential_dipole.py --
+ * Dipoles mu (N,3), output "potential" V (N,3), energy sum_i mu_i . V_i.  Its own descriptor: the entry points that take
+ * a mipme_potential_t read every kind other than MIPME_COULOMB as an inverse power law, so dipoles are not a kind there.
+ * Real space, pair p = (i,j), r = neighbor_vectors[p] (P,3), T(r) = prefactor (B I - C r r^T):
+ *   smearing <= 0: B = 1/r^3, C = 3/r^5 (from_dist);  else the short-range part (sr_from_dist), or with an exclusion radius
+ *   -f_c(r) T_lr(r) (f_c = 1 - ((1 - cos(pi r/r_ex))/2)^n inside r_ex, 0 beyond)
+ *   mipme_dipole_rspace_forward   out[i] = 1/2 sum_p T mu_j (+ the (j,i) term for a half list)              (OVERWRITES)
+ *   mipme_dipole_rspace_backward  for L = sum_i grad_out_i . out_i: grad_dipoles (N,3) and grad_vectors (P,3), either
+ *                                 nullable (grad_dipoles is the forward sum applied to grad_out: T is symmetric)
+ * Reciprocal space, caller-supplied k-vectors (K,3), G / dG (K) from mipme_ewald_filter with a MIPME_COULOMB descriptor of
+ * the same smearing and prefactor (4 pi prefactor exp(-sigma^2 k^2/2)/k^2 is Coulomb's kernel); s_* / t_* (K):
+ *   mipme_dipole_structure  out_cos[k] = sum_j (w_j.k) cos(k r_j), out_sin likewise   (w = dipoles, or grad_out)
+ *   mipme_dipole_field      out[i] = sum_k G k (cos(k r_i) s_cos + sin(k r_i) s_sin)  (N,3), no 1/V; OVERWRITES
+ *   mipme_dipole_backward   with S = structure(dipoles), T = structure(grad_out):
+ *        grad_positions[i] = sum_k G k [ (g_i.k)(cos S_sin - sin S_cos) + (mu_i.k)(cos T_sin - sin T_cos) ]
+ *        grad_kvectors[k]  = 2 dG k (T.S) + G sum_i [ g_i (cos S_cos + sin S_sin) + mu_i (cos T_cos + sin T_sin)
+ *                                                     + r_i ((g_i.k)(cos S_sin - sin S_cos) + (mu_i.k)(cos T_sin - sin T_cos)) ]
+ *        (either output nullable; the dipole gradient is mipme_dipole_field with T in place of S)
+ * G and dG are nullable in mipme_dipole_structure: given, k-vectors where both are exactly 0 are skipped (their
+ * structure factors are written as 0).  mipme_dipole_field / _backward skip k-vectors with G = 0 in the same way.
+ * With few atoms the per-atom kernels split the k-vectors into slices and reduce the partial sums in a fixed order:
+ * `partials` is device scratch of mipme_dipole_partials_size(n_atoms, n_k) reals (0: none needed, may be NULL). */
+typedef struct {
+  double smearing;          /* sigma; <= 0 means None: the bare dipolar tensor, no k-space part */
+  double prefactor;
+  double exclusion_radius;  /* <= 0 means None */
+  int32_t exclusion_degree;
+  int32_t _pad;
+} mipme_dipole_t;
+int mipme_dipole_rspace_forward(void* stream, int dtype, int index_dtype, int64_t n_atoms, int64_t n_pairs,
+                                int full_list, const void* neighbor_indices, const void* neighbor_vectors,
+                                const void* dipoles, const mipme_dipole_t* pot, void* out);
+int mipme_dipole_rspace_backward(void* stream, int dtype, int index_dtype, int64_t n_atoms, int64_t n_pairs,
+                                 int full_list, const void* neighbor_indices, const void* neighbor_vectors,
+                                 const void* dipoles, const void* grad_out, const mipme_dipole_t* pot,
+                                 void* grad_dipoles, void* grad_vectors);
+int64_t mipme_dipole_partials_size(int64_t n_atoms, int64_t n_k);
+int mipme_dipole_structure(void* stream, int dtype, int64_t n_atoms, int64_t n_k, const void* positions,
+                           const void* weights, const void* kvectors, const void* G, const void* dG, void* out_cos,
+                           void* out_sin);
+int mipme_dipole_field(void* stream, int dtype, int64_t n_atoms, int64_t n_k, const void* positions,
+                       const void* kvectors, const void* G, const void* s_cos, const void* s_sin, void* out,
+                       void* partials);
+int mipme_dipole_backward(void* stream, int dtype, int64_t n_atoms, int64_t n_k, const void* positions,
+                          const void* dipoles, const void* grad_out, const void* kvectors, const void* G, const void* dG,
+                          const void* s_cos, const void* s_sin, const void* t_cos, const void* t_sin,
+                          void* grad_positions, void* grad_kvectors, void* partials);
+
 /* ---- device neighbour list (the reference uses third-party vesin on the host,
  * tests/helpers.py:240-275, and hands a fresh list to every call, examples/02-neighbor-lists-usage.py:97-164) -------------
  * One cell-list traversal, two products:

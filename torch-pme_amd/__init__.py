@@ -9,6 +9,7 @@ repository root).  All compute runs in ``libmipme.so`` (hand-written HIP, C-ABI 
 from . import lib, library, ops, prefactors, tuning, workloads  # noqa: F401  (library registers the torch.ops.mipme ops)
 from ._lib import LIB_PATH, MipmeError  # noqa: F401
 from .calculators import Calculator, EwaldCalculator, P3MCalculator, PMECalculator
+from .dipoles import CalculatorDipole, PotentialDipole
 from .graphed import EnergyLog, GraphedEnergyForces, GraphedFrameBatch
 from .neighbors import NeighborStream, neighbor_list, neighbor_list_device
 from .ops import pair_distances, weighted_sum
@@ -19,12 +20,14 @@ __version__ = "0.1.0"
 
 __all__ = [
     "Calculator",
+    "CalculatorDipole",
     "EwaldCalculator",
     "P3MCalculator",
     "PMECalculator",
     "CoulombPotential",
     "InversePowerLawPotential",
     "Potential",
+    "PotentialDipole",
     "pair_distances",
     "weighted_sum",
     "EnergyLog",

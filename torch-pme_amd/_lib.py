@@ -37,6 +37,8 @@ EXPORTS = (
     "mipme_scaled_match", "mipme_scaled_match_work", "mipme_scaled_match_wide", "mipme_md_supported", "mipme_md_lists_ints", "mipme_md_rebin", "mipme_md_step", "mipme_set_skip_flag", "mipme_energy_select", "mipme_energy_select_sum", "mipme_energy_select_contract",
     "mipme_kfilter_build_deriv", "mipme_cell_tail_work", "mipme_values_equal", "mipme_checksum", "mipme_checksum_words",
     "mipme_spread_jet", "mipme_gather_jet", "mipme_gather_jet3", "mipme_pair_sum", "mipme_pair_sum_rows", "mipme_pair_dot", "mipme_pair_diff", "mipme_pair_scatter",
+    "mipme_dipole_rspace_forward", "mipme_dipole_rspace_backward", "mipme_dipole_partials_size", "mipme_dipole_structure",
+    "mipme_dipole_field", "mipme_dipole_backward",
 )
 
 
@@ -44,6 +46,18 @@ class PotentialDesc(C.Structure):
     _fields_ = [
         ("kind", C.c_int32),
         ("exponent", C.c_int32),
+        ("smearing", C.c_double),
+        ("prefactor", C.c_double),
+        ("exclusion_radius", C.c_double),
+        ("exclusion_degree", C.c_int32),
+        ("_pad", C.c_int32),
+    ]
+
+
+class DipoleDesc(C.Structure):
+    """``mipme_dipole_t``: the dipolar pair tensor (its own descriptor, not a kind of ``mipme_potential_t``)."""
+
+    _fields_ = [
         ("smearing", C.c_double),
         ("prefactor", C.c_double),
         ("exclusion_radius", C.c_double),
@@ -268,6 +282,11 @@ def _declare(lib):
         "mipme_ewald_structure": [vp, ci, i64, ci, i64, vp, vp, vp, vp, vp, i64],
         "mipme_ewald_potential": [vp, ci, i64, ci, i64, vp, vp, vp, vp, vp, vp, i64],
         "mipme_ewald_backward": [vp, ci, i64, ci, i64] + [vp] * 12 + [i64],
+        "mipme_dipole_rspace_forward": [vp, ci, ci, i64, i64, ci, vp, vp, vp, C.POINTER(DipoleDesc), vp],
+        "mipme_dipole_rspace_backward": [vp, ci, ci, i64, i64, ci, vp, vp, vp, vp, C.POINTER(DipoleDesc), vp, vp],
+        "mipme_dipole_structure": [vp, ci, i64, i64] + [vp] * 7,
+        "mipme_dipole_field": [vp, ci, i64, i64] + [vp] * 7,
+        "mipme_dipole_backward": [vp, ci, i64, i64] + [vp] * 13,
         "mipme_dot_forward": [vp, ci, i64, vp, vp, vp, vp],
         "mipme_dot_backward": [vp, ci, i64, vp, vp, vp, vp, vp],
         "mipme_energy_log_push": [vp, ci, ci, vp, vp, vp, ci],
@@ -294,6 +313,8 @@ def _declare(lib):
         fn.argtypes = argtypes
     lib.mipme_cellgrad_partials_size.restype = i64
     lib.mipme_cellgrad_partials_size.argtypes = [MP, i64]
+    lib.mipme_dipole_partials_size.restype = i64
+    lib.mipme_dipole_partials_size.argtypes = [i64, i64]
     lib.mipme_pair_partials_size.restype = i64
     lib.mipme_pair_partials_size.argtypes = [i64]
     lib.mipme_topology_workspace_bytes.restype = i64

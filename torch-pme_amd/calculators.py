@@ -507,6 +507,26 @@ def _reciprocal_and_det(cell: torch.Tensor):
     return torch.stack((bc, ca, ab), dim=-2) / det[..., None, None], det
 
 
+def _integer_frequencies(cell: torch.Tensor, lr_wavelength: float, cache=None):
+    """Integer frequencies (K,3) of all k-vectors with wavelength ``>= lr_wavelength``: ``fftfreq(ns_d) * ns_d`` per axis,
+    ``ns_d = ceil(|a_d| / lr_wavelength)``, x-major order, the zero vector first.  The mesh size needs the cell on the host
+    (as in the reference, ``ewald.py:88-93``).  ``cache`` is what the previous call returned for the same owner: returns
+    ``(frequencies, cache)``, reusing the table while the cell tensor, its version, device and the wavelength are the same."""
+    c = cache
+    if c is not None and c[0]() is cell and c[1] == cell._version and c[2] == cell.device and c[3] == lr_wavelength:
+        return c[4], c
+    cell_host = cell.detach().to("cpu", torch.float64).numpy()
+    det = float(np.linalg.det(cell_host))
+    if det == 0.0 or not np.isfinite(det):  # the cross-product inverse would quietly produce inf / NaN k-vectors
+        raise ValueError(f"provided `cell` has a determinant of {det}, i.e. it is not a valid unit cell")
+    norms = np.linalg.norm(cell_host, axis=1)
+    ns = np.ceil(norms / lr_wavelength).astype(np.int64)
+    f = [np.fft.fftfreq(int(n)) * int(n) for n in ns]
+    F = np.stack(np.meshgrid(*f, indexing="ij"), axis=-1).reshape(-1, 3)
+    freq = torch.tensor(F, dtype=cell.dtype, device=cell.device)
+    return freq, (weakref.ref(cell), cell._version, cell.device, lr_wavelength, freq)
+
+
 class EwaldCalculator(Calculator):
     r"""Ewald summation: real-space pair sum + explicit reciprocal-space sum over all k-vectors with wavelength
     ``>= lr_wavelength`` (reference ``calculators/ewald.py:8-142``).  O(N K); meant for small cells.
@@ -535,22 +555,8 @@ class EwaldCalculator(Calculator):
         self._spec()
 
     def _frequencies(self, cell: torch.Tensor) -> torch.Tensor:
-        """Integer frequencies (K,3) of all k-vectors: ``fftfreq(ns_d) * ns_d`` per axis, ``ns_d = ceil(|a_d| /
-        lr_wavelength)``, x-major order, the zero vector first.  The mesh size needs the cell on the host (as in the
-        reference, ``ewald.py:88-93``); cached per cell tensor."""
-        c = self._freq_cache
-        if c is not None and c[0]() is cell and c[1] == cell._version and c[2] == cell.device and c[3] == self.lr_wavelength:
-            return c[4]
-        cell_host = cell.detach().to("cpu", torch.float64).numpy()
-        det = float(np.linalg.det(cell_host))
-        if det == 0.0 or not np.isfinite(det):  # the cross-product inverse below would quietly produce inf / NaN k-vectors
-            raise ValueError(f"provided `cell` has a determinant of {det}, i.e. it is not a valid unit cell")
-        norms = np.linalg.norm(cell_host, axis=1)
-        ns = np.ceil(norms / self.lr_wavelength).astype(np.int64)
-        f = [np.fft.fftfreq(int(n)) * int(n) for n in ns]
-        F = np.stack(np.meshgrid(*f, indexing="ij"), axis=-1).reshape(-1, 3)
-        freq = torch.tensor(F, dtype=cell.dtype, device=cell.device)
-        self._freq_cache = (weakref.ref(cell), cell._version, cell.device, self.lr_wavelength, freq)
+        """Integer frequencies (K,3) of all k-vectors (:func:`_integer_frequencies`), cached per cell tensor."""
+        freq, self._freq_cache = _integer_frequencies(cell, self.lr_wavelength, self._freq_cache)
         return freq
 
     def _forward_batched(self, batch_size, in_dims, charges, cell, positions, neighbor_indices, neighbor_distances,

@@ -34,9 +34,9 @@ SECOND_ORDER_HINT = (
     "twice exactly either way.")
 
 
-def first_order(fn):
+def first_order(fn, hint: str = SECOND_ORDER_HINT):
     """``torch.autograd.function.once_differentiable`` with an error message that names the way out (reference behaviour:
-    plain ATen ops differentiate any number of times, ``calculators/calculator.py:103-189``)."""
+    plain ATen ops differentiate any number of times, ``calculators/calculator.py:103-189``); ``hint`` is that message."""
     import functools
 
     @functools.wraps(fn)
@@ -50,7 +50,7 @@ def first_order(fn):
         # output points at a node that raises when something differentiates through it
         single = not isinstance(outputs, tuple)
         outs = (outputs,) if single else outputs
-        err = torch._C._functions.DelayedError(SECOND_ORDER_HINT.encode(), len(outs))
+        err = torch._C._functions.DelayedError(hint.encode(), len(outs))
 
         def fake_requires_grad(v):
             if v is not None:
