@@ -1,7 +1,8 @@
 """Registers, scratch and LDS of every kernel in a built object file, read from the code object's metadata (no recompilation):
     python tools/r06/kernel_resources.py torch-pme_amd/csrc/bricks.o [substring ...]
 Waves per SIMD follow MI355X_MICROARCH.md ("Residency"): min(8, 512 // vgpr granule-of-8) by vector registers,
-800 // (ceil(sgpr / 16) * 16 + 16) by scalar registers."""
+800 // (ceil(sgpr / 16) * 16 + 16) by scalar registers.
+To compare the device code of two commits without building objects at all: tools/device_digest.py."""
 import re
 import subprocess
 import sys
@@ -13,7 +14,7 @@ LLVM = "/opt/rocm/lib/llvm/bin/"
 def resources(obj):
     with tempfile.TemporaryDirectory() as d:
         fat, co = d + "/fat", d + "/co"
-        subprocess.run([LLVM + "llvm-objcopy", "--dump-section", f".hip_fatbin={fat}", obj], check=True)
+        subprocess.run([LLVM + "llvm-objcopy", "--dump-section", f".hip_fatbin={fat}", obj, d + "/copy"], check=True)  # (no output operand: rewrites obj)
         subprocess.run([LLVM + "clang-offload-bundler", "--type=o", "--unbundle", f"--input={fat}",
                         "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={co}"], check=True)
         notes = subprocess.run([LLVM + "llvm-readelf", "--notes", co], capture_output=True, text=True, check=True).stdout

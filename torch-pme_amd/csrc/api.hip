@@ -8,7 +8,7 @@
 #include <string>
 #include <vector>
 
-#include "common.h"
+#include "host.h"
 
 namespace mipme {
 
@@ -22,56 +22,6 @@ void set_error(const char* fmt, ...) {
   vsnprintf(g_error, sizeof(g_error), fmt, ap);
   va_end(ap);
 }
-
-// implemented in mesh.hip / kfilter.hip / rspace.hip
-template <typename T> int spread_impl(hipStream_t, const mipme_mesh_t*, int64_t, const void*, const void*, double, void*);
-template <typename T> int gather_impl(hipStream_t, const mipme_mesh_t*, int64_t, const void*, const void*, void*);
-template <typename T> int gather_epilogue_impl(hipStream_t, const mipme_mesh_t*, int64_t, const void*, const void*, const void*, const void*, double, double, void*, void*, int, void*);
-template <typename T> int gather_grad_impl(hipStream_t, const mipme_mesh_t*, int64_t, const void*, const void*, const void*, const void*, const void*, const void*, const void*, double, double, void*, void*);
-template <typename T> int kfilter_build_impl(hipStream_t, const mipme_mesh_t*, const mipme_potential_t*, void*);
-template <typename T> int apply_filter_impl(hipStream_t, int64_t, int, const void*, const void*, void*, void*);
-template <typename T> int apply_filter_cellgrad_impl(hipStream_t, const mipme_mesh_t*, const mipme_potential_t*, const void*, const void*, const void*, void*, void*, void*);
-template <typename T> int cellgrad_finalize_impl(hipStream_t, const mipme_mesh_t*, double, int64_t, void*, const void*, const void*, const void*, const void*, const void*, const void*, const void*, void*, int64_t, const void*, const void*);
-int64_t xconv_blocks(const mipme_fft_plan*);
-int64_t cellgrad_scratch_doubles();
-int64_t cellgrad_blocks(const mipme_mesh_t*);
-int fft_plan_create(int, int, int, int, int, mipme_fft_plan**);
-int fft_plan_destroy(mipme_fft_plan*);
-int fft_forward(mipme_fft_plan*, hipStream_t, const void*, void*);
-int fft_inverse(mipme_fft_plan*, hipStream_t, void*, void*);
-bool fft_plan_xfused(const mipme_fft_plan*);
-int convolve_xfused(mipme_fft_plan*, hipStream_t, const void*, const void*, void*, void*, void*, int64_t, const mipme_mesh_t*,
-                    const mipme_potential_t*, void*, void*, const void*, int64_t, const RowRideHost*, void*, const ConvCell*);
-const void* bins_epart(const mipme_mesh_t*, int64_t, int, void*, int64_t*);
-template <typename T, typename I> int rspace_forward_impl(hipStream_t, int64_t, int64_t, int, const void*, const void*, const void*, const void*, int, const mipme_potential_t*, int, void*);
-template <typename T, typename I> int rspace_backward_impl(hipStream_t, int64_t, int64_t, int, const void*, const void*, const void*, const void*, int, const mipme_potential_t*, const void*, const void*, void*, void*);
-template <typename T, typename I> int distance_forward_impl(hipStream_t, int64_t, const void*, const void*, const void*, const void*, void*);
-template <typename T> int pack_pair_shifts_impl(hipStream_t, int64_t, const void*, void*, void*);
-template <typename T> int distance_forward_packed_impl(hipStream_t, int64_t, const void*, const void*, const void*, const void*, void*);
-template <typename T, typename I> int distance_backward_impl(hipStream_t, int64_t, int64_t, const void*, const void*, const void*, const void*, const void*, void*, void*, void*);
-int64_t pair_partials_blocks(int64_t);
-
-struct FftDims { int dtype, nx, ny, nz, batch; };
-FftDims fft_plan_dims(const mipme_fft_plan*);
-// bricks.hip
-bool bricks_supported(const mipme_mesh_t*, int dtype);
-int64_t bins_bytes(const mipme_mesh_t*, int64_t, int dtype);
-template <typename T> int bins_build(hipStream_t, const mipme_mesh_t*, int64_t, const void*, void*, int*, const void*, void*, bool = false);
-template <typename T> int spread_bricks(hipStream_t, const mipme_mesh_t*, int64_t, void*, const void*, double, void*, int*,
-                                        const mipme_sr_job_t*, bool, double*, const PlaneHost* = nullptr, bool* = nullptr);
-bool fft_plan_plane_forward_ok(const mipme_fft_plan*);
-int plane_bins_capacity(const mipme_mesh_t*, int64_t, int);
-int plane_bands(const mipme_mesh_t*, int);
-void fft_plan_set_forward_done(mipme_fft_plan*, bool, int);
-void fft_plan_set_forward_ycols(mipme_fft_plan*, bool);
-void* fft_plan_hat_parts(mipme_fft_plan*, hipStream_t, int);
-template <typename T> int kfilter_deriv_impl(hipStream_t, const mipme_mesh_t*, const mipme_potential_t*, void*);
-template <typename T> int cell_tail_finalize_impl(hipStream_t, const mipme_mesh_t*, double, double, int64_t, int64_t, const void*,
-                                                  const void*, const void*, const void*, void*);
-bool sr_job_fusable(const mipme_sr_job_t*);
-int* fft_plan_brick_count(const mipme_fft_plan*);
-template <typename T> int gather_bricks(hipStream_t, const mipme_mesh_t*, int64_t, void*, const void*, const void*, const void*, double, double, void*, void*, int, void*, const GatherTailHost*, void*, int*);
-template <typename T> int gather_grad_bricks(hipStream_t, const mipme_mesh_t*, int64_t, void*, const void*, const void*, const void*, const void*, const void*, const void*, double, double, void*, void*);
 
 // ---- optional per-stage timing (bench.py): HIP events recorded on the launch stream around every stage ----
 struct ProfEntry {
@@ -151,18 +101,6 @@ struct ProfScope {
     if ((rc = (call))) return rc;    \
   } while (0)
 
-// self / background corrections: potentials/coulomb.py:144-158, potentials/inversepowerlaw.py:143-166
-static void correction_terms(const mipme_potential_t* pot, double& self_c, double& bg_c) {
-  const int p = pot->kind == MIPME_COULOMB ? 1 : pot->exponent;
-  const double two_s2 = 2.0 * pot->smearing * pot->smearing;
-  self_c = pot->prefactor / std::tgamma(0.5 * p + 1.0) / std::pow(two_s2, 0.5 * p);
-  if (p >= 3)
-    bg_c = 0.0;
-  else
-    bg_c = pot->prefactor * std::pow(3.14159265358979323846, 1.5) * std::pow(two_s2, 0.5 * (3 - p)) /
-           ((3 - p) * std::tgamma(0.5 * p));
-}
-
 static int check_plan(const mipme_fft_plan* plan, int dtype, const mipme_mesh_t* m) {
   MIPME_REQUIRE(plan != nullptr, "FFT plan is NULL");
   const FftDims d = fft_plan_dims(plan);
@@ -171,50 +109,22 @@ static int check_plan(const mipme_fft_plan* plan, int dtype, const mipme_mesh_t*
   return MIPME_OK;
 }
 
-// cell_work of an energy step's cell gradient (mipme_cell_tail_work), in doubles:
-// [rows 25 per rider][rpart 9 per brick][cwave 9 per wavefront of the pair kernel][wbuf: one real per half-grid point]
-struct CellWork {
-  int64_t n_riders, n_bricks, n_waves;
-  double *rows, *rpart, *cwave;
-  void* wbuf;
-  int64_t total;
-};
-static CellWork cell_work_layout(const mipme_mesh_t* m, int64_t N, void* base) {
-  CellWork w;
-  const int64_t Mh = int64_t(m->nx) * m->ny * (m->nz / 2 + 1);
-  w.n_riders = std::min<int64_t>(256, std::max<int64_t>(8, Mh / 2048));  // ~2 k-points per rider thread (1024 threads)
-  w.n_bricks = int64_t((m->nx + 7) / 8) * ((m->ny + 7) / 8) * ((m->nz + 7) / 8);
-  w.n_waves = (N + 3) / 4;  // 16 lanes per row: 4 rows per wavefront (rows_body.h)
-  double* b = (double*)base;
-  w.rows = b;
-  w.rpart = w.rows + 25 * w.n_riders;
-  w.cwave = w.rpart + 9 * w.n_bricks;
-  w.wbuf = w.cwave + 9 * w.n_waves;
-  w.total = 25 * w.n_riders + 9 * w.n_bricks + 9 * w.n_waves + Mh;  // (wbuf: Mh reals of <= 8 bytes)
-  return w;
-}
-
-static constexpr int kPlanePartsMax = 8;
-static int plane_spread_parts_setting() {
-  static const int parts_env = [] { const char* e = getenv("MIPME_PLANE_PARTS"); return e ? atoi(e) : 2; }();
-  return parts_env < 1 ? 1 : (parts_env > kPlanePartsMax ? kPlanePartsMax : parts_env);
-}
-
+// a: the caller's arguments as mipme_kspace_forward has checked them; tail: its gather tail (NULL: potentials only)
 template <typename T>
-static int kspace_forward_t(mipme_fft_plan* plan, hipStream_t st, const mipme_mesh_t* m, const mipme_potential_t* pot,
-                            int64_t N, const void* pos, const void* q, const void* G, void* rho_mesh, void* rho_hat,
-                            void* hat_work, void* phi_mesh, void* dc, void* out_lr, void* out_phi, void* bins,
-                            void* wait_event, int accumulate, void* out_field, void* out_records,
-                            const mipme_sr_job_t* job, void* cell_partials, const GatherTailHost* tail, void* nan_flag,
-                            void* out_grad_cell = nullptr, const void* G_deriv = nullptr, void* cell_work = nullptr,
-                            void* out_rho_hat = nullptr, bool rho_mesh_unused = false) {
+static int kspace_forward_t(const mipme_kspace_forward_args_t& a, const GatherTailHost* tail) {
+  mipme_fft_plan* plan = a.plan;
+  hipStream_t st = (hipStream_t)a.stream;
+  const mipme_mesh_t* m = a.mesh;
+  const int64_t N = a.n_atoms;
+  void* bins = a.atom_bins;
+  const mipme_sr_job_t* job = a.sr_job;
   int rc;
   CellWork cw{};
-  if (out_grad_cell) cw = cell_work_layout(m, N, cell_work);
+  if (a.out_grad_cell) cw = cell_work_layout(m, N, a.cell_work);
   const int64_t Mh = int64_t(m->nx) * m->ny * (m->nz / 2 + 1);
   double self_c, bg_c;
-  correction_terms(pot, self_c, bg_c);
-  fft_plan_set_forward_done(plan, false, 1);               // (nor the plane spread's "forward planes done": set below, consumed by convolve_xfused)
+  correction_terms(a.pot, self_c, bg_c);
+  fft_plan_begin_step(plan);  // (the plane spread's "forward planes done" is set below and consumed by convolve_xfused)
   // the plan's brick counters are zero here; the binning pass fills them and the gather -- the last consumer -- zeroes them
   // again (no memset launch per call).  If anything in between fails they are cleared explicitly, so that a failed call does
   // not poison the next one.
@@ -233,8 +143,8 @@ static int kspace_forward_t(mipme_fft_plan* plan, hipStream_t st, const mipme_me
     guard.armed = true;
     // fused convolution ahead and planes that fit a workgroup: the spread will write the forward (y,z) transform itself, from
     // the plane lists the binning pass leaves (bricks.hip plane_spread_yz_body)
-    const bool want_planes = !rho_hat && rho_mesh_unused && fft_plan_plane_forward_ok(plan);
-    STAGE(st, "bin_atoms", bins_build<T>(st, m, N, pos, bins, counters, q, out_records, want_planes));
+    const bool want_planes = !a.rho_hat && (a.flags & MIPME_FWD_RHO_MESH_UNUSED) != 0 && fft_plan_plane_forward_ok(plan);
+    STAGE(st, "bin_atoms", bins_build<T>(st, m, N, a.positions, bins, counters, a.charges, a.out_records, want_planes));
     {
       const bool co = job && sr_job_fusable(job);
       const int reps = (g_prof_on && co) ? kProfRepeat : 1;
@@ -244,7 +154,7 @@ static int kspace_forward_t(mipme_fft_plan* plan, hipStream_t st, const mipme_me
       bool planes = false;
       ph.slot_values = m->n_channels == 1;  // (bins_build above was handed these very charges)
       if (want_planes) {
-        ph.hat = hat_work;
+        ph.hat = a.hat_work;
         ph.keep_mesh = false;
         // MIPME_PLANE_PARTS workgroups per plane (default 2, at most 8; measured 1 / 2 / 3 / 4 / 8: profiles/r05_experiments.txt): a plane's LDS atomics are what its workgroup waits for,
         // and they go through ONE CU's LDS pipe
@@ -256,142 +166,143 @@ static int kspace_forward_t(mipme_fft_plan* plan, hipStream_t st, const mipme_me
         }
       }
       for (int r = 0; r < reps; ++r)
-        if ((rc = spread_bricks<T>(st, m, N, bins, q, 1.0, rho_mesh, counters, co ? job : nullptr, tail != nullptr,
-                                   out_grad_cell ? cw.cwave : nullptr, &ph, &planes))) return rc;
+        if ((rc = spread_bricks<T>(st, m, N, bins, a.charges, 1.0, a.rho_mesh, counters, co ? job : nullptr, tail != nullptr,
+                                   a.out_grad_cell ? cw.cwave : nullptr, &ph, &planes))) return rc;
       fft_plan_set_forward_done(plan, planes, planes ? ph.parts_used : 1);
       fft_plan_set_forward_ycols(plan, planes && ph.ycols_pending);
     }
     if (job && !sr_job_fusable(job))  // no co-scheduled kernel for this potential / shift format: one after the other
       STAGE(st, "rspace_forward",
-            mipme_sr_rows_fused(st, sizeof(T) == 4 ? MIPME_F32 : MIPME_F64, job->n_atoms, job->row_ptr, job->entries_shift,
+            mipme_sr_rows_fused(st, dtype_of<T>(), job->n_atoms, job->row_ptr, job->entries_shift,
                                 job->entries, nullptr, job->positions, job->cell, job->charges, job->charges, nullptr, 0,
                                 job->full_list, job->pot, 0, job->shift_format, job->records, 1, job->out, job->force,
                                 nullptr, nullptr, job->dist_out));
   } else {
-    STAGE(st, "spread", spread_impl<T>(st, m, N, pos, q, 1.0, rho_mesh));
+    STAGE(st, "spread", spread_impl<T>(st, m, N, a.positions, a.charges, 1.0, a.rho_mesh));
   }
-  if (!rho_hat) {
+  if (!a.rho_hat) {
     // nobody needs rfftn(rho) itself: (y,z) hipFFT planes + one kernel for x-FFT * G * inverse x-FFT
     int64_t n_sr_part = 0;
-    const void* sr_part = tail ? bins_epart(m, N, sizeof(T) == 4 ? MIPME_F32 : MIPME_F64, bins, &n_sr_part) : nullptr;
+    const void* sr_part = tail ? bins_epart(m, N, dtype_of<T>(), bins, &n_sr_part) : nullptr;
     ConvCell cc{};
-    if (out_grad_cell) cc = ConvCell{G_deriv, cw.cwave, cw.n_waves, cw.wbuf, cw.rows, int(cw.n_riders), nullptr, nullptr, nullptr, nullptr};
-    cc.rho_hat_out = out_rho_hat;
-    STAGE(st, "convolve_xfused", convolve_xfused(plan, st, rho_mesh, G, hat_work, phi_mesh, dc, 0, m, pot, cell_partials,
-                                                 tail ? const_cast<void*>(tail->epart_k) : nullptr, sr_part, n_sr_part,
-                                                 nullptr, nan_flag, (out_grad_cell || out_rho_hat) ? &cc : nullptr));
+    if (a.out_grad_cell) cc = ConvCell{a.G_deriv, cw.cwave, cw.n_waves, cw.wbuf, cw.rows, int(cw.n_riders), nullptr, nullptr, nullptr, nullptr};
+    cc.rho_hat_out = a.out_rho_hat;
+    STAGE(st, "convolve_xfused", convolve_xfused(plan, st, a.rho_mesh, a.G, a.hat_work, a.phi_mesh, a.dc, 0, m, a.pot,
+                                                 a.out_cell_partials, tail ? const_cast<void*>(tail->epart_k) : nullptr, sr_part,
+                                                 n_sr_part, nullptr, a.nan_flag,
+                                                 (a.out_grad_cell || a.out_rho_hat) ? &cc : nullptr));
   } else {
-    STAGE(st, "fft_r2c", fft_forward(plan, st, rho_mesh, rho_hat));
-    STAGE(st, "apply_filter", apply_filter_impl<T>(st, Mh, m->n_channels, rho_hat, G, hat_work, dc));
-    STAGE(st, "fft_c2r", fft_inverse(plan, st, hat_work, phi_mesh));
+    STAGE(st, "fft_r2c", fft_forward(plan, st, a.rho_mesh, a.rho_hat));
+    STAGE(st, "apply_filter", apply_filter_impl<T>(st, Mh, m->n_channels, a.rho_hat, a.G, a.hat_work, a.dc));
+    STAGE(st, "fft_c2r", fft_inverse(plan, st, a.hat_work, a.phi_mesh));
   }
   // the short-range sum may be running on another stream into out_lr: join it before the gather adds to it
-  if (wait_event) MIPME_CHECK_HIP(hipStreamWaitEvent(st, (hipEvent_t)wait_event, 0));
+  if (a.gather_wait_event) MIPME_CHECK_HIP(hipStreamWaitEvent(st, (hipEvent_t)a.gather_wait_event, 0));
   if (bins)
     STAGE(st, tail ? "gather+energy+forces" : "gather",
-          gather_bricks<T>(st, m, N, bins, phi_mesh, q, dc, self_c, bg_c, out_lr, out_phi, accumulate, out_field, tail, nan_flag,
-                           fft_plan_brick_count(plan)));
+          gather_bricks<T>(st, m, N, bins, a.phi_mesh, a.charges, a.dc, self_c, bg_c, a.out_lr, a.out_phi, a.accumulate_out,
+                           a.out_field, tail, a.nan_flag, fft_plan_brick_count(plan)));
   else
-    STAGE(st, "gather", gather_epilogue_impl<T>(st, m, N, pos, phi_mesh, q, dc, self_c, bg_c, out_lr, out_phi, accumulate, nan_flag));
-  guard.armed = N == 0 && bins;  // the gather has zeroed the counters (it does not run without atoms: nothing was counted either)
-  guard.armed = false;
-  if (out_grad_cell)
+    STAGE(st, "gather", gather_epilogue_impl<T>(st, m, N, a.positions, a.phi_mesh, a.charges, a.dc, self_c, bg_c, a.out_lr, a.out_phi,
+                                                a.accumulate_out, a.nan_flag));
+  guard.armed = false;  // the gather has zeroed the counters (it does not run without atoms: nothing was counted either)
+  if (a.out_grad_cell)
     STAGE(st, "cell_finalize",
-          cell_tail_finalize_impl<T>(st, m, bg_c, 0.5 * tail->force_scale, cw.n_riders, cw.n_bricks, cw.rows, cw.rpart, dc,
-                                     tail->aux_seed ? tail->aux_seed : tail->seed, out_grad_cell));
+          cell_tail_finalize_impl<T>(st, m, bg_c, 0.5 * tail->force_scale, cw.n_riders, cw.n_bricks, cw.rows, cw.rpart, a.dc,
+                                     tail->aux_seed ? tail->aux_seed : tail->seed, a.out_grad_cell));
   return MIPME_OK;
 }
 
 template <typename T>
-static int kspace_backward_t(mipme_fft_plan* plan, hipStream_t st, const mipme_mesh_t* m, const mipme_potential_t* pot,
-                             int64_t N, const void* pos, const void* q, const void* gout, const void* G,
-                             const void* phi_mesh, const void* rho_hat, const void* rho_dc, const void* phi_atoms,
-                             void* psi_mesh, void* psi_hat, void* hat_work, void* chi_mesh, void* dc, void* partials,
-                             void* grad_pos, void* grad_q, void* grad_cell, void* bins, const void* grad_scale,
-                             const void* mesh_field, int64_t kgrid_blocks_ready, const void* G_deriv) {
+static int kspace_backward_t(const mipme_kspace_backward_args_t& a) {
+  mipme_fft_plan* plan = a.plan;
+  hipStream_t st = (hipStream_t)a.stream;
+  const mipme_mesh_t* m = a.mesh;
+  const int64_t N = a.n_atoms;
+  void* bins = a.atom_bins;
   int rc;
   double self_c, bg_c;
-  correction_terms(pot, self_c, bg_c);
-  fft_plan_set_forward_done(plan, false, 1);  // (a forward call that failed after its plane spread must not make this call's convolution skip its forward planes)
-  if (grad_scale) {
+  correction_terms(a.pot, self_c, bg_c);
+  fft_plan_begin_step(plan);  // (a forward call that failed after its plane spread must not make this call's convolution skip its forward planes)
+  if (a.grad_scale) {
     // energy mode: grad_out = grad_scale * charges  =>  psi = (grad_scale/2V) rho, chi = (grad_scale/2V) phi:
     // no second spread / FFT / filter / inverse FFT (special case L = sum q V)
-    MIPME_REQUIRE(rho_dc, "energy-mode backward needs rho_dc");
+    MIPME_REQUIRE(a.rho_dc, "energy-mode backward needs rho_dc");
     // mesh_field (the forward gather's per-atom field, single channel): the mesh forces are gE q_a field_a -- no gradient
     // gather; the caller assembles them (mipme_sr_rows_finalize) and passes grad_positions = grad_charges = NULL
-    const bool from_field = mesh_field != nullptr && !grad_pos && !grad_q;
+    const bool from_field = a.mesh_field != nullptr && !a.grad_positions && !a.grad_charges;
     if (!from_field) {
       if (bins)
-        STAGE(st, "gather_grad", gather_grad_bricks<T>(st, m, N, bins, q, gout, phi_mesh, phi_mesh, rho_dc, grad_scale, self_c, bg_c, grad_pos, grad_q));
+        STAGE(st, "gather_grad", gather_grad_bricks<T>(st, m, N, bins, a.charges, a.grad_out, a.phi_mesh, a.phi_mesh, a.rho_dc, a.grad_scale, self_c, bg_c, a.grad_positions, a.grad_charges));
       else
-        STAGE(st, "gather_grad", gather_grad_impl<T>(st, m, N, pos, q, gout, phi_mesh, phi_mesh, rho_dc, grad_scale, self_c, bg_c, grad_pos, grad_q));
+        STAGE(st, "gather_grad", gather_grad_impl<T>(st, m, N, a.positions, a.charges, a.grad_out, a.phi_mesh, a.phi_mesh, a.rho_dc, a.grad_scale, self_c, bg_c, a.grad_positions, a.grad_charges));
     }
-    if (grad_cell) {
+    if (a.grad_cell) {
       // dL/dG(k) = (gE / 2V) mu(k) |rho^(k)|^2: the 12 k-grid sums from rho^ alone, scaled in the finalisation -- either
       // already in `partials` (kgrid_blocks_ready of them, written by the forward's fused convolution) or formed here from
       // the saved rho^
-      MIPME_REQUIRE(phi_atoms && partials && (grad_pos || from_field),
+      MIPME_REQUIRE(a.phi_atoms && a.partials && (a.grad_positions || from_field),
                     "cell gradient needs phi_atoms, partials and grad_positions (or the mesh field) buffers");
-      if (kgrid_blocks_ready <= 0) {
-        MIPME_REQUIRE(rho_hat, "cell gradient needs rho_hat unless the k-grid sums are ready");
-        STAGE(st, "apply_filter_cellgrad", apply_filter_cellgrad_impl<T>(st, m, pot, rho_hat, rho_hat, G, nullptr, nullptr, partials));
+      if (a.kgrid_blocks_ready <= 0) {
+        MIPME_REQUIRE(a.rho_hat, "cell gradient needs rho_hat unless the k-grid sums are ready");
+        STAGE(st, "apply_filter_cellgrad", apply_filter_cellgrad_impl<T>(st, m, a.pot, a.rho_hat, a.rho_hat, a.G, nullptr, nullptr, a.partials));
       }
       STAGE(st, "cellgrad_finalize",
-            cellgrad_finalize_impl<T>(st, m, bg_c, N, partials, pos, from_field ? nullptr : grad_pos, gout, phi_atoms, rho_dc,
-                                      rho_dc, grad_scale, grad_cell, kgrid_blocks_ready, mesh_field, q));
+            cellgrad_finalize_impl<T>(st, m, bg_c, N, a.partials, a.positions, from_field ? nullptr : a.grad_positions, a.grad_out, a.phi_atoms, a.rho_dc,
+                                      a.rho_dc, a.grad_scale, a.grad_cell, a.kgrid_blocks_ready, a.mesh_field, a.charges));
     }
     return MIPME_OK;
   }
   // psi = spread(g / 2V); chi = F psi
   if (bins)
-    STAGE(st, "spread", spread_bricks<T>(st, m, N, bins, gout, 0.5 / m->volume, psi_mesh, nullptr, nullptr, false, nullptr));
+    STAGE(st, "spread", spread_bricks<T>(st, m, N, bins, a.grad_out, 0.5 / m->volume, a.psi_mesh, nullptr, nullptr, false, nullptr));
   else
-    STAGE(st, "spread", spread_impl<T>(st, m, N, pos, gout, 0.5 / m->volume, psi_mesh));
+    STAGE(st, "spread", spread_impl<T>(st, m, N, a.positions, a.grad_out, 0.5 / m->volume, a.psi_mesh));
   const int64_t Mh = int64_t(m->nx) * m->ny * (m->nz / 2 + 1);
-  if (grad_cell && !psi_hat) {
+  if (a.grad_cell && !a.psi_hat) {
     // the fused convolution with the cell sums: psi^ is contracted with the saved rho^ by the x stage, the k-grid sums against
     // the derivative table are formed by the riders of the inverse (y,z) launch -- as 12-value rows for cellgrad_finalize_kernel
-    MIPME_REQUIRE(G_deriv && rho_hat && rho_dc && phi_atoms && partials && grad_pos && m->n_channels == 1,
+    MIPME_REQUIRE(a.G_deriv && a.rho_hat && a.rho_dc && a.phi_atoms && a.partials && a.grad_positions && m->n_channels == 1,
                   "fused cell gradient needs G_deriv, rho_hat, rho_dc, phi_atoms, partials, grad_positions and one channel");
     const int64_t n_riders = std::min<int64_t>(256, std::max<int64_t>(8, Mh / 2048));
-    double* kh = (double*)partials;
+    double* kh = (double*)a.partials;
     double* rows = kh + 12 * n_riders + cellgrad_scratch_doubles();
     void* wbuf = rows + 25 * n_riders;
-    ConvCell cc{G_deriv, nullptr, 0, wbuf, rows, int(n_riders), nullptr, rho_hat, kh,
+    ConvCell cc{a.G_deriv, nullptr, 0, wbuf, rows, int(n_riders), nullptr, a.rho_hat, kh,
                 reinterpret_cast<int*>(kh + 12 * n_riders + cellgrad_scratch_doubles() - 1)};
-    STAGE(st, "convolve_xfused", convolve_xfused(plan, st, psi_mesh, G, hat_work, chi_mesh, dc, 0, m, pot, nullptr, nullptr,
+    STAGE(st, "convolve_xfused", convolve_xfused(plan, st, a.psi_mesh, a.G, a.hat_work, a.chi_mesh, a.dc, 0, m, a.pot, nullptr, nullptr,
                                                  nullptr, 0, nullptr, nullptr, &cc));
     if (bins)
-      STAGE(st, "gather_grad", gather_grad_bricks<T>(st, m, N, bins, q, gout, phi_mesh, chi_mesh, dc, nullptr, self_c, bg_c, grad_pos, grad_q));
+      STAGE(st, "gather_grad", gather_grad_bricks<T>(st, m, N, bins, a.charges, a.grad_out, a.phi_mesh, a.chi_mesh, a.dc, nullptr, self_c, bg_c, a.grad_positions, a.grad_charges));
     else
-      STAGE(st, "gather_grad", gather_grad_impl<T>(st, m, N, pos, q, gout, phi_mesh, chi_mesh, dc, nullptr, self_c, bg_c, grad_pos, grad_q));
+      STAGE(st, "gather_grad", gather_grad_impl<T>(st, m, N, a.positions, a.charges, a.grad_out, a.phi_mesh, a.chi_mesh, a.dc, nullptr, self_c, bg_c, a.grad_positions, a.grad_charges));
     STAGE(st, "cellgrad_finalize",
-          cellgrad_finalize_impl<T>(st, m, bg_c, N, partials, pos, grad_pos, gout, phi_atoms, rho_dc, dc, nullptr, grad_cell,
+          cellgrad_finalize_impl<T>(st, m, bg_c, N, a.partials, a.positions, a.grad_positions, a.grad_out, a.phi_atoms, a.rho_dc, a.dc, nullptr, a.grad_cell,
                                     n_riders, nullptr, nullptr));
     return MIPME_OK;
   }
-  const bool xfused = !grad_cell && !psi_hat;
+  const bool xfused = !a.grad_cell && !a.psi_hat;
   if (xfused) {
-    STAGE(st, "convolve_xfused", convolve_xfused(plan, st, psi_mesh, G, hat_work, chi_mesh, dc, 0, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr));
+    STAGE(st, "convolve_xfused", convolve_xfused(plan, st, a.psi_mesh, a.G, a.hat_work, a.chi_mesh, a.dc, 0, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr));
   } else {
-    STAGE(st, "fft_r2c", fft_forward(plan, st, psi_mesh, psi_hat));
+    STAGE(st, "fft_r2c", fft_forward(plan, st, a.psi_mesh, a.psi_hat));
   }
   if (xfused) {
-  } else if (grad_cell) {
-    MIPME_REQUIRE(rho_hat && rho_dc && phi_atoms && partials && grad_pos,
+  } else if (a.grad_cell) {
+    MIPME_REQUIRE(a.rho_hat && a.rho_dc && a.phi_atoms && a.partials && a.grad_positions,
                   "cell gradient needs rho_hat, rho_dc, phi_atoms, partials and grad_positions buffers");
-    STAGE(st, "apply_filter_cellgrad", apply_filter_cellgrad_impl<T>(st, m, pot, psi_hat, rho_hat, G, hat_work, dc, partials));
+    STAGE(st, "apply_filter_cellgrad", apply_filter_cellgrad_impl<T>(st, m, a.pot, a.psi_hat, a.rho_hat, a.G, a.hat_work, a.dc, a.partials));
   } else {
-    STAGE(st, "apply_filter", apply_filter_impl<T>(st, Mh, m->n_channels, psi_hat, G, hat_work, dc));
+    STAGE(st, "apply_filter", apply_filter_impl<T>(st, Mh, m->n_channels, a.psi_hat, a.G, a.hat_work, a.dc));
   }
-  if (!xfused) STAGE(st, "fft_c2r", fft_inverse(plan, st, hat_work, chi_mesh));
+  if (!xfused) STAGE(st, "fft_c2r", fft_inverse(plan, st, a.hat_work, a.chi_mesh));
   if (bins)
-    STAGE(st, "gather_grad", gather_grad_bricks<T>(st, m, N, bins, q, gout, phi_mesh, chi_mesh, dc, nullptr, self_c, bg_c, grad_pos, grad_q));
+    STAGE(st, "gather_grad", gather_grad_bricks<T>(st, m, N, bins, a.charges, a.grad_out, a.phi_mesh, a.chi_mesh, a.dc, nullptr, self_c, bg_c, a.grad_positions, a.grad_charges));
   else
-    STAGE(st, "gather_grad", gather_grad_impl<T>(st, m, N, pos, q, gout, phi_mesh, chi_mesh, dc, nullptr, self_c, bg_c, grad_pos, grad_q));
-  if (grad_cell)
+    STAGE(st, "gather_grad", gather_grad_impl<T>(st, m, N, a.positions, a.charges, a.grad_out, a.phi_mesh, a.chi_mesh, a.dc, nullptr, self_c, bg_c, a.grad_positions, a.grad_charges));
+  if (a.grad_cell)
     STAGE(st, "cellgrad_finalize",
-          cellgrad_finalize_impl<T>(st, m, bg_c, N, partials, pos, grad_pos, gout, phi_atoms, rho_dc, dc, nullptr, grad_cell, 0,
+          cellgrad_finalize_impl<T>(st, m, bg_c, N, a.partials, a.positions, a.grad_positions, a.grad_out, a.phi_atoms, a.rho_dc, a.dc, nullptr, a.grad_cell, 0,
                                     nullptr, nullptr));
   return MIPME_OK;
 }
@@ -937,9 +848,6 @@ static int slab_backward_t(hipStream_t st, int axis, const mipme_mesh_t* m, doub
 
 }  // namespace mipme
 
-namespace mipme {
-void* fft_plan_tail_scratch(mipme_fft_plan*, int64_t bytes);
-}
 // Copy a caller's versioned argument struct into the library's own layout: only the first `size` bytes the caller
 // compiled are read, everything after them stays zero (fields are only ever appended).
 template <typename A>
@@ -956,24 +864,7 @@ static int load_args(const A* in, A& out, const char* what) {
 
 using namespace mipme;
 
-#define DT_SWITCH(dtype, CALL_F32, CALL_F64)                    \
-  do {                                                          \
-    if ((dtype) == MIPME_F32) return CALL_F32;                  \
-    if ((dtype) == MIPME_F64) return CALL_F64;                  \
-    set_error("invalid dtype %d", int(dtype));                  \
-    return MIPME_EINVAL;                                        \
-  } while (0)
-
-// ---- MD step on live bins (bricks.hip) ---------------------------------------------------------------------------------------
-namespace mipme {
-bool live_supported(const mipme_mesh_t*, int64_t, int);
-int64_t live_lists_ints(const mipme_mesh_t*, int64_t);
-template <typename T> int live_rebin(hipStream_t, const mipme_mesh_t*, int64_t, const void*, void*, void*, void*);
-template <typename T> int live_spread(hipStream_t, const mipme_mesh_t*, int64_t, const void*, void*, void*, void*, const mipme_sr_job_t*, void*, double*);
-template <typename T> int live_gather(hipStream_t, const mipme_mesh_t*, int64_t, const void*, void*, void*, const void*, const void*,
-                                      double, double, void*, void*, const GatherTailHost*, void*);
-}  // namespace mipme
-
+// ---- MD step on live bins (live.hip) -----------------------------------------------------------------------------------------
 static int md_check(const mipme_md_args_t* in, mipme_md_args_t& a, const char* who) {
   MIPME_REQUIRE(in && in->size >= 16 && in->version == 1, "%s: NULL or unversioned argument struct", who);
   std::memset(&a, 0, sizeof(a));
@@ -994,6 +885,7 @@ static int md_step_t(const mipme_md_args_t& a) {
   const mipme_mesh_t* m = a.mesh;
   double self_c, bg_c;
   correction_terms(a.pot, self_c, bg_c);
+  fft_plan_begin_step(a.plan);
   mipme_sr_job_t job{};
   job.n_atoms = a.n_atoms;
   job.row_ptr = a.row_ptr;
@@ -1015,11 +907,7 @@ static int md_step_t(const mipme_md_args_t& a) {
   tail.seed = a.grad_seed;
   tail.grad_pos = a.grad_positions;
   tail.energy = a.energy;
-  tail.n_k = xconv_blocks(a.plan);
-  tail.epart_k = fft_plan_tail_scratch(a.plan, 3 * int64_t(sizeof(double)) * tail.n_k);
-  tail.sr_reduced = 1;
-  MIPME_REQUIRE(tail.epart_k, "could not allocate the energy partial sums of the plan (not possible during stream capture: run "
-                              "one evaluation before capturing)");
+  if ((rc = tail_attach_plan_scratch(tail, a.plan))) return rc;
   CellWork cw{};
   if (a.grad_cell) {
     cw = cell_work_layout(m, a.n_atoms, a.cell_work);
@@ -1028,12 +916,9 @@ static int md_step_t(const mipme_md_args_t& a) {
   tail.grad_q = a.grad_charges;
   tail.aux_seed = a.aux_seed;
   tail.live_flags = a.host_flags;
-  if (a.energy_log) {
-    MIPME_REQUIRE(a.energy_log_cursor && a.energy_log_capacity > 0, "energy_log needs energy_log_cursor and a capacity > 0");
-    tail.elog = (double*)a.energy_log;
-    tail.elog_cursor = (int*)a.energy_log_cursor;
-    tail.elog_cap = int(a.energy_log_capacity);
-  }
+  if (a.energy_log && (rc = tail_attach_energy_log(tail, a.energy_log, a.energy_log_cursor, a.energy_log_capacity,
+                                                   "energy_log needs energy_log_cursor")))
+    return rc;
   STAGE(st, "spread+rspace_forward", live_spread<T>(st, m, a.n_atoms, a.records, a.atom_bins, a.live_lists, a.rho_mesh, &job, a.host_flags,
                                                      a.grad_cell ? cw.cwave : nullptr));
   int64_t n_sr_part = 0;
@@ -1173,20 +1058,14 @@ int mipme_kspace_forward(const mipme_kspace_forward_args_t* args_in) {
     tail.energy = a.out_energy;
     MIPME_REQUIRE(!a.rho_hat && mesh->n_channels == 1 && sr_job_fusable(a.sr_job),
                   "the gather tail needs the fused convolution (rho_hat == NULL), one channel and a co-schedulable sr_job");
-    tail.n_k = xconv_blocks(a.plan);
-    tail.epart_k = fft_plan_tail_scratch(a.plan, 3 * int64_t(sizeof(double)) * tail.n_k);  // + the reduced pair partials
-    tail.sr_reduced = 1;
-    MIPME_REQUIRE(tail.epart_k, "could not allocate the energy partial sums of the plan (not possible during stream "
-                                "capture: run one evaluation before capturing)");
+    if ((rc = tail_attach_plan_scratch(tail, a.plan))) return rc;
     tp = &tail;
   }
-  if (a.energy_log) {
-    MIPME_REQUIRE(tp && a.energy_log_cursor && a.energy_log_capacity > 0,
-                  "energy_log rides on the gather tail (out_energy, out_grad_positions) and needs energy_log_cursor and a capacity > 0");
-    tail.elog = (double*)a.energy_log;
-    tail.elog_cursor = (int*)a.energy_log_cursor;
-    tail.elog_cap = int(a.energy_log_capacity);
-  }
+  // (without a tail the log is refused like one without a cursor)
+  if (a.energy_log && (rc = tail_attach_energy_log(tail, a.energy_log, tp ? a.energy_log_cursor : nullptr, a.energy_log_capacity,
+                                                   "energy_log rides on the gather tail (out_energy, out_grad_positions) and "
+                                                   "needs energy_log_cursor")))
+    return rc;
   if (a.out_grad_charges || a.out_grad_cell) {
     MIPME_REQUIRE(tp, "out_grad_charges / out_grad_cell ride on the gather tail (out_energy, out_grad_positions)");
     MIPME_REQUIRE(!a.out_grad_charges || !a.sr_job->full_list || (a.sr_job->shift_format & MIPME_ROWS_PADDED),
@@ -1203,16 +1082,7 @@ int mipme_kspace_forward(const mipme_kspace_forward_args_t* args_in) {
       tail.records = a.out_records;
     }
   }
-  hipStream_t st = (hipStream_t)a.stream;
-  DT_SWITCH(a.dtype,
-            kspace_forward_t<float>(a.plan, st, mesh, a.pot, a.n_atoms, a.positions, a.charges, a.G, a.rho_mesh, a.rho_hat,
-                                    a.hat_work, a.phi_mesh, a.dc, a.out_lr, a.out_phi, a.atom_bins, a.gather_wait_event,
-                                    a.accumulate_out, a.out_field, a.out_records, a.sr_job, a.out_cell_partials, tp, a.nan_flag,
-                                    a.out_grad_cell, a.G_deriv, a.cell_work, a.out_rho_hat, (a.flags & MIPME_FWD_RHO_MESH_UNUSED) != 0),
-            kspace_forward_t<double>(a.plan, st, mesh, a.pot, a.n_atoms, a.positions, a.charges, a.G, a.rho_mesh, a.rho_hat,
-                                     a.hat_work, a.phi_mesh, a.dc, a.out_lr, a.out_phi, a.atom_bins, a.gather_wait_event,
-                                     a.accumulate_out, a.out_field, a.out_records, a.sr_job, a.out_cell_partials, tp, a.nan_flag,
-                                     a.out_grad_cell, a.G_deriv, a.cell_work, a.out_rho_hat, (a.flags & MIPME_FWD_RHO_MESH_UNUSED) != 0));
+  DT_SWITCH(a.dtype, kspace_forward_t<float>(a, tp), kspace_forward_t<double>(a, tp));
 }
 
 int mipme_md_supported(const mipme_mesh_t* mesh, const mipme_potential_t* pot, int64_t n_atoms, int dtype) {
@@ -1271,16 +1141,7 @@ int mipme_kspace_backward(const mipme_kspace_backward_args_t* args_in) {
                 "psi_hat may only be NULL for plans with a power-of-two nx, and with a cell gradient only together with G_deriv");
   MIPME_REQUIRE(a.n_atoms == 0 || (a.positions && a.charges && a.grad_out), "NULL atom buffer passed to mipme_kspace_backward");
   MIPME_REQUIRE(!a.atom_bins || bricks_supported(a.mesh, a.dtype), "atom bins passed for a mesh the brick kernels do not support");
-  hipStream_t st = (hipStream_t)a.stream;
-  DT_SWITCH(a.dtype,
-            kspace_backward_t<float>(a.plan, st, a.mesh, a.pot, a.n_atoms, a.positions, a.charges, a.grad_out, a.G, a.phi_mesh,
-                                     a.rho_hat, a.rho_dc, a.phi_atoms, a.psi_mesh, a.psi_hat, a.hat_work, a.chi_mesh, a.dc,
-                                     a.partials, a.grad_positions, a.grad_charges, a.grad_cell, a.atom_bins, a.grad_scale,
-                                     a.mesh_field, a.kgrid_blocks_ready, a.G_deriv),
-            kspace_backward_t<double>(a.plan, st, a.mesh, a.pot, a.n_atoms, a.positions, a.charges, a.grad_out, a.G, a.phi_mesh,
-                                      a.rho_hat, a.rho_dc, a.phi_atoms, a.psi_mesh, a.psi_hat, a.hat_work, a.chi_mesh, a.dc,
-                                      a.partials, a.grad_positions, a.grad_charges, a.grad_cell, a.atom_bins, a.grad_scale,
-                                      a.mesh_field, a.kgrid_blocks_ready, a.G_deriv));
+  DT_SWITCH(a.dtype, kspace_backward_t<float>(a), kspace_backward_t<double>(a));
 }
 
 int mipme_fft_plan_xfused(const mipme_fft_plan* plan) { return plan && fft_plan_xfused(plan) ? 1 : 0; }
@@ -1419,10 +1280,8 @@ int mipme_pair_distance_forward(void* stream, int dtype, int idx_dtype, int64_t 
 int mipme_pack_pair_shifts(void* stream, int dtype, int64_t n_pairs, const void* shifts, void* packed, void* flag) {
   MIPME_REQUIRE(n_pairs >= 0 && flag && (n_pairs == 0 || (shifts && packed)), "invalid arguments to mipme_pack_pair_shifts");
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == MIPME_F32) return pack_pair_shifts_impl<float>(st, n_pairs, shifts, packed, flag);
-  if (dtype == MIPME_F64) return pack_pair_shifts_impl<double>(st, n_pairs, shifts, packed, flag);
-  set_error("invalid dtype %d", dtype);
-  return MIPME_EINVAL;
+  DT_SWITCH(dtype, pack_pair_shifts_impl<float>(st, n_pairs, shifts, packed, flag),
+            pack_pair_shifts_impl<double>(st, n_pairs, shifts, packed, flag));
 }
 
 int mipme_pair_distance_forward_packed(void* stream, int dtype, int64_t n_pairs, const void* pairs32,
@@ -1432,10 +1291,8 @@ int mipme_pair_distance_forward_packed(void* stream, int dtype, int64_t n_pairs,
   MIPME_REQUIRE(n_pairs == 0 || (pairs32 && packed_shifts && positions && cell && out_dist),
                 "NULL buffer passed to mipme_pair_distance_forward_packed");
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == MIPME_F32) return distance_forward_packed_impl<float>(st, n_pairs, pairs32, packed_shifts, positions, cell, out_dist);
-  if (dtype == MIPME_F64) return distance_forward_packed_impl<double>(st, n_pairs, pairs32, packed_shifts, positions, cell, out_dist);
-  set_error("invalid dtype %d", dtype);
-  return MIPME_EINVAL;
+  DT_SWITCH(dtype, distance_forward_packed_impl<float>(st, n_pairs, pairs32, packed_shifts, positions, cell, out_dist),
+            distance_forward_packed_impl<double>(st, n_pairs, pairs32, packed_shifts, positions, cell, out_dist));
 }
 
 int mipme_pair_distance_backward(void* stream, int dtype, int idx_dtype, int64_t n_pairs, int64_t n_atoms,

@@ -11,10 +11,28 @@
 // Replaces, like mesh.hip, MeshInterpolator.compute_weights / points_to_mesh / mesh_to_points
 // (reference lib/mesh_interpolator.py:303-457).
 // (device code: bricks_device.h; this file holds the host wrappers of the single-frame path)
-#define MIPME_BRICKS_MAIN_TU
 #include "bricks_device.h"
 
 namespace mipme {
+// Brick path preconditions: >= 3 bricks per axis (the 27 neighbours are distinct bricks) and enough LDS.
+bool bricks_supported(const mipme_mesh_t* m, int dtype) {
+  const size_t s = dtype == MIPME_F32 ? 4 : 8;
+  const int ns[3] = {m->nx, m->ny, m->nz};
+  for (int d = 0; d < 3; ++d) {
+    if (ns[d] <= 2 * BRICK) return false;               // need >= 3 distinct bricks per axis
+    const int rem = ns[d] % BRICK;
+    if (rem != 0 && rem < 4) return false;              // a narrow last brick would be skipped over by a stencil
+  }
+  const size_t tile = BRICK + m->order - 1;
+  if (2 * size_t(m->n_channels) * tile * tile * tile * s > 60 * 1024) return false;  // gather_grad: phi+chi per channel
+  if (spread_stage_rows(m->order, s) == 0) return false;  // spread staging
+  return true;
+}
+int64_t bins_bytes(const mipme_mesh_t* m, int64_t N, int dtype) {
+  if (!bricks_supported(m, dtype)) return 0;
+  return int64_t(bins_layout(m, N, dtype).total);
+}
+int plane_bins_capacity(const mipme_mesh_t* m, int64_t N, int dtype) { return plane_list_capacity(m, N, dtype); }
 // bands of rows a plane of this mesh is spread in (1: whole planes; 0: no plane spread) -- api.hip mipme_plane_spread_parts
 int plane_bands(const mipme_mesh_t* m, int dtype) {
   const int rows = plane_band_rows(m, dtype);
@@ -31,7 +49,7 @@ const void* bins_epart(const mipme_mesh_t* m, int64_t N, int dtype, void* bins, 
 template <typename T>
 int bins_build(hipStream_t st, const mipme_mesh_t* m, int64_t n_atoms, const void* pos, void* bins, int* live,
                const void* q, void* atom_rec, bool plane_lists) {
-  const int dtype = sizeof(T) == 4 ? MIPME_F32 : MIPME_F64;
+  const int dtype = dtype_of<T>();
   const Geom g = make_geom(m);
   const BrickGeom bg = make_brick_geom(m);
   BinsView v = bins_view(m, n_atoms, dtype, bins);
@@ -88,7 +106,7 @@ template <typename T>
 int spread_bricks(hipStream_t st, const mipme_mesh_t* m, int64_t N, void* bins, const void* val, double scale, void* mesh,
                   int* clear_count, const mipme_sr_job_t* job, bool want_epart, double* cpart, const PlaneHost* ph,
                   bool* used_planes) {
-  const int dtype = sizeof(T) == 4 ? MIPME_F32 : MIPME_F64;
+  const int dtype = dtype_of<T>();
   const BrickGeom bg = make_brick_geom(m);
   const BinsView v = bins_view(m, N, dtype, bins);
   // sparse bricks: quarter-size brick workgroups in a launch of their own, the pair sum (if any) in a second launch -- its row
@@ -120,7 +138,7 @@ int spread_bricks(hipStream_t st, const mipme_mesh_t* m, int64_t N, void* bins, 
   if (used_planes) *used_planes = false;
   // whole planes, or bands of rows for planes whose tile does not fit the launch's LDS (PlaneArgs::band_rows); the banded
   // co-scheduled kernels exist for 4-byte pair entries only (what every caller of this package uses): others keep the bricks
-  const int band_rows = v.idx.pcap > 0 ? plane_band_rows(m, sizeof(T) == 4 ? MIPME_F32 : MIPME_F64) : 0;
+  const int band_rows = v.idx.pcap > 0 ? plane_band_rows(m, dtype) : 0;
   const bool bands_ok = band_rows == m->ny || !job || (job->shift_format & kShiftFormatMask) == kShiftTable32;
   if (ph && ph->hat && ph->slot_values && !ph->keep_mesh && used_planes && clear_count && v.idx.pcap > 0 && sa.C == 1 && !sparse &&
       !sa.det && N > 0 && band_rows > 0 && bands_ok) {
@@ -294,7 +312,7 @@ int gather_bricks(hipStream_t st, const mipme_mesh_t* m, int64_t N, void* bins, 
                   const void* qsum, double self_c, double bg_c, void* out, void* raw, int accumulate, void* field,
                   const GatherTailHost* th, void* nan_flag, int* live) {
   if (N == 0) return MIPME_OK;
-  const int dtype = sizeof(T) == 4 ? MIPME_F32 : MIPME_F64;
+  const int dtype = dtype_of<T>();
   const Geom g = make_geom(m);
   const BrickGeom bg = make_brick_geom(m);
   BinsView v = bins_view(m, N, dtype, bins);
@@ -304,28 +322,12 @@ int gather_bricks(hipStream_t st, const mipme_mesh_t* m, int64_t N, void* bins, 
   if (th) {
     MIPME_REQUIRE(field && accumulate && q && qsum && th->force && th->grad_pos && th->energy && th->epart_k,
                   "the gather tail needs the field output, accumulate = 1, pair force sums and output buffers");
-    GatherTail<T> tail;
-    tail.force = (const T*)th->force;
-    tail.force_scale = T(th->force_scale);
-    tail.seed = (const T*)th->seed;
-    tail.grad_pos = (T*)th->grad_pos;
-    tail.energy = (T*)th->energy;
-    tail.epart_sr = (const double*)v.epart;
-    tail.n_sr = int((N + 64 / kRowLanes - 1) / (64 / kRowLanes));  // waves that hold a valid row (slot = first row / rows per wave)
-    tail.epart_k = (const double*)th->epart_k;
-    tail.n_k = int(th->n_k);
-    if (th->sr_reduced) {  // pre-reduced by the x stage of the convolution (kfilter.hip xconv_kernel, sr_part)
-      tail.epart_sr = tail.epart_k + tail.n_k;
-      tail.n_sr = tail.n_k;
-    }
-    tail.grad_q = (T*)th->grad_q;
-    tail.rpart = th->rpart;
-    tail.rec4 = (const AtomRecord<T>*)th->records;
-    tail.aux_seed = (const T*)th->aux_seed;
-    tail.live_flags = nullptr;
-    tail.elog = th->elog;
-    tail.elog_cursor = th->elog_cursor;
-    tail.elog_cap = th->elog_cap;
+    // the pair kernel's energy partial sums: one pair per wave that holds a valid row (slot = first row / rows per wave), or
+    // pre-reduced by the x stage of the convolution (kfilter.hip xconv_kernel, sr_part)
+    const GatherTail<T> tail =
+        th->sr_reduced ? make_gather_tail<T>(*th, (const double*)th->epart_k + th->n_k, int(th->n_k), th->records, nullptr)
+                       : make_gather_tail<T>(*th, (const double*)v.epart, int((N + 64 / kRowLanes - 1) / (64 / kRowLanes)),
+                                             th->records, nullptr);
     MIPME_REQUIRE(!tail.rpart || tail.rec4, "the cell sums of the gather need the atom records");
     if (sparse_bricks(N, bg.nb))
       MIPME_DISPATCH_STENCIL_B(m->scheme, m->order,
@@ -371,7 +373,7 @@ int gather_grad_bricks(hipStream_t st, const mipme_mesh_t* m, int64_t N, void* b
                        const void* phi, const void* chi, const void* psi_dc, const void* gscale, double self_c,
                        double bg_c, void* grad_pos, void* grad_q) {
   if (N == 0) return MIPME_OK;
-  const int dtype = sizeof(T) == 4 ? MIPME_F32 : MIPME_F64;
+  const int dtype = dtype_of<T>();
   const Geom g = make_geom(m);
   const BrickGeom bg = make_brick_geom(m);
   const BinsView v = bins_view(m, N, dtype, bins);

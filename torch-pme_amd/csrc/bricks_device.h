@@ -3,8 +3,8 @@
 //   frames.hip  independent frames in one launch (mipme_frames_*)
 //   live.hip    live bins of an MD-like loop (mipme_md_rebin / mipme_md_step)
 // Sections, in order: atom bins + binning pass; deterministic slots; spread (bricks); plane spread; gather (+ tail of the energy
-// step); host-side views of the bins buffer and the stencil dispatch macro.  bricks.hip defines MIPME_BRICKS_MAIN_TU and thereby
-// the few non-template functions other files link against.
+// step); host-side views of the bins buffer and the stencil dispatch macro.  The host functions other files link against are declared
+// in host.h and defined in bricks.hip.
 #ifndef MIPME_BRICKS_DEVICE_H
 #define MIPME_BRICKS_DEVICE_H
 #include <algorithm>
@@ -13,7 +13,7 @@
 
 #include <rocprim/device/device_radix_sort.hpp>
 
-#include "common.h"
+#include "host.h"
 #include <map>
 #include <utility>
 
@@ -61,25 +61,6 @@ __device__ __forceinline__ int wrap1(int a, int n) {
   a += a < 0 ? n : 0;
   return a >= n ? a - n : a;
 }
-
-// Brick path preconditions: >= 3 bricks per axis (the 27 neighbours are distinct bricks) and enough LDS.
-#ifdef MIPME_BRICKS_MAIN_TU
-bool bricks_supported(const mipme_mesh_t* m, int dtype) {
-  const size_t s = dtype == MIPME_F32 ? 4 : 8;
-  const int ns[3] = {m->nx, m->ny, m->nz};
-  for (int d = 0; d < 3; ++d) {
-    if (ns[d] <= 2 * BRICK) return false;               // need >= 3 distinct bricks per axis
-    const int rem = ns[d] % BRICK;
-    if (rem != 0 && rem < 4) return false;              // a narrow last brick would be skipped over by a stencil
-  }
-  const size_t tile = BRICK + m->order - 1;
-  if (2 * size_t(m->n_channels) * tile * tile * tile * s > 60 * 1024) return false;  // gather_grad: phi+chi per channel
-  if (spread_stage_rows(m->order, s) == 0) return false;  // spread staging
-  return true;
-}
-#else
-bool bricks_supported(const mipme_mesh_t* m, int dtype);
-#endif
 
 // ---- atom bins: fixed-capacity brick slots, ONE binning pass -----------------------------------------------------------
 // Brick b owns the slots [b * cap, (b + 1) * cap) of the record / weight arrays; an atom takes the next free slot of its
@@ -257,23 +238,6 @@ __device__ __forceinline__ unsigned reach_code(const int (&m)[3], int nx, int ny
   }
   return code;
 }
-
-#ifdef MIPME_BRICKS_MAIN_TU
-int plane_bins_capacity(const mipme_mesh_t* m, int64_t N, int dtype) { return plane_list_capacity(m, N, dtype); }
-int plane_bands(const mipme_mesh_t* m, int dtype);
-#else
-int plane_bins_capacity(const mipme_mesh_t* m, int64_t N, int dtype);
-int plane_bands(const mipme_mesh_t* m, int dtype);
-#endif
-
-#ifdef MIPME_BRICKS_MAIN_TU
-int64_t bins_bytes(const mipme_mesh_t* m, int64_t N, int dtype) {
-  if (!bricks_supported(m, dtype)) return 0;
-  return int64_t(bins_layout(m, N, dtype).total);
-}
-#else
-int64_t bins_bytes(const mipme_mesh_t* m, int64_t N, int dtype);
-#endif
 
 __device__ __forceinline__ void split_runtime(double u, bool even, int& m, double& x) {
   if (even) {
@@ -1712,6 +1676,32 @@ struct GatherTail {
   int* elog_cursor = nullptr;
   int elog_cap = 0, elog_stride = 1;
 };
+// The device form of a host-side tail.  What differs between the launches stays with the caller: where the pair kernel's energy
+// partial sums are (per wave in the bins buffer, or th.epart_k + th.n_k once the x stage of the convolution has reduced them),
+// the atom records of the cell sums, and the flag word of a live step.
+template <typename T>
+static GatherTail<T> make_gather_tail(const GatherTailHost& th, const double* epart_sr, int n_sr, const void* rec4,
+                                      const void* live_flags) {
+  GatherTail<T> tail;
+  tail.force = (const T*)th.force;
+  tail.force_scale = T(th.force_scale);
+  tail.seed = (const T*)th.seed;
+  tail.grad_pos = (T*)th.grad_pos;
+  tail.energy = (T*)th.energy;
+  tail.epart_sr = epart_sr;
+  tail.n_sr = n_sr;
+  tail.epart_k = (const double*)th.epart_k;
+  tail.n_k = int(th.n_k);
+  tail.grad_q = (T*)th.grad_q;
+  tail.rpart = th.rpart;
+  tail.rec4 = (const AtomRecord<T>*)rec4;
+  tail.aux_seed = (const T*)th.aux_seed;
+  tail.live_flags = (const int*)live_flags;
+  tail.elog = th.elog;
+  tail.elog_cursor = th.elog_cursor;
+  tail.elog_cap = th.elog_cap;
+  return tail;
+}
 
 // R sums of a workgroup -> rpart[9 * block ...].  r3: lanes 0..2 of every 8-lane atom group hold r_c * gp_l for c = 0..2 (l = the
 // lane's Cartesian component of the gradient), zero elsewhere.  Uniform call (barrier inside).

@@ -253,7 +253,8 @@ static inline size_t plan_counter_words(int nx, int ny, int nz) {
   return size_t((nx + 7) / 8) * size_t((ny + 7) / 8) * size_t((nz + 7) / 8) + 1 + size_t(kPlaneSub) * size_t(nx) + 1;
 }
 
-// Host-side description of the gather's tail (energy + force assembly in the gather launch, csrc/bricks.hip GatherTail)
+// Host-side description of the gather's tail (energy + force assembly in the gather launch; device form: bricks_device.h GatherTail,
+// make_gather_tail; filled by the entry points through host.h tail_attach_plan_scratch / tail_attach_energy_log)
 struct GatherTailHost {
   const void* force;   // (N,3) pair force sums
   double force_scale;  // 1/2 for a full list

@@ -141,16 +141,6 @@ __global__ __launch_bounds__(256) void frames_finalize_kernel(const FrameDev<T>*
   f.grad_pos[t] = gscale[blockIdx.y] * f.q[t / 3] * (f.force_scale * f.force[t] + f.field[t]);
 }
 
-static void frame_correction_terms(const mipme_potential_t* pot, double& self_c, double& bg_c) {
-  // potentials/coulomb.py:144-158, potentials/inversepowerlaw.py:143-166 (as correction_terms in api.hip)
-  const int p = pot->kind == MIPME_COULOMB ? 1 : pot->exponent;
-  const double two_s2 = 2.0 * pot->smearing * pot->smearing;
-  self_c = pot->prefactor / std::tgamma(0.5 * p + 1.0) / std::pow(two_s2, 0.5 * p);
-  bg_c = p >= 3 ? 0.0
-                : pot->prefactor * std::pow(3.14159265358979323846, 1.5) * std::pow(two_s2, 0.5 * (3 - p)) /
-                      ((3 - p) * std::tgamma(0.5 * p));
-}
-
 // int32 words of a frame's counter buffer: brick counters + overflow counter, and -- when the plane spread applies to the frame
 // (plane_list_capacity) -- the plane lists' counters + their overflow counter
 static int64_t frame_counter_ints(const mipme_mesh_t* m, int64_t n_atoms, int dtype) {
@@ -205,8 +195,8 @@ static int frames_table_build_t(int n_frames, const mipme_frame_t* fr, const mip
   MIPME_REQUIRE(pot->smearing > 0 && (pfast == 1 || pfast == 6), "the frames path covers 1/r and 1/r^6 with a smearing");
   const FastRS cf = make_fast_rs(s);
   double self_c, bg_c;
-  frame_correction_terms(pot, self_c, bg_c);
-  const int dtype = sizeof(T) == 4 ? MIPME_F32 : MIPME_F64;
+  correction_terms(pot, self_c, bg_c);
+  const int dtype = dtype_of<T>();
   FrameDev<T>* out = (FrameDev<T>*)host_table;
   for (int k = 0; k < n_frames; ++k) {
     const mipme_frame_t& f = fr[k];
@@ -262,20 +252,14 @@ static int frames_table_build_t(int n_frames, const mipme_frame_t* fr, const mip
     d.force = (const T*)f.force;
     d.grad_pos = (T*)f.grad_positions;
     d.force_scale = f.full_list ? T(0.5) : T(1);
-    d.tail.force = d.force;
-    d.tail.force_scale = d.force_scale;
-    d.tail.seed = (const T*)f.grad_seed;
-    d.tail.grad_pos = d.grad_pos;
-    d.tail.energy = d.energy;
-    d.tail.epart_sr = v.epart;
-    d.tail.n_sr = int((f.n_atoms + 64 / kRowLanes - 1) / (64 / kRowLanes));
-    d.tail.epart_k = nullptr;  // per batch entry: set by frames_forward (plan scratch)
-    d.tail.n_k = 0;
-    d.tail.grad_q = nullptr;   // (the frames path forms energy + forces only)
-    d.tail.rpart = nullptr;
-    d.tail.rec4 = nullptr;
-    d.tail.aux_seed = nullptr;
-    d.tail.live_flags = nullptr;
+    // energy + forces only (no grad_q, no cell sums); epart_k / n_k per batch entry: set by the gather kernel (plan scratch)
+    GatherTailHost th{};
+    th.force = f.force;
+    th.force_scale = f.full_list ? 0.5 : 1.0;
+    th.seed = f.grad_seed;
+    th.grad_pos = f.grad_positions;
+    th.energy = f.energy;
+    d.tail = make_gather_tail<T>(th, v.epart, int((f.n_atoms + 64 / kRowLanes - 1) / (64 / kRowLanes)), nullptr, nullptr);
     d.use_tail = f.use_tail != 0;
     d.rows.epart = f.use_tail ? v.epart : nullptr;
     out[k] = d;
@@ -283,24 +267,10 @@ static int frames_table_build_t(int n_frames, const mipme_frame_t* fr, const mip
   return MIPME_OK;
 }
 
-int convolve_xfused(mipme_fft_plan*, hipStream_t, const void*, const void*, void*, void*, void*, int64_t, const mipme_mesh_t*,
-                    const mipme_potential_t*, void*, void*, const void*, int64_t, const RowRideHost*, void*, const ConvCell*);
-int64_t xconv_blocks(const mipme_fft_plan*);
-void* fft_plan_tail_scratch(mipme_fft_plan*, int64_t bytes);
-bool fft_plan_xfused(const mipme_fft_plan*);
-int fft_plan_batch(const mipme_fft_plan*);
-bool fft_plan_plane_forward_ok_batched(const mipme_fft_plan*);
-void fft_plan_set_forward_done(mipme_fft_plan*, bool, int);
-void* fft_plan_hat_parts(mipme_fft_plan*, hipStream_t, int);
-static int plane_parts_setting() {  // (as api.hip plane_spread_parts_setting)
-  static const int parts_env = [] { const char* e = getenv("MIPME_PLANE_PARTS"); return e ? atoi(e) : 2; }();
-  return parts_env < 1 ? 1 : (parts_env > 8 ? 8 : parts_env);
-}
-
 template <typename T>
 static int frames_forward_t(mipme_fft_plan* plan, hipStream_t st, int n_frames, const mipme_frame_t* fr, const void* table,
-                            const mipme_potential_t* /*unused*/, const void* G, int64_t G_stride, void* rho_all, void* hat_all,
-                            void* phi_all, void* dc_all, int pfast) {
+                            const void* G, int64_t G_stride, void* rho_all, void* hat_all, void* phi_all, void* dc_all,
+                            int pfast) {
   const FrameDev<T>* tb = (const FrameDev<T>*)table;
   const mipme_mesh_t* m = &fr[0].mesh;
   const BrickGeom bg = make_brick_geom(m);
@@ -316,10 +286,9 @@ static int frames_forward_t(mipme_fft_plan* plan, hipStream_t st, int n_frames, 
   const unsigned grid_x = unsigned(bg.nb) + unsigned((max_atoms + rpb - 1) / rpb);
   const bool compact = fr[0].shift_format == kShiftTable32;  // frames_check: the same format for every frame
   // plane spread (every frame of the batch has its plane lists: frame_plane_lists, decided when the table was built)
-  const int dtype_f = sizeof(T) == 4 ? MIPME_F32 : MIPME_F64;
   bool planes = fft_plan_plane_forward_ok_batched(plan);
-  for (int k = 0; k < n_frames && planes; ++k) planes = frame_plane_lists(fr[k], dtype_f);
-  fft_plan_set_forward_done(plan, false, 1);
+  for (int k = 0; k < n_frames && planes; ++k) planes = frame_plane_lists(fr[k], dtype_of<T>());
+  fft_plan_begin_step(plan);
   if (!planes) note_cosched_kernel("frames_spread_rows_kernel");
   if (planes) {
     PlaneArgs<T> pa;
@@ -330,10 +299,10 @@ static int frames_forward_t(mipme_fft_plan* plan, hipStream_t st, int n_frames, 
     // a batch has its frames for parallelism: as many parts as keep the plane workgroups of the launch at or below 128 (the
     // single-frame optimum at 64^3: 2 x 64); measured on 8 x 8000 ions / 32^3 fp64: 1 part 0.1243, 2 parts 0.1291, 3 parts
     // 0.1322 ms (bricks 0.1336); 16 x 1000 atoms / 32^3 fp32: 0.0569 / 0.0633 / 0.0691 (bricks 0.0600)
-    pa.parts = plane_parts_setting();
+    pa.parts = plane_spread_parts_setting();
     while (pa.parts > 1 && int64_t(pa.parts) * m->nx * n_frames > 128) --pa.parts;
     if (pa.parts > 1) {
-      pa.hat_more = (Cplx<T>*)fft_plan_hat_parts(plan, st, 7);
+      pa.hat_more = (Cplx<T>*)fft_plan_hat_parts(plan, st, kPlanePartsMax - 1);
       pa.more_stride = Mh * n_frames;
       if (!pa.hat_more) pa.parts = 1;
     }
@@ -371,15 +340,15 @@ static int frames_forward_t(mipme_fft_plan* plan, hipStream_t st, int n_frames, 
   bool all_tail = true;
   for (int k = 0; k < n_frames; ++k) all_tail = all_tail && fr[k].use_tail != 0;
   const int64_t n_k = xconv_blocks(plan) / n_frames;  // blocks of the x stage per batch entry
-  double* epart_k = all_tail ? (double*)fft_plan_tail_scratch(plan, int64_t(sizeof(double)) * n_k * n_frames) : nullptr;
-  MIPME_REQUIRE(!all_tail || epart_k, "could not allocate the energy partial sums of the plan (not possible during stream "
-                                      "capture: run one evaluation before capturing)");
-  int rc = convolve_xfused(plan, st, rho_all, G, hat_all, phi_all, dc_all, G_stride, nullptr, nullptr, nullptr, epart_k, nullptr, 0, nullptr, nullptr, nullptr);
+  void* epart_k = nullptr;
+  int rc;
+  if (all_tail && (rc = fft_plan_tail_scratch(plan, int64_t(sizeof(double)) * n_k * n_frames, &epart_k))) return rc;
+  rc = convolve_xfused(plan, st, rho_all, G, hat_all, phi_all, dc_all, G_stride, nullptr, nullptr, nullptr, epart_k, nullptr, 0, nullptr, nullptr, nullptr);
   if (rc) return rc;
   if (all_tail) {  // energy + forces of every frame in the gather launch
     MIPME_DISPATCH_STENCIL_B(m->scheme, m->order,
                              ((void)S, frames_gather_tail_kernel<N, T><<<dim3(unsigned(bg.nb), F), GATHER_THREADS, 0, st>>>(
-                                 tb, epart_k, int(n_k))));
+                                 tb, (const double*)epart_k, int(n_k))));
     MIPME_LAUNCH_CHECK();
     return MIPME_OK;
   }
@@ -421,8 +390,8 @@ int mipme_frames_table_build(int dtype, int n_frames, const mipme_frame_t* frame
   if (rc) return rc;
   MIPME_REQUIRE(pot && host_table && host_table_bytes >= mipme_frames_table_bytes(dtype, n_frames),
                 "invalid arguments to mipme_frames_table_build");
-  if (dtype == MIPME_F32) return frames_table_build_t<float>(n_frames, frames, pot, host_table);
-  return frames_table_build_t<double>(n_frames, frames, pot, host_table);
+  DT_SWITCH(dtype, frames_table_build_t<float>(n_frames, frames, pot, host_table),
+            frames_table_build_t<double>(n_frames, frames, pot, host_table));
 }
 
 int mipme_frames_table_energy_log(int dtype, int n_frames, void* host_table, int64_t host_table_bytes, void* log, void* cursors,
@@ -430,8 +399,8 @@ int mipme_frames_table_energy_log(int dtype, int n_frames, void* host_table, int
   MIPME_REQUIRE((dtype == MIPME_F32 || dtype == MIPME_F64) && n_frames > 0 && host_table &&
                     host_table_bytes >= mipme_frames_table_bytes(dtype, n_frames) && (!log || (cursors && capacity > 0)),
                 "invalid arguments to mipme_frames_table_energy_log");
-  if (dtype == MIPME_F32) return frames_table_energy_log_t<float>(n_frames, host_table, log, cursors, capacity);
-  return frames_table_energy_log_t<double>(n_frames, host_table, log, cursors, capacity);
+  DT_SWITCH(dtype, frames_table_energy_log_t<float>(n_frames, host_table, log, cursors, capacity),
+            frames_table_energy_log_t<double>(n_frames, host_table, log, cursors, capacity));
 }
 
 int mipme_frames_forward(mipme_fft_plan* plan, void* stream, int dtype, int n_frames, const mipme_frame_t* frames,
@@ -448,11 +417,11 @@ int mipme_frames_forward(mipme_fft_plan* plan, void* stream, int dtype, int n_fr
   const int pfast = fast_rs_exponent(s);
   MIPME_REQUIRE(pfast == 1 || pfast == 6, "the frames path covers 1/r and 1/r^6 with a smearing");
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == MIPME_F32)
-    return frames_forward_t<float>(plan, st, n_frames, frames, device_table, pot, G, G_stride, rho_mesh_all, hat_work_all,
-                                   phi_mesh_all, dc_all, pfast);
-  return frames_forward_t<double>(plan, st, n_frames, frames, device_table, pot, G, G_stride, rho_mesh_all, hat_work_all,
-                                  phi_mesh_all, dc_all, pfast);
+  DT_SWITCH(dtype,
+            frames_forward_t<float>(plan, st, n_frames, frames, device_table, G, G_stride, rho_mesh_all, hat_work_all,
+                                    phi_mesh_all, dc_all, pfast),
+            frames_forward_t<double>(plan, st, n_frames, frames, device_table, G, G_stride, rho_mesh_all, hat_work_all,
+                                     phi_mesh_all, dc_all, pfast));
 }
 
 int64_t mipme_frames_counter_ints(const mipme_mesh_t* mesh, int64_t n_atoms, int dtype) {

@@ -1,0 +1,186 @@
+// Host-side interfaces between the libmipme translation units: the one declaration of every host function that is defined in
+// one .hip file and called from another, the few structs they exchange, and the helpers every entry point shares.  Each file
+// that defines or calls one of these includes this header, so a definition that drifts from its declaration does not compile.
+#pragma once
+
+#include <algorithm>
+#include <climits>
+#include <cmath>
+
+#include "common.h"
+
+namespace mipme {
+
+template <typename T>
+constexpr int dtype_of() {
+  return sizeof(T) == 4 ? MIPME_F32 : MIPME_F64;
+}
+
+#define DT_SWITCH(dtype, CALL_F32, CALL_F64)                    \
+  do {                                                          \
+    if ((dtype) == MIPME_F32) return CALL_F32;                  \
+    if ((dtype) == MIPME_F64) return CALL_F64;                  \
+    mipme::set_error("invalid dtype %d", int(dtype));           \
+    return MIPME_EINVAL;                                        \
+  } while (0)
+
+// ---- mesh.hip: particle <-> mesh without bins -------------------------------------------------------------------------------
+template <typename T> int spread_impl(hipStream_t st, const mipme_mesh_t* m, int64_t n_atoms, const void* pos, const void* val, double scale,
+                                      void* mesh);
+template <typename T> int gather_impl(hipStream_t st, const mipme_mesh_t* m, int64_t n_atoms, const void* pos, const void* mesh, void* out);
+template <typename T> int gather_epilogue_impl(hipStream_t st, const mipme_mesh_t* m, int64_t n_atoms, const void* pos, const void* mesh,
+                                               const void* q, const void* qsum, double self_c, double bg_c, void* out, void* raw,
+                                               int accumulate, void* nan_flag);
+template <typename T> int gather_grad_impl(hipStream_t st, const mipme_mesh_t* m, int64_t n_atoms, const void* pos, const void* q,
+                                           const void* gout, const void* phi, const void* chi, const void* gsum_dc, const void* gscale,
+                                           double self_c, double bg_c, void* grad_pos, void* grad_q);
+
+// ---- kfilter.hip: the FFT plan, the k-space filter and the fused convolution -------------------------------------------------
+struct FftDims { int dtype, nx, ny, nz, batch; };
+int fft_plan_create(int dtype, int nx, int ny, int nz, int batch, mipme_fft_plan** out);
+int fft_plan_destroy(mipme_fft_plan* p);
+FftDims fft_plan_dims(const mipme_fft_plan* p);
+int fft_plan_batch(const mipme_fft_plan* p);
+bool fft_plan_xfused(const mipme_fft_plan* p);
+int* fft_plan_brick_count(const mipme_fft_plan* p);
+int fft_forward(mipme_fft_plan* p, hipStream_t st, const void* in, void* out);
+int fft_inverse(mipme_fft_plan* p, hipStream_t st, void* in, void* out);
+int64_t xconv_blocks(const mipme_fft_plan* p);
+int convolve_xfused(mipme_fft_plan* p, hipStream_t st, const void* mesh_in, const void* G, void* hat, void* mesh_out,
+                    void* dc, int64_t G_stride, const mipme_mesh_t* cell_mesh, const mipme_potential_t* cell_pot,
+                    void* cell_partials, void* epart, const void* sr_part, int64_t n_sr_part, const RowRideHost* rh,
+                    void* err_flag, const ConvCell* cc);
+// Every entry point that runs a convolution on the plan calls this first: it clears what a plane spread tells the convolution
+// ("forward planes done", their parts, "y columns pending"), so that a call that failed half-way cannot make the next one skip
+// its forward planes.
+void fft_plan_begin_step(mipme_fft_plan* p);
+bool fft_plan_plane_forward_ok(const mipme_fft_plan* p);
+bool fft_plan_plane_forward_ok_batched(const mipme_fft_plan* p);
+void fft_plan_set_forward_done(mipme_fft_plan* p, bool done, int parts);
+void fft_plan_set_forward_ycols(mipme_fft_plan* p, bool pending);
+void* fft_plan_hat_parts(mipme_fft_plan* p, hipStream_t st, int n_more);
+// *out = the plan's scratch for the energy partial sums of a gather tail (`bytes` of it, zeroed when first allocated), or
+// MIPME_EINVAL with the advice to warm up before a stream capture
+int fft_plan_tail_scratch(mipme_fft_plan* p, int64_t bytes, void** out);
+template <typename T> int kfilter_build_impl(hipStream_t st, const mipme_mesh_t* m, const mipme_potential_t* pot, void* G);
+template <typename T> int kfilter_deriv_impl(hipStream_t st, const mipme_mesh_t* m, const mipme_potential_t* pot, void* D);
+template <typename T> int apply_filter_impl(hipStream_t st, int64_t Mh, int C, const void* hat, const void* G, void* out, void* dc);
+template <typename T> int apply_filter_cellgrad_impl(hipStream_t st, const mipme_mesh_t* m, const mipme_potential_t* pot, const void* psi_hat,
+                                                     const void* rho_hat, const void* G, void* out, void* dc, void* partials);
+int64_t cellgrad_blocks(const mipme_mesh_t* m);
+int64_t cellgrad_scratch_doubles();
+template <typename T> int cellgrad_finalize_impl(hipStream_t st, const mipme_mesh_t* m, double bg, int64_t n_atoms, void* partials,
+                                                 const void* pos, const void* grad_pos, const void* gout, const void* phi_atoms,
+                                                 const void* rho_dc, const void* psi_dc, const void* energy_scale, void* grad_cell,
+                                                 int64_t kgrid_blocks, const void* field, const void* q);
+template <typename T> int cell_tail_finalize_impl(hipStream_t st, const mipme_mesh_t* m, double bg, double pair_scale, int64_t n_rows,
+                                                  int64_t n_bricks, const void* rows, const void* rpart, const void* dc, const void* seed, void* out);
+
+// ---- rspace.hip: pair-list kernels -------------------------------------------------------------------------------------------
+template <typename T, typename I> int rspace_forward_impl(hipStream_t st, int64_t P, int64_t N, int C, const void* pairs, const void* dist, const void* q,
+                                                          const void* mask, int full, const mipme_potential_t* pot, int accumulate, void* out);
+template <typename T, typename I> int rspace_backward_impl(hipStream_t st, int64_t P, int64_t N, int C, const void* pairs, const void* dist,
+                                                           const void* q, const void* mask, int full, const mipme_potential_t* pot, const void* g,
+                                                           const void* gscale, void* grad_d, void* grad_q);
+template <typename T, typename I> int distance_forward_impl(hipStream_t st, int64_t P, const void* pairs, const void* pos, const void* cell,
+                                                            const void* shifts, void* out);
+template <typename T, typename I> int distance_backward_impl(hipStream_t st, int64_t P, int64_t N, const void* pairs, const void* pos, const void* cell,
+                                                             const void* shifts, const void* grad_d, void* partials, void* grad_pos, void* grad_cell);
+template <typename T> int pack_pair_shifts_impl(hipStream_t st, int64_t P, const void* shifts, void* packed, void* flag);
+template <typename T> int distance_forward_packed_impl(hipStream_t st, int64_t P, const void* pairs, const void* packed, const void* pos,
+                                                       const void* cell, void* out);
+int64_t pair_partials_blocks(int64_t P);
+
+// ---- bricks.hip: the brick-binned single-frame path --------------------------------------------------------------------------
+bool bricks_supported(const mipme_mesh_t* m, int dtype);
+int64_t bins_bytes(const mipme_mesh_t* m, int64_t N, int dtype);
+int plane_bins_capacity(const mipme_mesh_t* m, int64_t N, int dtype);
+int plane_bands(const mipme_mesh_t* m, int dtype);
+const void* bins_epart(const mipme_mesh_t* m, int64_t N, int dtype, void* bins, int64_t* n);
+bool sr_job_fusable(const mipme_sr_job_t* job);
+template <typename T> int bins_build(hipStream_t st, const mipme_mesh_t* m, int64_t n_atoms, const void* pos, void* bins, int* live,
+                                     const void* q, void* atom_rec, bool plane_lists = false);
+template <typename T> int spread_bricks(hipStream_t st, const mipme_mesh_t* m, int64_t N, void* bins, const void* val, double scale, void* mesh,
+                                        int* clear_count, const mipme_sr_job_t* job, bool want_epart, double* cpart, const PlaneHost* ph = nullptr,
+                                        bool* used_planes = nullptr);
+template <typename T> int gather_bricks(hipStream_t st, const mipme_mesh_t* m, int64_t N, void* bins, const void* mesh, const void* q,
+                                        const void* qsum, double self_c, double bg_c, void* out, void* raw, int accumulate, void* field,
+                                        const GatherTailHost* th, void* nan_flag, int* live);
+template <typename T> int gather_grad_bricks(hipStream_t st, const mipme_mesh_t* m, int64_t N, void* bins, const void* q, const void* gout,
+                                             const void* phi, const void* chi, const void* psi_dc, const void* gscale, double self_c,
+                                             double bg_c, void* grad_pos, void* grad_q);
+
+// ---- live.hip: the MD step on live bins --------------------------------------------------------------------------------------
+bool live_supported(const mipme_mesh_t* m, int64_t N, int dtype);
+int64_t live_lists_ints(const mipme_mesh_t* m, int64_t N);
+template <typename T> int live_rebin(hipStream_t st, const mipme_mesh_t* m, int64_t N, const void* rec4, void* bins, void* lists, void* host_flags);
+template <typename T> int live_spread(hipStream_t st, const mipme_mesh_t* m, int64_t N, const void* rec4, void* bins, void* lists, void* mesh,
+                                      const mipme_sr_job_t* job, void* host_flags, double* cpart);
+template <typename T> int live_gather(hipStream_t st, const mipme_mesh_t* m, int64_t N, const void* rec4, void* bins, void* lists, const void* mesh,
+                                      const void* qsum, double self_c, double bg_c, void* out, void* field, const GatherTailHost* th, void* nan_flag);
+
+// ---- shared by the entry points of a step (api.hip, frames.hip) --------------------------------------------------------------
+// self / background corrections: potentials/coulomb.py:144-158, potentials/inversepowerlaw.py:143-166
+inline void correction_terms(const mipme_potential_t* pot, double& self_c, double& bg_c) {
+  const int p = pot->kind == MIPME_COULOMB ? 1 : pot->exponent;
+  const double two_s2 = 2.0 * pot->smearing * pot->smearing;
+  self_c = pot->prefactor / std::tgamma(0.5 * p + 1.0) / std::pow(two_s2, 0.5 * p);
+  if (p >= 3)
+    bg_c = 0.0;
+  else
+    bg_c = pot->prefactor * std::pow(3.14159265358979323846, 1.5) * std::pow(two_s2, 0.5 * (3 - p)) /
+           ((3 - p) * std::tgamma(0.5 * p));
+}
+
+// MIPME_PLANE_PARTS: workgroups per plane of the plane spread (default 2, at most kPlanePartsMax; read once per process)
+static constexpr int kPlanePartsMax = 8;
+inline int plane_spread_parts_setting() {
+  static const int parts_env = [] { const char* e = getenv("MIPME_PLANE_PARTS"); return e ? atoi(e) : 2; }();
+  return parts_env < 1 ? 1 : (parts_env > kPlanePartsMax ? kPlanePartsMax : parts_env);
+}
+
+// The plan's scratch behind a gather tail: the energy partial sums of the convolution's x stage, one per block, and behind them
+// the pair kernel's sums, which that stage reduces to two more per block
+inline int tail_attach_plan_scratch(GatherTailHost& tail, mipme_fft_plan* plan) {
+  void* scratch = nullptr;
+  tail.n_k = xconv_blocks(plan);
+  tail.sr_reduced = 1;
+  const int rc = fft_plan_tail_scratch(plan, 3 * int64_t(sizeof(double)) * tail.n_k, &scratch);
+  tail.epart_k = scratch;
+  return rc;
+}
+
+// The energy of a gather tail also goes to a log (mipme.h, energy_log): needs the log's cursor and a capacity the device's int
+// holds.  `needs`: the start of the refusal, up to and including "energy_log_cursor".
+inline int tail_attach_energy_log(GatherTailHost& tail, void* log, void* cursor, int64_t capacity, const char* needs) {
+  MIPME_REQUIRE(cursor && capacity > 0 && capacity <= INT_MAX, "%s and a capacity > 0 (at most %d)", needs, INT_MAX);
+  tail.elog = (double*)log;
+  tail.elog_cursor = (int*)cursor;
+  tail.elog_cap = int(capacity);
+  return MIPME_OK;
+}
+
+// cell_work of an energy step's cell gradient (mipme_cell_tail_work), in doubles:
+// [rows 25 per rider][rpart 9 per brick][cwave 9 per wavefront of the pair kernel][wbuf: one real per half-grid point]
+struct CellWork {
+  int64_t n_riders, n_bricks, n_waves;
+  double *rows, *rpart, *cwave;
+  void* wbuf;
+  int64_t total;
+};
+inline CellWork cell_work_layout(const mipme_mesh_t* m, int64_t N, void* base) {
+  CellWork w;
+  const int64_t Mh = int64_t(m->nx) * m->ny * (m->nz / 2 + 1);
+  w.n_riders = std::min<int64_t>(256, std::max<int64_t>(8, Mh / 2048));  // ~2 k-points per rider thread (1024 threads)
+  w.n_bricks = int64_t((m->nx + 7) / 8) * ((m->ny + 7) / 8) * ((m->nz + 7) / 8);
+  w.n_waves = (N + 3) / 4;  // 16 lanes per row: 4 rows per wavefront (rows_body.h)
+  double* b = (double*)base;
+  w.rows = b;
+  w.rpart = w.rows + 25 * w.n_riders;
+  w.cwave = w.rpart + 9 * w.n_bricks;
+  w.wbuf = w.cwave + 9 * w.n_waves;
+  w.total = 25 * w.n_riders + 9 * w.n_bricks + 9 * w.n_waves + Mh;  // (wbuf: Mh reals of <= 8 bytes)
+  return w;
+}
+
+}  // namespace mipme

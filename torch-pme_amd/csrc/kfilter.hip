@@ -12,7 +12,7 @@
 #include <cstdlib>
 #include <new>
 
-#include "common.h"
+#include "host.h"
 #include "kpot.h"
 #include "fft_lds.h"
 
@@ -1176,9 +1176,6 @@ int convolve_xfused(mipme_fft_plan* p, hipStream_t st, const void* mesh_in, cons
                                    sr_part, n_sr_part, cc);
 }
 
-int fft_forward(mipme_fft_plan* p, hipStream_t st, const void* in, void* out);
-int fft_inverse(mipme_fft_plan* p, hipStream_t st, void* in, void* out);
-
 // the plane spread can stand in for the forward (y,z) launch of convolve_xfused_t: own single-launch plane kernels, one mesh
 bool fft_plan_plane_forward_ok(const mipme_fft_plan* p) {
   return p && p->own_yz && !p->split_yz && p->batch == 1;
@@ -1194,6 +1191,7 @@ void fft_plan_set_forward_done(mipme_fft_plan* p, bool done, int parts) {
 void fft_plan_set_forward_ycols(mipme_fft_plan* p, bool pending) {
   if (p) p->forward_ycols = pending && p->forward_done;
 }
+void fft_plan_begin_step(mipme_fft_plan* p) { fft_plan_set_forward_done(p, false, 1); }
 // room for `n_more` more half-complex meshes (the partial transforms of a plane spread with several workgroups per plane);
 // allocated on first use -- not possible during stream capture: NULL then (the caller runs with one part)
 void* fft_plan_hat_parts(mipme_fft_plan* p, hipStream_t st, int n_more) {
@@ -1430,12 +1428,11 @@ int fft_plan_create(int dtype, int nx, int ny, int nz, int batch, mipme_fft_plan
   return MIPME_OK;
 }
 
-struct FftDims { int dtype, nx, ny, nz, batch; };
 FftDims fft_plan_dims(const mipme_fft_plan* p) { return FftDims{p->dtype, p->nx, p->ny, p->nz, p->batch}; }
 int* fft_plan_brick_count(const mipme_fft_plan* p) { return p->brick_count; }
 
 // Allocated on first use (a synchronous hipMalloc + hipMemset: not during stream capture -- the callers warm up first).
-void* fft_plan_tail_scratch(mipme_fft_plan* p, int64_t bytes) {
+static void* tail_scratch_or_null(mipme_fft_plan* p, int64_t bytes) {
   if (p->tail_scratch && p->tail_bytes >= bytes) return p->tail_scratch;
   if (p->tail_scratch) return nullptr;  // the size is a function of the plan's mesh: cannot change
   void* buf = nullptr;
@@ -1447,6 +1444,12 @@ void* fft_plan_tail_scratch(mipme_fft_plan* p, int64_t bytes) {
   p->tail_scratch = buf;
   p->tail_bytes = bytes;
   return buf;
+}
+int fft_plan_tail_scratch(mipme_fft_plan* p, int64_t bytes, void** out) {
+  *out = tail_scratch_or_null(p, bytes);
+  MIPME_REQUIRE(*out, "could not allocate the energy partial sums of the plan (not possible during stream capture: run one "
+                      "evaluation before capturing)");
+  return MIPME_OK;
 }
 
 int fft_plan_destroy(mipme_fft_plan* p) {

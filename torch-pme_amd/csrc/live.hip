@@ -3,7 +3,6 @@
 #include "bricks_device.h"
 
 namespace mipme {
-bool sr_job_fusable(const mipme_sr_job_t* job);  // (bricks.hip)
 // ==========================================================================================================================
 // Live bins: the particle <-> mesh kernels of an MD-like loop (mipme_md_rebin / mipme_md_step, csrc/api.hip)
 // --------------------------------------------------------------------------------------------------------------------------
@@ -570,7 +569,7 @@ bool live_supported(const mipme_mesh_t* m, int64_t N, int dtype) {
 
 template <typename T>
 int live_rebin(hipStream_t st, const mipme_mesh_t* m, int64_t N, const void* rec4, void* bins, void* lists, void* host_flags) {
-  const int dtype = sizeof(T) == 4 ? MIPME_F32 : MIPME_F64;
+  const int dtype = dtype_of<T>();
   MIPME_REQUIRE(live_supported(m, N, dtype), "mesh / atom count outside the live-bin kernels' range");
   const Geom g = make_geom(m);
   const BrickGeom bg = make_brick_geom(m);
@@ -590,7 +589,7 @@ int live_rebin(hipStream_t st, const mipme_mesh_t* m, int64_t N, const void* rec
 template <typename T>
 int live_spread(hipStream_t st, const mipme_mesh_t* m, int64_t N, const void* rec4, void* bins, void* lists, void* mesh,
                 const mipme_sr_job_t* job, void* host_flags, double* cpart) {
-  const int dtype = sizeof(T) == 4 ? MIPME_F32 : MIPME_F64;
+  const int dtype = dtype_of<T>();
   const BrickGeom bg = make_brick_geom(m);
   const BinsView v = bins_view(m, N, dtype, bins);
   const LiveLists ll = live_view(m, N, lists, nullptr);
@@ -647,30 +646,15 @@ int live_spread(hipStream_t st, const mipme_mesh_t* m, int64_t N, const void* re
 template <typename T>
 int live_gather(hipStream_t st, const mipme_mesh_t* m, int64_t N, const void* rec4, void* bins, void* lists, const void* mesh,
                 const void* qsum, double self_c, double bg_c, void* out, void* field, const GatherTailHost* th, void* nan_flag) {
-  const int dtype = sizeof(T) == 4 ? MIPME_F32 : MIPME_F64;
+  const int dtype = dtype_of<T>();
   const Geom g = make_geom(m);
   const BrickGeom bg = make_brick_geom(m);
   const BinsView v = bins_view(m, N, dtype, bins);
   const LiveLists ll = live_view(m, N, lists, nullptr);
   MIPME_REQUIRE(th && th->force && th->grad_pos && th->energy && th->epart_k && out && qsum, "NULL buffer passed to the live gather");
-  GatherTail<T> tail;
-  tail.force = (const T*)th->force;
-  tail.force_scale = T(th->force_scale);
-  tail.seed = (const T*)th->seed;
-  tail.grad_pos = (T*)th->grad_pos;
-  tail.energy = (T*)th->energy;
-  tail.epart_k = (const double*)th->epart_k;
-  tail.n_k = int(th->n_k);
-  tail.epart_sr = tail.epart_k + tail.n_k;  // pre-reduced by the x stage of the convolution
-  tail.n_sr = tail.n_k;
-  tail.grad_q = (T*)th->grad_q;
-  tail.rpart = th->rpart;
-  tail.rec4 = (const AtomRecord<T>*)rec4;
-  tail.aux_seed = (const T*)th->aux_seed;
-  tail.live_flags = (const int*)th->live_flags;
-  tail.elog = th->elog;
-  tail.elog_cursor = th->elog_cursor;
-  tail.elog_cap = th->elog_cap;
+  // (the pair kernel's energy partial sums: pre-reduced by the x stage of the convolution)
+  const GatherTail<T> tail =
+      make_gather_tail<T>(*th, (const double*)th->epart_k + th->n_k, int(th->n_k), rec4, th->live_flags);
   MIPME_DISPATCH_ORDER(m->order, (live_gather_tail_kernel<N, T><<<brick_grid(bg), GATHER_THREADS, 0, st>>>(
                                      g, bg, v.idx, ll.rec_now, (const T*)v.wts, (const AtomRecord<T>*)rec4, (const T*)mesh,
                                      (const T*)qsum, T(1.0 / m->volume), T(self_c), T(bg_c), (T*)out, (T*)field, tail,

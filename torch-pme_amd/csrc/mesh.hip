@@ -7,7 +7,7 @@
 // (ty,tz) column of the n^3 stencil and walks tx.  Consecutive lanes hit consecutive z addresses, so
 // the n contiguous mesh points of a stencil row share one cache line and one atomic request.
 // The meshes of the benchmark configurations (<= 8 MiB) are L2 / Infinity-Cache resident.
-#include "common.h"
+#include "host.h"
 
 namespace mipme {
 

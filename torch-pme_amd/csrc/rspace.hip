@@ -6,7 +6,7 @@
 // potentials/inversepowerlaw.py:55-106.  One pass over the pair stream: 2 indices + 1 distance per pair
 // are read once (coalesced, 16-byte index loads), charges are gathered from the L2-resident (N,C) table,
 // and contributions are added with hardware float atomics.
-#include "common.h"
+#include "host.h"
 #include "srpot.h"
 
 namespace mipme {
