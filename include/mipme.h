@@ -617,8 +617,10 @@ int64_t mipme_rows_partials_size(int64_t n_atoms);
  *                 shifts).  The shift is stored role-adjusted (S for role i, -S for role j).  shift_format 0: 3 x int8;
  *                 1: index into a 7^3 table of Cartesian shift vectors kept in LDS (needs |s| <= 3, no pair mask).
  *                 2: the table code and the partner in ONE int32 per entry, other | code << 22 (int32[2P]; atoms < 2^22,
- *                 |s| <= 3) -- half the entry stream; read by the co-scheduled pair sum of mipme_kspace_forward (sr_job) and
- *                 by mipme_frames_forward only, mipme_sr_rows_fused takes formats 0 and 1.
+ *                 |s| <= 3) -- half the entry stream; read by the co-scheduled pair sum of mipme_kspace_forward (sr_job), by
+ *                 mipme_frames_forward, and by mipme_sr_rows_fused in its potential + force-sum mode (out and force, src ==
+ *                 charges, no partials) for the range-separated 1/r and 1/r^6 potentials; mipme_sr_rows_fused refuses it in
+ *                 every other case; it takes formats 0 and 1 in every mode (with a pair mask: format 0).
  *                 flag[0] bit 0: some shift is not an integer in [-127,127] (unusable); bit 1: some |s| > 3 (formats 1, 2
  *                 unusable).
  *   out   (N) nullable: out[a] (+)= 1/2 sum_{potential roles} src[o] v_SR(d_e)          (transpose as mipme_rspace_rows)

@@ -95,6 +95,21 @@ def test_abi_argument_errors_without_gpu():
     assert lib.mipme_sr_rows_fused(None, _lib.F32, 4, None, None, None, None, None, None, None, None, None, 0, 0,
                                    C.byref(pd), 0, 0, None, 0, None, None, None, None, None) == -1
     assert b"mipme_sr_rows_fused" in lib.mipme_last_error()
+    # 4-byte entries (shift format 2) serve the potential + force pass of the 1/r and 1/r^6 fast paths only: another exponent is
+    # refused before any launch.  The "device" pointers below are one host buffer: the checks rely on every refusal coming before
+    # the first launch -- records_ready = 1 (nothing to pack) and the format / mode checks of sr_fused_rows_impl precede its kernels;
+    # a refusal that regressed would have to be caught here by its return code, never by running this call on a GPU with real work
+    buf = (C.c_double * 64)()
+    a = C.addressof(buf)
+    p3 = _lib.PotentialDesc(kind=_lib.INVERSE_POWER_LAW, exponent=3, smearing=1.0, prefactor=1.0, exclusion_radius=-1, exclusion_degree=1)
+    rows_fused = lambda pot, fmt, force: lib.mipme_sr_rows_fused(  # noqa: E731
+        None, _lib.F32, 4, a, a, a, None, a, a, a, a, None, 0, 0, C.byref(pot), 0, fmt, a, 1, a, force, None, None, None)
+    assert rows_fused(p3, 2, a) == -1
+    assert b"4-byte entries serve the potential + force pass of the Coulomb / dispersion fast paths only" in lib.mipme_last_error()
+    assert rows_fused(pd, 2, None) == -1  # the right potential, but potentials alone
+    assert b"4-byte entries serve the potential + force pass" in lib.mipme_last_error()
+    assert rows_fused(pd, 3, a) == -1
+    assert b"invalid shift format 3" in lib.mipme_last_error()
     assert C.sizeof(_lib.SrJob) == 104  # mipme_sr_job_t: int64 + 7 pointers + 2 x int32 + 4 pointers
     # mipme_frame_t: int64 + 3 pointers + mipme_mesh_t (6 x int32 + 19 doubles) + 5 pointers + 2 x int32 + 12 pointers
     assert C.sizeof(_lib.Frame) == 8 + 24 + C.sizeof(_lib.MeshDesc) + 40 + 8 + 96 and C.sizeof(_lib.MeshDesc) == 176

@@ -167,9 +167,12 @@ __device__ __forceinline__ double erfc_from_exp(double y, double e, const double
 }
 // exp(-x), x >= 0, in double: n = round(-x log2 e), r = -x - n ln 2 (two-step reduction), e^r from its degree-13 Taylor
 // polynomial (|r| <= ln 2 / 2: 2e-16), scaled by 2^n -- 18 instructions where libm's exp takes about twice as many (its range
-// checks and table look-ups are for arguments this one never sees)
+// checks and table look-ups are for arguments this one never sees).  x is clamped at kExpNegMax = 746, where exp(-x) < 2^-1075
+// rounds to zero: n stays an int for any x, and up to there ldexp underflows gradually like the function itself (a clamp at 700
+// returned e^-700 for every larger x: a factor e too much at x = 701 already -- y = 26.5, inside the 0 <= y <= 27 of the fit).
+static constexpr double kExpNegMax = 746.0;
 __device__ __forceinline__ double exp_neg_fast(double x) {
-  x = __builtin_fmin(x, 700.0);
+  x = __builtin_fmin(x, kExpNegMax);
   const double n = __builtin_rint(-x * 1.4426950408889634);
   double r = __builtin_fma(n, -0.693147180369123816490, -x);
   r = __builtin_fma(n, -1.90821492927058770002e-10, r);
@@ -222,7 +225,7 @@ __device__ __forceinline__ void exp_neg_table2(const double (&xin)[2], double (&
   int n[2];
 #pragma unroll
   for (int u = 0; u < 2; ++u) {
-    const double x = __builtin_fmin(xin[u], 700.0);
+    const double x = __builtin_fmin(xin[u], kExpNegMax);
     nf[u] = __builtin_rint(-x * 92.33248261689366);                 // 64 / ln2
     r[u] = __builtin_fma(nf[u], -0.01083042469326756, -x);          // ln2 / 64: 32 significant bits (n * hi is exact)
     r[u] = __builtin_fma(nf[u], -2.9815858269852933e-12, r[u]);     // ... and the rest
@@ -282,7 +285,7 @@ __device__ __forceinline__ void exp_neg_fast2(const double (&xin)[2], double (&o
   double n[2], r[2], p[2];
 #pragma unroll
   for (int u = 0; u < 2; ++u) {
-    const double x = __builtin_fmin(xin[u], 700.0);
+    const double x = __builtin_fmin(xin[u], kExpNegMax);
     n[u] = __builtin_rint(-x * 1.4426950408889634);
     r[u] = __builtin_fma(n[u], -0.693147180369123816490, -x);
     r[u] = __builtin_fma(n[u], -1.90821492927058770002e-10, r[u]);
@@ -449,7 +452,12 @@ __device__ __forceinline__ double rs_erfc(double y, double e, const double* c) {
 
 template <int P, bool DERIV, typename T>
 __device__ __forceinline__ void fast_rs_eval(T inv_2s2, T c1, T pref, T d2, T& v, T& dvd, const double* cheb) {
-  d2 = d2 < T(1e-30) ? T(1e-30) : d2;  // (NaN stays NaN)
+  // (NaN stays NaN.)  Coincident atoms: d^2 >= 1e-30 in double; in float 1e-24, so that pref / d^3 of the Coulomb derivative stays
+  // finite (1e36; with 1e-30 it is inf, and inf times the zero pair vector a NaN force).  Coulomb only: P = 6 in float has no such
+  // floor -- 1/d^6 leaves the format below d = 4e-7 -- and still gives inf and a NaN force at d = 0, as does sr_eval<float> for
+  // p >= 3 at its floor of 1e-15; in double every exponent stays finite (1e90 at most)
+  constexpr T d2_min = sizeof(T) == 4 ? T(1e-24) : T(1e-30);
+  d2 = d2 < d2_min ? d2_min : d2;
   const T inv = rs_rsqrt(d2);
   const T inv2 = inv * inv;
   const T x = d2 * inv_2s2;
