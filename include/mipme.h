@@ -727,6 +727,41 @@ int mipme_dipole_backward(void* stream, int dtype, int64_t n_atoms, int64_t n_k,
                           const void* s_cos, const void* s_sin, const void* t_cos, const void* t_sin,
                           void* grad_positions, void* grad_kvectors, void* partials);
 
+/* ---- tabulated potentials: SplinePotential, potentials/spline.py; CubicSpline / CubicSplineReciprocal, lib/splines.py:4-121 --
+ * Its own descriptor, like the dipoles: the fused kernels that take a mipme_potential_t do not know splines; a calculator with
+ * a spline potential is evaluated through the differentiable primitives above, and these three kernels are the spline itself.
+ * A plain spline is the natural cubic spline through n knots (x increasing), x / y / d2y FLOAT64 arrays ON THE DEVICE whatever
+ * `dtype` is; the interval of an argument v is searchsorted(x, v, right=True) - 1 clamped to [0, n-2], so the end cubics
+ * extrapolate on both sides.  A reciprocal-axis spline (reciprocal = 1) is  v < zero_x[1] ? Z(v) : R(1/v)  with R the plain
+ * spline of the table (knots in 1/v: 0, 1/x_N, ..., 1/x_1) and Z the 3-knot spline zero_x / zero_y / zero_d2y (host values)
+ * through (0, y_at_zero), (x_1, y_1), (x_2, y_2).  Every evaluation is in double precision; results are stored as `dtype`.
+ * A NaN argument gives NaN.  Tables of up to 2048 knots are staged in LDS (48 KB), longer ones are read from global memory.
+ *   mipme_spline_eval             out[i] = d^order/dv^order of the PLAIN spline of the table at x[i], order 0..3 (3: the constant
+ *                                 third derivative of the interval; `reciprocal` and the zero_* fields are not read)
+ *   mipme_spline_eval_reciprocal  out[i] = the reciprocal-axis spline at x[i], dout[i] (nullable) its first derivative
+ *                                 (-R'(1/v)/v^2 above the first knot): one read and one or two writes per argument
+ *   mipme_spline_kfilter_build    G(k) = prefactor * spline(|k|^2) on the rfft half grid (nx,ny,nz/2+1), for MIPME_P3M divided
+ *                                 by U^2(k) = prod_c sinc(k_c h_c/2)^(2 order) with G = 0 where U^2 = 0; k-vectors from the
+ *                                 index as in mipme_kfilter_build; k = 0 goes through the same evaluation (the value at zero
+ *                                 of the spline: yhat_at_zero of a reciprocal-axis one).  KSpaceFilter.update with a spline
+ *                                 kernel: lib/kspace_filter.py:97-120,293-329,349-361 */
+typedef struct {
+  const double* x;       /* knots: abscissas (device, float64, n values) */
+  const double* y;       /* ordinates */
+  const double* d2y;     /* second derivatives of the natural spline */
+  int32_t n;             /* number of knots, >= 2 */
+  int32_t reciprocal;    /* 0: plain spline; 1: reciprocal-axis spline */
+  double zero_x[3];      /* reciprocal = 1: the spline below the first knot */
+  double zero_y[3];
+  double zero_d2y[3];
+  double prefactor;      /* mipme_spline_kfilter_build only */
+} mipme_spline_t;
+int mipme_spline_eval(void* stream, int dtype, const mipme_spline_t* spline, int order, int64_t n_points, const void* x,
+                      void* out);
+int mipme_spline_eval_reciprocal(void* stream, int dtype, const mipme_spline_t* spline, int64_t n_points, const void* x,
+                                 void* out, void* dout);
+int mipme_spline_kfilter_build(void* stream, int dtype, const mipme_mesh_t* mesh, const mipme_spline_t* spline, void* G);
+
 /* ---- device neighbour list (the reference uses third-party vesin on the host,
  * tests/helpers.py:240-275, and hands a fresh list to every call, examples/02-neighbor-lists-usage.py:97-164) -------------
  * One cell-list traversal, two products:

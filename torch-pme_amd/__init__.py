@@ -13,7 +13,7 @@ from .dipoles import CalculatorDipole, PotentialDipole
 from .graphed import EnergyLog, GraphedEnergyForces, GraphedFrameBatch
 from .neighbors import NeighborStream, neighbor_list, neighbor_list_device
 from .ops import pair_distances, weighted_sum
-from .potentials import CoulombPotential, InversePowerLawPotential, Potential
+from .potentials import CoulombPotential, InversePowerLawPotential, Potential, SplinePotential
 from .tuning import tune_ewald, tune_p3m, tune_pme
 
 __version__ = "0.1.0"
@@ -28,6 +28,7 @@ __all__ = [
     "InversePowerLawPotential",
     "Potential",
     "PotentialDipole",
+    "SplinePotential",
     "pair_distances",
     "weighted_sum",
     "EnergyLog",

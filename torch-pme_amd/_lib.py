@@ -39,6 +39,7 @@ EXPORTS = (
     "mipme_spread_jet", "mipme_gather_jet", "mipme_gather_jet3", "mipme_pair_sum", "mipme_pair_sum_rows", "mipme_pair_dot", "mipme_pair_diff", "mipme_pair_scatter",
     "mipme_dipole_rspace_forward", "mipme_dipole_rspace_backward", "mipme_dipole_partials_size", "mipme_dipole_structure",
     "mipme_dipole_field", "mipme_dipole_backward",
+    "mipme_spline_eval", "mipme_spline_eval_reciprocal", "mipme_spline_kfilter_build",
 )
 
 
@@ -63,6 +64,23 @@ class DipoleDesc(C.Structure):
         ("exclusion_radius", C.c_double),
         ("exclusion_degree", C.c_int32),
         ("_pad", C.c_int32),
+    ]
+
+
+class SplineDesc(C.Structure):
+    """``mipme_spline_t``: float64 knot tables on the device (plain or reciprocal-axis spline) and the 3-knot spline below the
+    first knot of a reciprocal-axis one."""
+
+    _fields_ = [
+        ("x", C.c_void_p),
+        ("y", C.c_void_p),
+        ("d2y", C.c_void_p),
+        ("n", C.c_int32),
+        ("reciprocal", C.c_int32),
+        ("zero_x", C.c_double * 3),
+        ("zero_y", C.c_double * 3),
+        ("zero_d2y", C.c_double * 3),
+        ("prefactor", C.c_double),
     ]
 
 
@@ -287,6 +305,9 @@ def _declare(lib):
         "mipme_dipole_structure": [vp, ci, i64, i64] + [vp] * 7,
         "mipme_dipole_field": [vp, ci, i64, i64] + [vp] * 7,
         "mipme_dipole_backward": [vp, ci, i64, i64] + [vp] * 13,
+        "mipme_spline_eval": [vp, ci, C.POINTER(SplineDesc), ci, i64, vp, vp],
+        "mipme_spline_eval_reciprocal": [vp, ci, C.POINTER(SplineDesc), i64, vp, vp, vp],
+        "mipme_spline_kfilter_build": [vp, ci, MP, C.POINTER(SplineDesc), vp],
         "mipme_dot_forward": [vp, ci, i64, vp, vp, vp, vp],
         "mipme_dot_backward": [vp, ci, i64, vp, vp, vp, vp, vp],
         "mipme_energy_log_push": [vp, ci, ci, vp, vp, vp, ci],

@@ -421,18 +421,23 @@ def potentials(calculator, charges, cell, positions, neighbor_indices, neighbor_
         raise NotImplementedError('padded batches are not served by `double_backward = "analytic"`')
     dtype = charges.dtype
     pairs = neighbor_indices.contiguous()
+    from .potentials import SplinePotential, _PowerLawPotential, _reg_upper_gamma
+
+    # a spline potential with the zero short-range part of its class: no pair sum (the reference adds 0 * d per pair, which
+    # differs only for non-finite distances); a subclass that overrides sr_from_dist gets its sum
+    skip_pairs = isinstance(pot, SplinePotential) and pot.smearing is not None and pot._own_sr()
     # ---- real space: _compute_rspace (calculators/calculator.py:43-87)
     if pot.smearing is None:
         bare = pot.from_dist(neighbor_distances, pair_mask)
         if pot.exclusion_radius is not None:
             bare = bare * (1 - pot.f_cutoff(neighbor_distances, pair_mask))
-    elif pot.exclusion_radius is None:
+    elif skip_pairs:
+        bare = None
+    elif pot.exclusion_radius is None and isinstance(pot, _PowerLawPotential):
         # v_SR = (1 - P(p/2, x)) / d^p = Q(p/2, x) / d^p, x = d^2 / 2 sigma^2, in ONE piece: erfc(sqrt x) (+ a finite sum) for odd p,
         # e^-x times a finite sum for even p (potentials/coulomb.py:98-120, potentials/inversepowerlaw.py:72-107 form it as the
         # difference 1/d^p - P/d^p).  A handful of elementwise operations on the pair list instead of the incomplete-gamma
         # series' eighty -- autograd keeps a (P,) tensor for each -- and no cancellation at short distances.
-        from .potentials import _reg_upper_gamma
-
         sm, pref, p = pot._host_params()  # Python floats (one copy per parameter set): no device copy per call
         d = neighbor_distances
         bare = pref * _reg_upper_gamma(p, d * d * (0.5 / (sm * sm))) / (d if p == 1 else d**p)
@@ -440,7 +445,10 @@ def potentials(calculator, charges, cell, positions, neighbor_indices, neighbor_
             bare = bare * pair_mask
     else:
         bare = pot.sr_from_dist(neighbor_distances, pair_mask)
-    out = _PairSum.apply(bare.to(dtype), charges, pairs, 1 if calculator.full_neighbor_list else 0) / 2
+    if bare is None:
+        out = 0.0
+    else:
+        out = _PairSum.apply(bare.to(dtype), charges, pairs, 1 if calculator.full_neighbor_list else 0) / 2
     if pot.smearing is None:
         return out
     from .calculators import _reciprocal_and_det  # inv(cell).T and det from cross products: no host synchronisation
@@ -495,13 +503,43 @@ def _geometry(calculator, cell):
     return geom
 
 
+def _spline_filter(calculator, pot, cell, geom, dtype):
+    """G(k) of a spline potential for a cell that needs no gradient, from ``mipme_spline_kfilter_build``: cached on the
+    calculator per (cell tensor, version, tables of the potential, prefactor, mesh key, dtype), as ``_kspace_setup`` does."""
+    import weakref
+
+    from . import splines
+
+    krn = pot._splines()[1]
+    pref = pot._prefactor_float()
+    key = (id(pot), pot._tables_version, pref, calculator.mesh_spacing, calculator._scheme, calculator.interpolation_nodes,
+           dtype, cell.device)
+    c = calculator.__dict__.get("_spline_G")
+    if c is not None and c[0]() is cell and c[1] == cell._version and c[2] == key:
+        return c[3]
+    G = splines.build_filter(geom, krn, pref, dtype, cell.device)
+    try:
+        calculator.__dict__["_spline_G"] = (weakref.ref(cell), cell._version, key, G)
+    except TypeError:  # (a tensor subclass without weak references: no cache)
+        pass
+    return G
+
+
 def _mesh_kspace(calculator, charges, cell, positions, inv_cell) -> torch.Tensor:
     """``mesh_to_points(filter(points_to_mesh(charges)))`` (before the 1 / V): calculators/pme.py:88-113."""
     dtype = charges.dtype
     geom = _geometry(calculator, cell)
     ns = geom.ns
     u = _mesh_sizes(geom, dtype, positions.device) * (positions @ inv_cell)
-    G = filter_table(calculator, cell, ns, geom).to(dtype)
+    pot = calculator.potential
+    from .potentials import Potential, SplinePotential
+
+    own_kernel = (isinstance(pot, SplinePotential) and type(pot).lr_from_k_sq is SplinePotential.lr_from_k_sq
+                  and type(pot).kernel_from_k_sq is Potential.kernel_from_k_sq)
+    if own_kernel and not (cell.requires_grad and torch.is_grad_enabled()):
+        G = _spline_filter(calculator, pot, cell, geom, dtype)  # a constant of this cell: built by its own kernel, cached
+    else:  # (a spline potential: kernel_from_k_sq is the device node of splines.py, differentiable to any order in k^2)
+        G = filter_table(calculator, cell, ns, geom).to(dtype)
     zero = (0, 0, 0)
     rho = _Spread.apply(u, charges, geom, zero)
     phi = _Convolve.apply(rho, G, geom)

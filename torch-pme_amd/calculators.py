@@ -17,7 +17,7 @@ import torch
 
 from . import _front, _lib, ops
 from ._utils import _validate_parameters
-from .potentials import Potential
+from .potentials import Potential, SplinePotential
 
 import os
 
@@ -68,7 +68,8 @@ class Calculator(torch.nn.Module):
     #: per-instance device state that must not travel with a copy / pickle (FFT plans own raw device pointers, the caches
     #: hold weak references to the caller's tensors); rebuilt on first use
     _TRANSIENT = {"_cache": None, "_plan_store": dict, "_freq_cache": None, "_nan_flag": None, "_nan_shape": None,
-                  "_speculated": None, "_bet_flag": None, "_bet_flag_np": None, "_bet_skip": 0, "_bet_backoff": 2, "_analytic_geom": None}
+                  "_speculated": None, "_bet_flag": None, "_bet_flag_np": None, "_bet_skip": 0, "_bet_backoff": 2, "_analytic_geom": None,
+                  "_spline_G": None}
 
 
     def __getstate__(self):
@@ -142,6 +143,9 @@ class Calculator(torch.nn.Module):
         from . import library
 
         spec = self._spec()
+        if spec is None and isinstance(self.potential, SplinePotential):
+            raise TypeError(f"{type(self).__name__} with a SplinePotential ({type(self.potential).__name__}) has no dispatcher "
+                            "op and no scriptable stand-in: call the calculator eagerly")
         if spec is None:
             raise TypeError(f"{type(self).__name__} with a {type(self.potential).__name__} has no dispatcher op")
         return library.ScriptableCalculator(spec)
@@ -179,6 +183,8 @@ class Calculator(torch.nn.Module):
 
     @torch.compiler.disable
     def _eager_forward(self, *args):
+        if isinstance(self.potential, SplinePotential):
+            return self._spline_forward(*args)
         if ops.inside_vmap(*args):
             return ops.vmap_bridge(self._forward_impl, *args)
         if self.double_backward is not None and torch.is_grad_enabled() and any(
@@ -215,6 +221,24 @@ class Calculator(torch.nn.Module):
             if out is not None:
                 return out
         return self._forward_impl(*args)
+
+    def _spline_forward(self, charges, cell, positions, pairs, dist, *rest):
+        """A calculator whose potential is a :class:`SplinePotential`: the fused kernels do not know it, so every call --
+        whatever ``double_backward`` says -- goes through the differentiable primitives of :mod:`analytic`, with the spline
+        from ``csrc/spline.hip`` (pair values, G(k))."""
+        from . import analytic
+
+        if ops.inside_vmap(charges, cell, positions, pairs, dist, *rest):
+            raise NotImplementedError("a calculator with a SplinePotential is not served under torch.vmap: call it eagerly, "
+                                      "one structure at a time")
+        if getattr(pairs, "_mipme_stream", None) is not None:
+            raise TypeError("the handles of a NeighborStream serve the fused kernels, which do not know a SplinePotential: call "
+                            "the calculator eagerly with a list in the reference's format (`stream.pairs()`)")
+        dist = dist.materialize() if isinstance(dist, ops.LazyPairGradient) else dist
+        src = getattr(dist, "_mipme_src", None)
+        if src is not None and src.pending:
+            src.materialize()
+        return analytic.potentials(self, charges, cell, positions, pairs, dist, *rest)
 
     def _front_forward(self, charges, cell, positions, neighbor_indices, neighbor_distances):
         return None

@@ -17,6 +17,16 @@ import torch
 from . import _lib, ops
 
 
+
+def _refuse_spline(calculator, what: str):
+    """The captured steps run the fused kernels, which do not know a spline potential: say so before anything is launched."""
+    from .potentials import SplinePotential
+
+    if isinstance(getattr(calculator, "potential", None), SplinePotential):
+        raise TypeError(f"{what} runs the fused kernels, which do not serve a SplinePotential: call the calculator eagerly "
+                        "-- `calculator(charges, cell, positions, neighbor_indices, neighbor_distances)`")
+
+
 class _LiveStep:
     """Buffers and argument struct of ``mipme_md_rebin`` / ``mipme_md_step`` (include/mipme.h): the energy + forces step of an
     MD-like loop on device-resident neighbour structures.  The atoms live in ONE (N, 4) array of records (x, y, z, charge) that
@@ -211,6 +221,7 @@ class GraphedEnergyForces:
                  cell_gradient: bool = False, store_distances: bool = False, neighbors=None,
                  periodic=(True, True, True), live_bins: bool | None = None, charge_gradient: bool = False,
                  energy_log=None, epilogue=None):
+        _refuse_spline(calculator, "GraphedEnergyForces" + (" (`neighbors=` included)" if neighbors is not None else ""))
         self.calc = calculator
         self.energy_log = _as_energy_log(energy_log, 1, positions.device)
         self._epilogue = epilogue
@@ -515,6 +526,7 @@ class GraphedFrameBatch:
     """
 
     def __init__(self, calculator, frames, warmup: int = 2, store_distances: bool = False, energy_log=None, epilogue=None):
+        _refuse_spline(calculator, "GraphedFrameBatch")
         lib = _lib.load()
         self.calc = calculator
         self.store_distances = bool(store_distances)

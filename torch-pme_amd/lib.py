@@ -12,8 +12,9 @@ import ctypes as C
 
 import torch
 
-from . import _lib, ops
-from .potentials import Potential
+from . import _lib, ops, splines
+from .potentials import Potential, SplinePotential
+from .splines import CubicSpline, CubicSplineReciprocal, compute_second_derivatives, compute_spline_ft  # noqa: F401
 
 
 def get_ns_mesh(cell: torch.Tensor, mesh_spacing: float) -> torch.Tensor:
@@ -199,7 +200,10 @@ class KSpaceFilter:
         self._geom = ops.MeshGeometry(
             self.cell.detach().to("cpu", torch.float64).numpy(), self.ns_mesh, self._scheme, self._order
         )
-        if isinstance(self.kernel, Potential):
+        if isinstance(self.kernel, SplinePotential):  # G from the spline's own kernel (the fused ones do not know it)
+            self._kfilter = splines.build_filter(self._geom, self.kernel._splines()[1], self.kernel._prefactor_float(),
+                                                 self.cell.dtype, self.cell.device)
+        elif isinstance(self.kernel, Potential):
             self._kfilter = ops.build_filter(self._geom, self.kernel._descriptor(), self.cell.dtype, self.cell.device)
         else:  # a custom KSpaceKernel: tabulated with tensor operations, then the same convolution kernels
             k = generate_kvectors_for_mesh(self.cell.detach(), self.ns_mesh)

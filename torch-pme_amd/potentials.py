@@ -318,3 +318,155 @@ class CoulombPotential(_PowerLawPotential):
         prefactor: float = 1.0,
     ):
         super().__init__(smearing, exclusion_radius, exclusion_degree, prefactor)
+
+
+class SplinePotential(Potential):
+    r"""Potential given as tables: a cubic spline of the real-space function and one of its Fourier-space kernel (reference
+    ``potentials/spline.py:12-191``).  It is assumed to have a long-range part only -- ``sr_from_dist`` is zero; a subclass that
+    redefines it with tensor operations adds a short-range part -- and to vanish at infinite separation.
+
+    A calculator with a spline potential is evaluated through the differentiable primitives of :mod:`analytic` (spread,
+    convolution, gather, pair sum), with the spline itself from ``csrc/spline.hip``: differentiable to any order w.r.t. charges,
+    positions, cell and distances, at the cost of that route (a dozen launches, atomics in the spread) rather than that of the
+    fused kernels, which do not know splines (:meth:`_descriptor` raises; no graph capture, no dispatcher op).
+
+    Differences from the reference: the knot tables are float64 and the spline is evaluated in double precision, the result
+    having the dtype of the argument (the reference evaluates in the dtype of the grids and promotes to it); with the
+    ``sr_from_dist`` of this class the calculators skip the real-space pair sum instead of adding ``0 * d`` per pair, which
+    differs only for non-finite distances.  The knot tables (grids, second derivatives) are detached float64 host copies of
+    the buffers, made at construction and again after a buffer was written to: the spline is differentiable in its ARGUMENT
+    to any order, but no gradient flows to ``y_grid`` / ``yhat_grid`` (the reference builds its second derivatives with
+    tensor operations, so its tables can be learned in place; here a learned table is a new potential, or a
+    ``load_state_dict``, per update).  As in the reference, ``from_dist`` applies the prefactor twice
+    (``prefactor * (lr_from_dist + sr_from_dist)`` with ``lr_from_dist = prefactor * spline``).
+
+    :param r_grid: radial grid of the real-space function
+    :param y_grid: its values
+    :param k_grid: radial grid of the k-space kernel; by default ``2 pi / r_grid`` (flipped) for a reciprocal-axis spline and
+        ``r_grid`` otherwise
+    :param yhat_grid: values of the k-space kernel; by default the Fourier transform of the spline
+        (:func:`~splines.compute_spline_ft`)
+    :param reciprocal: spline on a 1/r axis, for long-range functions; ``r_grid`` must be strictly positive
+    :param y_at_zero: value for r -> 0 of a reciprocal-axis spline
+    :param yhat_at_zero: value of the kernel for k -> 0
+    :param smearing, exclusion_radius, exclusion_degree, prefactor: see :class:`Potential`
+    """
+
+    def __init__(
+        self,
+        r_grid: torch.Tensor,
+        y_grid: torch.Tensor,
+        k_grid: torch.Tensor | None = None,
+        yhat_grid: torch.Tensor | None = None,
+        reciprocal: bool | None = False,
+        y_at_zero: float | None = None,
+        yhat_at_zero: float | None = None,
+        smearing: float | None = None,
+        exclusion_radius: float | None = None,
+        exclusion_degree: int = 1,
+        prefactor: float = 1.0,
+    ):
+        super().__init__(smearing=smearing, exclusion_radius=exclusion_radius, exclusion_degree=exclusion_degree,
+                         prefactor=prefactor)
+        from . import splines
+
+        if len(y_grid) != len(r_grid):
+            raise ValueError("Length of radial grid and value array mismatch.")
+        self.register_buffer("r_grid", r_grid)
+        self.register_buffer("y_grid", y_grid)
+        self._reciprocal = bool(reciprocal)
+        if reciprocal and torch.min(r_grid) <= 0.0:
+            raise ValueError("Positive-valued radial grid is needed for reciprocal axis spline.")
+        if k_grid is None:
+            if reciprocal:
+                k_grid = torch.pi * 2 * torch.reciprocal(r_grid).flip(dims=[0])
+            else:
+                k_grid = r_grid.clone().detach()
+        self.register_buffer("k_grid", k_grid)
+        if yhat_grid is None:
+            yhat_grid = splines.compute_spline_ft(k_grid, r_grid, y_grid, splines.compute_second_derivatives(r_grid, y_grid))
+        self.register_buffer("yhat_grid", yhat_grid)
+        self._y_at_zero_arg = None if y_at_zero is None else float(y_at_zero)
+        self._yhat_at_zero_arg = None if yhat_at_zero is None else float(yhat_at_zero)
+        self._tables_version = 0
+        self._build_tables()
+
+    # ---- the splines: host tables from the buffers, device copies made on first use (splines._Table) --------------------------
+    def _buffers_key(self):
+        return tuple((b.data_ptr(), b._version) for b in (self.r_grid, self.y_grid, self.k_grid, self.yhat_grid))
+
+    def _build_tables(self):
+        from . import splines
+
+        d = self.__dict__
+        if self._reciprocal:
+            spline = splines.CubicSplineReciprocal(self.r_grid, self.y_grid, y_at_zero=self._y_at_zero_arg)
+            krn = splines.CubicSplineReciprocal(self.k_grid**2, self.yhat_grid, y_at_zero=self._yhat_at_zero_arg)
+        else:
+            spline = splines.CubicSpline(self.r_grid, self.y_grid)
+            krn = splines.CubicSpline(self.k_grid**2, self.yhat_grid)
+        # (plain attributes: the splines hold no parameters or buffers, and state dicts stay those of the reference)
+        d["_spline"], d["_krn_spline"] = spline, krn
+        zero = torch.zeros(1, dtype=torch.float64)
+        d["_y_at_zero"] = float(spline(zero)) if self._y_at_zero_arg is None else self._y_at_zero_arg
+        d["_yhat_at_zero"] = float(krn(zero)) if self._yhat_at_zero_arg is None else self._yhat_at_zero_arg
+        d["_tables_key"] = self._buffers_key()
+        d["_tables_version"] = self._tables_version + 1
+        d["_prefactor_cache"] = None
+
+    def _splines(self):
+        """(real-space spline, kernel spline), rebuilt when a buffer was written to (``load_state_dict``)."""
+        if self._tables_key != self._buffers_key():
+            self._build_tables()
+        return self._spline, self._krn_spline
+
+    def _apply(self, fn, *args, **kwargs):
+        # buffers written to since the tables were built (load_state_dict, then .to(device)): rebuild from them first, while
+        # they still have the dtype they were loaded in
+        if self.__dict__.get("_tables_key") is not None and self._tables_key != self._buffers_key():
+            self._build_tables()
+        out = super()._apply(fn, *args, **kwargs)
+        # the buffers moved (or changed dtype): the float64 host tables stay what they were built from, device copies of them
+        # are made on the device of the arguments (splines._Table.tensor)
+        self.__dict__["_tables_key"] = self._buffers_key()
+        self.__dict__["_prefactor_cache"] = None
+        return out
+
+    def _prefactor_float(self) -> float:
+        key = (self.prefactor.data_ptr(), self.prefactor._version)
+        c = self.__dict__.get("_prefactor_cache")
+        if c is None or c[0] != key:
+            c = self.__dict__["_prefactor_cache"] = (key, float(self.prefactor))
+        return c[1]
+
+    def _descriptor(self):
+        raise TypeError(
+            f"{self.__class__.__name__} (a SplinePotential) has no fused HIP kernel: the descriptor-based entry points "
+            "(graph capture, frame batches, live neighbour lists, the dispatcher op) do not serve it; call the calculator "
+            "eagerly -- `calculator(charges, cell, positions, neighbor_indices, neighbor_distances)` -- which evaluates it "
+            "through the differentiable primitives and `csrc/spline.hip`")
+
+    def _own_sr(self) -> bool:
+        """Whether ``sr_from_dist`` is this class's zero (the calculators then skip the pair sum)."""
+        return type(self).sr_from_dist is SplinePotential.sr_from_dist
+
+    # ---- reference method surface --------------------------------------------------------------------------------------------
+    def from_dist(self, dist: torch.Tensor, pair_mask: torch.Tensor | None = None) -> torch.Tensor:
+        """``prefactor * (lr_from_dist + sr_from_dist)``: the prefactor enters twice, as in the reference."""
+        return self.prefactor * (self.lr_from_dist(dist, pair_mask) + self.sr_from_dist(dist, pair_mask))
+
+    def sr_from_dist(self, dist: torch.Tensor, pair_mask: torch.Tensor | None = None) -> torch.Tensor:
+        return 0.0 * dist
+
+    def lr_from_dist(self, dist: torch.Tensor, pair_mask: torch.Tensor | None = None) -> torch.Tensor:
+        return self.prefactor.to(dist.device) * self._splines()[0](dist)
+
+    def lr_from_k_sq(self, k_sq: torch.Tensor) -> torch.Tensor:
+        return self.prefactor.to(k_sq.device) * self._splines()[1](k_sq)
+
+    def self_contribution(self) -> torch.Tensor:
+        self._splines()
+        return self.prefactor * self._y_at_zero
+
+    def background_correction(self) -> torch.Tensor:
+        return self.prefactor * torch.zeros(1, device=self.prefactor.device)
