@@ -762,6 +762,36 @@ int mipme_spline_eval_reciprocal(void* stream, int dtype, const mipme_spline_t* 
                                  void* out, void* dout);
 int mipme_spline_kfilter_build(void* stream, int dtype, const mipme_mesh_t* mesh, const mipme_spline_t* spline, void* G);
 
+/* ---- weighted sums of 1/r^p potentials: CombinedPotential, potentials/combined.py ---------------------------------------------
+ * Its own descriptor, like the dipoles and the splines: a combination is not a kind of mipme_potential_t, and the fused kernels
+ * take one potential.  A calculator with a combined potential is evaluated through the differentiable primitives above; these
+ * two kernels are the terms themselves.  Every term is a Coulomb / inverse-power-law descriptor, exponent 1..6, whose exclusion
+ * fields are not read; the terms are all range separated (smearing > 0) or all direct (smearing <= 0) -- term 0 decides, a
+ * term that differs is refused.  The weights are NOT part of the descriptor: they live on the device (a learnable parameter).
+ *   mipme_combined_sr_eval        the `order`-th derivative (0..MIPME_COMBINED_MAX_ORDER) w.r.t. d of every term's pair function
+ *                                 v_t = prefactor Q(p/2, x) / d^p, x = d^2 / 2 sigma^2 (range separated) or prefactor / d^p
+ *                                 (direct), one pass over d (n_points values of `dtype`, floored at 1e-15; NaN stays NaN):
+ *                                   v^(n) = (-1)^n prefactor d^-(p+n) [ R_n(x) A + (p)_n Q ],  A = 2 x^(p/2) e^-x / Gamma(p/2),
+ *                                   R_0 = 0, R_n+1 = (n + 2x) R_n - 2x R_n' + (p)_n   (direct: A = 0, Q = 1).
+ *                                 weights == NULL: out[t * n_points + i] = v_t^(n)(d_i); otherwise `weights` are n_terms device
+ *                                 values of `dtype` and out[i] = sum_t weights[t] v_t^(n)(d_i) (never read by the host).
+ *                                 coeff (nullable, HOST, n_terms * MIPME_COMBINED_MAX_ORDER doubles) receives the coefficients of
+ *                                 R_order per term, lowest power first, as the kernel gets them; with n_points = 0 nothing is
+ *                                 launched.
+ *   mipme_combined_kfilter_build  out[t][k] = G_t(k) on the rfft half grid, (n_terms, nx, ny, nz/2+1) of `dtype`: what
+ *                                 mipme_kfilter_build gives for term t alone, in one launch (k-vector and 1 / U^2 once per point).
+ *                                 Every term needs smearing > 0. */
+#define MIPME_COMBINED_MAX_TERMS 8
+#define MIPME_COMBINED_MAX_ORDER 6
+typedef struct {
+  int32_t n_terms;  /* 1..MIPME_COMBINED_MAX_TERMS */
+  int32_t reserved;
+  mipme_potential_t terms[8];
+} mipme_combined_t;
+int mipme_combined_sr_eval(void* stream, int dtype, const mipme_combined_t* comb, int order, double* coeff, int64_t n_points,
+                           const void* d, const void* weights, void* out);
+int mipme_combined_kfilter_build(void* stream, int dtype, const mipme_mesh_t* mesh, const mipme_combined_t* comb, void* out);
+
 /* ---- device neighbour list (the reference uses third-party vesin on the host,
  * tests/helpers.py:240-275, and hands a fresh list to every call, examples/02-neighbor-lists-usage.py:97-164) -------------
  * One cell-list traversal, two products:

@@ -13,7 +13,7 @@ from .dipoles import CalculatorDipole, PotentialDipole
 from .graphed import EnergyLog, GraphedEnergyForces, GraphedFrameBatch
 from .neighbors import NeighborStream, neighbor_list, neighbor_list_device
 from .ops import pair_distances, weighted_sum
-from .potentials import CoulombPotential, InversePowerLawPotential, Potential, SplinePotential
+from .potentials import CombinedPotential, CoulombPotential, InversePowerLawPotential, Potential, SplinePotential
 from .tuning import tune_ewald, tune_p3m, tune_pme
 
 __version__ = "0.1.0"
@@ -29,6 +29,7 @@ __all__ = [
     "Potential",
     "PotentialDipole",
     "SplinePotential",
+    "CombinedPotential",
     "pair_distances",
     "weighted_sum",
     "EnergyLog",

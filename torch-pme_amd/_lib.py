@@ -40,6 +40,7 @@ EXPORTS = (
     "mipme_dipole_rspace_forward", "mipme_dipole_rspace_backward", "mipme_dipole_partials_size", "mipme_dipole_structure",
     "mipme_dipole_field", "mipme_dipole_backward",
     "mipme_spline_eval", "mipme_spline_eval_reciprocal", "mipme_spline_kfilter_build",
+    "mipme_combined_sr_eval", "mipme_combined_kfilter_build",
 )
 
 
@@ -81,6 +82,20 @@ class SplineDesc(C.Structure):
         ("zero_y", C.c_double * 3),
         ("zero_d2y", C.c_double * 3),
         ("prefactor", C.c_double),
+    ]
+
+
+#: ``MIPME_COMBINED_MAX_TERMS`` / ``MIPME_COMBINED_MAX_ORDER`` of the header
+COMBINED_MAX_TERMS, COMBINED_MAX_ORDER = 8, 6
+
+
+class CombinedDesc(C.Structure):
+    """``mipme_combined_t``: the terms of a weighted sum of 1/r^p potentials (the weights stay on the device)."""
+
+    _fields_ = [
+        ("n_terms", C.c_int32),
+        ("reserved", C.c_int32),
+        ("terms", PotentialDesc * 8),
     ]
 
 
@@ -308,6 +323,8 @@ def _declare(lib):
         "mipme_spline_eval": [vp, ci, C.POINTER(SplineDesc), ci, i64, vp, vp],
         "mipme_spline_eval_reciprocal": [vp, ci, C.POINTER(SplineDesc), i64, vp, vp, vp],
         "mipme_spline_kfilter_build": [vp, ci, MP, C.POINTER(SplineDesc), vp],
+        "mipme_combined_sr_eval": [vp, ci, C.POINTER(CombinedDesc), ci, C.POINTER(dbl), i64, vp, vp, vp],
+        "mipme_combined_kfilter_build": [vp, ci, MP, C.POINTER(CombinedDesc), vp],
         "mipme_dot_forward": [vp, ci, i64, vp, vp, vp, vp],
         "mipme_dot_backward": [vp, ci, i64, vp, vp, vp, vp, vp],
         "mipme_energy_log_push": [vp, ci, ci, vp, vp, vp, ci],

@@ -426,8 +426,21 @@ def potentials(calculator, charges, cell, positions, neighbor_indices, neighbor_
     # a spline potential with the zero short-range part of its class: no pair sum (the reference adds 0 * d per pair, which
     # differs only for non-finite distances); a subclass that overrides sr_from_dist gets its sum
     skip_pairs = isinstance(pot, SplinePotential) and pot.smearing is not None and pot._own_sr()
+    # a combined potential whose members csrc/combined.hip serves: every member's pair function in one pass over the list (any
+    # other combination takes the branches below through its tensor methods, like an unknown Potential)
+    from . import combined
+
+    comb = combined.plan(pot)
     # ---- real space: _compute_rspace (calculators/calculator.py:43-87)
-    if pot.smearing is None:
+    if comb is not None:
+        # sum_t w_t v_t(d): from_dist of a direct combination, sr_from_dist of a range-separated one (whose own exclusion
+        # radius does not enter: its sr_from_dist is the members' sum, as in the reference)
+        bare = combined.pair_values(pot, comb, neighbor_distances)
+        if pair_mask is not None:
+            bare = bare * pair_mask
+        if pot.smearing is None and pot.exclusion_radius is not None:
+            bare = bare * (1 - pot.f_cutoff(neighbor_distances, pair_mask))
+    elif pot.smearing is None:
         bare = pot.from_dist(neighbor_distances, pair_mask)
         if pot.exclusion_radius is not None:
             bare = bare * (1 - pot.f_cutoff(neighbor_distances, pair_mask))
@@ -473,7 +486,12 @@ def potentials(calculator, charges, cell, positions, neighbor_indices, neighbor_
 
 def _ewald_kspace(pot, charges, positions, kvectors) -> torch.Tensor:
     """``sum_k G(k) [cos(k r_i) sum_j q_j cos(k r_j) + sin(k r_i) sum_j q_j sin(k r_j)]`` (before the 1 / V)."""
-    G = pot.lr_from_k_sq((kvectors * kvectors).sum(dim=-1)).to(charges.dtype)
+    from .potentials import CombinedPotential
+
+    k_sq = (kvectors * kvectors).sum(dim=-1)
+    if isinstance(pot, CombinedPotential):  # its kernel in float64, like the mesh filter's table (the single potentials: as ever)
+        k_sq = k_sq.to(torch.float64)
+    G = pot.lr_from_k_sq(k_sq).to(charges.dtype)
     n_k, n = kvectors.shape[0], positions.shape[0]
     step = max(1, (1 << 24) // max(1, n))
     acc = torch.zeros_like(charges)
@@ -525,6 +543,26 @@ def _spline_filter(calculator, pot, cell, geom, dtype):
     return G
 
 
+def _combined_tables(calculator, plan_, cell, geom, dtype):
+    """The members' filter tables G_t(k) of a combined potential for a cell that needs no gradient, from
+    ``mipme_combined_kfilter_build``: cached on the calculator per (cell tensor, version, member parameters, mesh key, dtype),
+    exactly as :func:`_spline_filter` does.  The weights are not part of the key: they are contracted with the tables per call."""
+    import weakref
+
+    from . import combined
+
+    key = (plan_.key, calculator.mesh_spacing, calculator._scheme, calculator.interpolation_nodes, dtype, cell.device)
+    c = calculator.__dict__.get("_combined_G")
+    if c is not None and c[0]() is cell and c[1] == cell._version and c[2] == key:
+        return c[3]
+    tables = combined.build_tables(geom, plan_, dtype, cell.device)
+    try:
+        calculator.__dict__["_combined_G"] = (weakref.ref(cell), cell._version, key, tables)
+    except TypeError:  # (a tensor subclass without weak references: no cache)
+        pass
+    return tables
+
+
 def _mesh_kspace(calculator, charges, cell, positions, inv_cell) -> torch.Tensor:
     """``mesh_to_points(filter(points_to_mesh(charges)))`` (before the 1 / V): calculators/pme.py:88-113."""
     dtype = charges.dtype
@@ -536,9 +574,17 @@ def _mesh_kspace(calculator, charges, cell, positions, inv_cell) -> torch.Tensor
 
     own_kernel = (isinstance(pot, SplinePotential) and type(pot).lr_from_k_sq is SplinePotential.lr_from_k_sq
                   and type(pot).kernel_from_k_sq is Potential.kernel_from_k_sq)
-    if own_kernel and not (cell.requires_grad and torch.is_grad_enabled()):
+    from . import combined
+
+    comb = combined.plan(pot)
+    if comb is not None and not (cell.requires_grad and torch.is_grad_enabled()):
+        # G = sum_t w_t G_t: the tables are constants of this cell (cached), the contraction carries the weight gradient
+        tables = _combined_tables(calculator, comb, cell, geom, dtype)
+        G = (pot.weights.to(dtype=dtype, device=tables.device).reshape(-1, 1, 1, 1) * tables).sum(dim=0)  # tensordot(w, tables)
+    elif own_kernel and not (cell.requires_grad and torch.is_grad_enabled()):
         G = _spline_filter(calculator, pot, cell, geom, dtype)  # a constant of this cell: built by its own kernel, cached
-    else:  # (a spline potential: kernel_from_k_sq is the device node of splines.py, differentiable to any order in k^2)
+    else:  # (a spline potential: kernel_from_k_sq is the device node of splines.py, differentiable to any order in k^2; a
+        # combined one: the weighted sum of the members' tensor lr_from_k_sq)
         G = filter_table(calculator, cell, ns, geom).to(dtype)
     zero = (0, 0, 0)
     rho = _Spread.apply(u, charges, geom, zero)

@@ -17,7 +17,7 @@ import torch
 
 from . import _front, _lib, ops
 from ._utils import _validate_parameters
-from .potentials import Potential, SplinePotential
+from .potentials import CombinedPotential, Potential, SplinePotential
 
 import os
 
@@ -69,7 +69,7 @@ class Calculator(torch.nn.Module):
     #: hold weak references to the caller's tensors); rebuilt on first use
     _TRANSIENT = {"_cache": None, "_plan_store": dict, "_freq_cache": None, "_nan_flag": None, "_nan_shape": None,
                   "_speculated": None, "_bet_flag": None, "_bet_flag_np": None, "_bet_skip": 0, "_bet_backoff": 2, "_analytic_geom": None,
-                  "_spline_G": None}
+                  "_spline_G": None, "_combined_G": None}
 
 
     def __getstate__(self):
@@ -143,6 +143,9 @@ class Calculator(torch.nn.Module):
         from . import library
 
         spec = self._spec()
+        if spec is None and isinstance(self.potential, CombinedPotential):
+            raise TypeError(f"{type(self).__name__} with a CombinedPotential ({type(self.potential).__name__}) has no dispatcher "
+                            "op and no scriptable stand-in: call the calculator eagerly")
         if spec is None and isinstance(self.potential, SplinePotential):
             raise TypeError(f"{type(self).__name__} with a SplinePotential ({type(self.potential).__name__}) has no dispatcher "
                             "op and no scriptable stand-in: call the calculator eagerly")
@@ -185,6 +188,8 @@ class Calculator(torch.nn.Module):
     def _eager_forward(self, *args):
         if isinstance(self.potential, SplinePotential):
             return self._spline_forward(*args)
+        if isinstance(self.potential, CombinedPotential):
+            return self._spline_forward(*args, kind="CombinedPotential")
         if ops.inside_vmap(*args):
             return ops.vmap_bridge(self._forward_impl, *args)
         if self.double_backward is not None and torch.is_grad_enabled() and any(
@@ -222,17 +227,18 @@ class Calculator(torch.nn.Module):
                 return out
         return self._forward_impl(*args)
 
-    def _spline_forward(self, charges, cell, positions, pairs, dist, *rest):
-        """A calculator whose potential is a :class:`SplinePotential`: the fused kernels do not know it, so every call --
-        whatever ``double_backward`` says -- goes through the differentiable primitives of :mod:`analytic`, with the spline
-        from ``csrc/spline.hip`` (pair values, G(k))."""
+    def _spline_forward(self, charges, cell, positions, pairs, dist, *rest, kind="SplinePotential"):
+        """A calculator whose potential is a :class:`SplinePotential` or a :class:`CombinedPotential` (``kind``: the name the
+        refusals give): the fused kernels do not know either, so every call -- whatever ``double_backward`` says -- goes through
+        the differentiable primitives of :mod:`analytic`, with the spline from ``csrc/spline.hip`` or the members of the
+        combination from ``csrc/combined.hip`` (pair values, G(k))."""
         from . import analytic
 
         if ops.inside_vmap(charges, cell, positions, pairs, dist, *rest):
-            raise NotImplementedError("a calculator with a SplinePotential is not served under torch.vmap: call it eagerly, "
+            raise NotImplementedError(f"a calculator with a {kind} is not served under torch.vmap: call it eagerly, "
                                       "one structure at a time")
         if getattr(pairs, "_mipme_stream", None) is not None:
-            raise TypeError("the handles of a NeighborStream serve the fused kernels, which do not know a SplinePotential: call "
+            raise TypeError(f"the handles of a NeighborStream serve the fused kernels, which do not know a {kind}: call "
                             "the calculator eagerly with a list in the reference's format (`stream.pairs()`)")
         dist = dist.materialize() if isinstance(dist, ops.LazyPairGradient) else dist
         src = getattr(dist, "_mipme_src", None)

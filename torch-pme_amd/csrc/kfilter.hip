@@ -58,12 +58,7 @@ __device__ inline void eval_point(const KGeom& g, const KPot& kp, int ix, int iy
   o.f[0] = fft_freq(ix, g.nx);
   o.f[1] = fft_freq(iy, g.ny);
   o.f[2] = iz;
-  double k2 = 0.0;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    o.k[c] = 2.0 * kPi * (o.f[0] * g.inv[3 * c + 0] + o.f[1] * g.inv[3 * c + 1] + o.f[2] * g.inv[3 * c + 2]);
-    k2 += o.k[c] * o.k[c];
-  }
+  const double k2 = kvector_dev(g.inv, o.f, o.k);
   double v, dv;
   lr_kernel_dev(kp, k2, v, dv);
   if (g.scheme == MIPME_LAGRANGE) {

@@ -19,12 +19,14 @@ from . import _lib, ops
 
 
 def _refuse_spline(calculator, what: str):
-    """The captured steps run the fused kernels, which do not know a spline potential: say so before anything is launched."""
-    from .potentials import SplinePotential
+    """The captured steps run the fused kernels, which know neither a spline potential nor a combined one: say so before
+    anything is launched."""
+    from .potentials import CombinedPotential, SplinePotential
 
-    if isinstance(getattr(calculator, "potential", None), SplinePotential):
-        raise TypeError(f"{what} runs the fused kernels, which do not serve a SplinePotential: call the calculator eagerly "
-                        "-- `calculator(charges, cell, positions, neighbor_indices, neighbor_distances)`")
+    for cls in (SplinePotential, CombinedPotential):
+        if isinstance(getattr(calculator, "potential", None), cls):
+            raise TypeError(f"{what} runs the fused kernels, which do not serve a {cls.__name__}: call the calculator eagerly "
+                            "-- `calculator(charges, cell, positions, neighbor_indices, neighbor_distances)`")
 
 
 class _LiveStep:

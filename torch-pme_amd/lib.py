@@ -12,8 +12,8 @@ import ctypes as C
 
 import torch
 
-from . import _lib, ops, splines
-from .potentials import Potential, SplinePotential
+from . import _lib, combined, ops, splines
+from .potentials import CombinedPotential, Potential, SplinePotential
 from .splines import CubicSpline, CubicSplineReciprocal, compute_second_derivatives, compute_spline_ft  # noqa: F401
 
 
@@ -169,7 +169,10 @@ class KSpaceFilter:
 
     Only the un-normalised convention used by the calculators (``fft_norm="backward"``,
     ``ifft_norm="forward"``) is implemented; ``kernel`` is a built-in :class:`Potential` (G built by the device kernel) or any
-    :class:`KSpaceKernel` (G tabulated from ``kernel_from_k_sq`` on :func:`generate_kvectors_for_mesh`)."""
+    :class:`KSpaceKernel` (G tabulated from ``kernel_from_k_sq`` on :func:`generate_kvectors_for_mesh`).
+
+    A :class:`CombinedPotential` kernel: G is the members' tables contracted with the weights as they are when the filter is
+    built or updated.  The filter does not follow later changes of the weights; call :meth:`update` after an optimizer step."""
 
     _scheme = _lib.LAGRANGE
     _order = 3
@@ -203,6 +206,21 @@ class KSpaceFilter:
         if isinstance(self.kernel, SplinePotential):  # G from the spline's own kernel (the fused ones do not know it)
             self._kfilter = splines.build_filter(self._geom, self.kernel._splines()[1], self.kernel._prefactor_float(),
                                                  self.cell.dtype, self.cell.device)
+        elif isinstance(self.kernel, CombinedPotential) and combined.plan(self.kernel) is not None:
+            # the members' tables from csrc/combined.hip, contracted with the weights as they are now
+            tables = combined.build_tables(self._geom, combined.plan(self.kernel), self.cell.dtype, self.cell.device)
+            self._kfilter = torch.tensordot(self.kernel.weights.detach().to(dtype=tables.dtype, device=tables.device), tables,
+                                            dims=1).contiguous()
+        elif isinstance(self.kernel, CombinedPotential):
+            # a combination the kernels do not serve (a spline member, a nested one, more than 8 terms ...): tabulated from the
+            # members' tensor lr_from_k_sq, as the calculators do -- correct, and slower
+            from types import SimpleNamespace
+
+            from . import analytic
+
+            shim = SimpleNamespace(potential=self.kernel, _scheme=self._scheme, interpolation_nodes=self._order)
+            with torch.no_grad():
+                self._kfilter = analytic.filter_table(shim, self.cell.detach(), self.ns_mesh).to(self.cell.dtype).contiguous()
         elif isinstance(self.kernel, Potential):
             self._kfilter = ops.build_filter(self._geom, self.kernel._descriptor(), self.cell.dtype, self.cell.device)
         else:  # a custom KSpaceKernel: tabulated with tensor operations, then the same convolution kernels

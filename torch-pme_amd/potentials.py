@@ -470,3 +470,97 @@ class SplinePotential(Potential):
 
     def background_correction(self) -> torch.Tensor:
         return self.prefactor * torch.zeros(1, device=self.prefactor.device)
+
+
+class CombinedPotential(Potential):
+    r"""Weighted sum :math:`\sum_t w_t v_t` of potentials, the weights fixed or learnable (reference
+    ``potentials/combined.py:6-124``): every method is the weighted sum of the members' methods; ``pbc_correction`` is the base
+    class's zero, as in the reference -- a combination has no slab term even with a Coulomb member.
+
+    A calculator with a combined potential is evaluated through the differentiable primitives of :mod:`analytic`, whatever its
+    ``double_backward`` says: differentiable to any order w.r.t. charges, positions, cell, distances and the weights, in ONE
+    mesh pass and ONE pair sum for all members.  Where every member is exactly a :class:`CoulombPotential` or an
+    :class:`InversePowerLawPotential` without an exclusion radius, and there are at most 8 of them, the members' pair functions
+    (to any derivative order up to 6) and filter tables come from ``csrc/combined.hip`` (see :mod:`combined`).  Any other
+    combination -- a :class:`SplinePotential` member, a nested combination, a member with an exclusion radius, a subclass,
+    more than 8 terms -- goes through the members' tensor methods, as any unknown :class:`Potential` does: correct, and slower.
+    The fused kernels take one potential and do not serve a combination (:meth:`_descriptor` raises; no graph capture, no
+    frame batches, no live neighbour lists, no dispatcher op).
+
+    Difference from the reference: the weights are cast to the dtype of the argument (the reference requires
+    ``weights.dtype`` to be the dtype of the computation: ``torch.inner`` raises otherwise).
+
+    :param potentials: the members; all range separated (``smearing`` set) or all direct
+    :param initial_weights: one weight per member; ones by default
+    :param learnable_weights: ``True``: ``weights`` is a ``Parameter``; ``False``: a buffer
+    :param smearing: must be given exactly when the members are range separated (its value only tells the calculators that
+        there is a long-range part)
+    :param exclusion_radius, exclusion_degree: see :class:`Potential`
+    """
+
+    def __init__(
+        self,
+        potentials: list[Potential],
+        initial_weights: torch.Tensor | None = None,
+        learnable_weights: bool | None = True,
+        smearing: float | None = None,
+        exclusion_radius: float | None = None,
+        exclusion_degree: int = 1,
+    ):
+        super().__init__(smearing=smearing, exclusion_radius=exclusion_radius, exclusion_degree=exclusion_degree)
+        smearings = [pot.smearing for pot in potentials]
+        if not all(smearings) and any(smearings):
+            raise ValueError(
+                r"Cannot combine direct (`smearing=None`) and range-separated (`smearing=float`) potentials."
+            )
+        if all(smearings) and not self.smearing:
+            raise ValueError(
+                r"You should specify a `smearing` when combining range-separated (`smearing=float`) potentials."
+            )
+        if not any(smearings) and self.smearing:
+            raise ValueError(
+                r"Cannot specify `smearing` when combining direct (`smearing=None`) potentials."
+            )
+        if initial_weights is not None:
+            if len(initial_weights) != len(potentials):
+                raise ValueError(
+                    "The number of initial weights must match the number of potentials being combined"
+                )
+        else:
+            initial_weights = torch.ones(len(potentials))
+        self.potentials = torch.nn.ModuleList(potentials)
+        if learnable_weights:
+            self.weights = torch.nn.Parameter(initial_weights)
+        else:
+            self.register_buffer("weights", initial_weights)
+
+    def _descriptor(self):
+        raise TypeError(
+            f"{self.__class__.__name__} (a CombinedPotential) has no fused HIP kernel: the descriptor-based entry points "
+            "(graph capture, frame batches, live neighbour lists, the dispatcher op) take one potential and do not serve a "
+            "combination; call the calculator eagerly -- `calculator(charges, cell, positions, neighbor_indices, "
+            "neighbor_distances)` -- which evaluates it through the differentiable primitives and `csrc/combined.hip`")
+
+    def _weighted(self, values: list) -> torch.Tensor:
+        stacked = torch.stack(values, dim=-1)
+        return torch.inner(self.weights.to(dtype=stacked.dtype, device=stacked.device), stacked)
+
+    # ---- reference method surface --------------------------------------------------------------------------------------------
+    def from_dist(self, dist: torch.Tensor, pair_mask: torch.Tensor | None = None) -> torch.Tensor:
+        return self._weighted([pot.from_dist(dist, pair_mask) for pot in self.potentials])
+
+    def sr_from_dist(self, dist: torch.Tensor, pair_mask: torch.Tensor | None = None) -> torch.Tensor:
+        return self._weighted([pot.sr_from_dist(dist, pair_mask) for pot in self.potentials])
+
+    def lr_from_dist(self, dist: torch.Tensor, pair_mask: torch.Tensor | None = None) -> torch.Tensor:
+        return self._weighted([pot.lr_from_dist(dist, pair_mask) for pot in self.potentials])
+
+    def lr_from_k_sq(self, k_sq: torch.Tensor) -> torch.Tensor:
+        return self._weighted([pot.lr_from_k_sq(k_sq) for pot in self.potentials])
+
+    def self_contribution(self) -> torch.Tensor:
+        # (scalars of shape () or (1,), depending on the member's class: stacked as scalars)
+        return self._weighted([pot.self_contribution().reshape(()) for pot in self.potentials])
+
+    def background_correction(self) -> torch.Tensor:
+        return self._weighted([pot.background_correction().reshape(()) for pot in self.potentials])
