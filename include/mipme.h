@@ -417,6 +417,13 @@ int64_t mipme_atom_bins_bytes(const mipme_mesh_t* mesh, int64_t n_atoms, int dty
  * "live_spread_rows_kernel", "frames_plane_rows_kernel", "frames_spread_rows_kernel"; "" before the first one.  What ran, as
  * opposed to mipme_plane_spread_parts (what the geometry allows): a benchmark labels its dominant launch with this. */
 const char* mipme_last_cosched_kernel(void);
+/* How the last mipme_kspace_forward of the calling thread filled the gather's brick slots (record, weights, charge, reach code of
+ * every atom): 0 = the binning pass did, in one pass; B > 0 = the binning pass ran lean and rider workgroups on the
+ * convolution's inverse (y,z) plane launch did, B atoms each, ceil(n_atoms / B) of them (MIPME_DEFER_SLOTS, docs/SWITCHES.md).  What ran --
+ * or was captured into a graph --, so that a test can assert the route it means to test. */
+int mipme_last_slot_fill(void);
+/* Cell-gradient rider workgroups on that same launch (0: none, or no deferred slot fill in the last forward call). */
+int mipme_last_cell_riders(void);
 /* Workgroups per x plane of the PLANE SPREAD that mipme_kspace_forward uses for this mesh / system when the caller sets
  * MIPME_FWD_RHO_MESH_UNUSED and rho_hat == NULL (0: the owner-computes bricks + the forward plane launch): single channel,
  * power-of-two nx, ny, nz, planes whose accumulation tile fits a workgroup's LDS, dense bricks, not MIPME_DETERMINISTIC.  For

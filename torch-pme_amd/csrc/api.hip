@@ -16,6 +16,10 @@ static thread_local char g_error[512] = "";
 
 static thread_local const char* g_last_cosched = "";
 void note_cosched_kernel(const char* name) { g_last_cosched = name ? name : ""; }
+static thread_local int g_last_slot_fill = 0;
+void note_slot_fill(int rider_atoms) { g_last_slot_fill = rider_atoms; }
+static thread_local int g_last_cell_riders = 0;
+void note_cell_riders(int n) { g_last_cell_riders = n; }
 void set_error(const char* fmt, ...) {
   va_list ap;
   va_start(ap, fmt);
@@ -125,6 +129,9 @@ static int kspace_forward_t(const mipme_kspace_forward_args_t& a, const GatherTa
   double self_c, bg_c;
   correction_terms(a.pot, self_c, bg_c);
   fft_plan_begin_step(plan);  // (the plane spread's "forward planes done" is set below and consumed by convolve_xfused)
+  note_slot_fill(0);
+  note_cell_riders(0);
+  SlotRider slots;  // deferred slot fill (n_atoms > 0): the riders of the convolution's inverse (y,z) plane launch
   // the plan's brick counters are zero here; the binning pass fills them and the gather -- the last consumer -- zeroes them
   // again (no memset launch per call).  If anything in between fails they are cleared explicitly, so that a failed call does
   // not poison the next one.
@@ -144,18 +151,27 @@ static int kspace_forward_t(const mipme_kspace_forward_args_t& a, const GatherTa
     // fused convolution ahead and planes that fit a workgroup: the spread will write the forward (y,z) transform itself, from
     // the plane lists the binning pass leaves (bricks.hip plane_spread_yz_body)
     const bool want_planes = !a.rho_hat && (a.flags & MIPME_FWD_RHO_MESH_UNUSED) != 0 && fft_plan_plane_forward_ok(plan);
-    STAGE(st, "bin_atoms", bins_build<T>(st, m, N, a.positions, bins, counters, a.charges, a.out_records, want_planes));
+    const bool co = job && sr_job_fusable(job);
+    PlaneHost ph;
+    ph.slot_values = m->n_channels == 1;  // (bins_build below is handed these very charges)
+    if (want_planes) {
+      ph.hat = a.hat_work;
+      ph.keep_mesh = false;
+    }
+    // Route of the slot fill, decided ONCE, before the binning launch: deferred to riders of the inverse (y,z) plane launch iff
+    // the plane spread will run (the same predicate spread_bricks uses), the fused convolution with our own single-launch inverse
+    // planes follows (want_planes: !rho_hat and fft_plan_plane_forward_ok -- the launch with the rider hook) and then a gather
+    // (always, with bins).  The riders sit behind that launch's skip flag, which is clear on forward calls (mipme_set_skip_flag
+    // is for backward passes): a thread that has it set keeps the one-pass kernel.
+    const bool defer = want_planes && skip_flag_slot() == nullptr && bins_defer_slots(m, N, dtype_of<T>(), co ? job : nullptr, &ph);
+    STAGE(st, "bin_atoms", bins_build<T>(st, m, N, a.positions, bins, counters, a.charges, a.out_records, want_planes, defer));
+    if (defer) slots = bins_slot_rider(m, N, dtype_of<T>(), bins, a.positions, a.charges);
     {
-      const bool co = job && sr_job_fusable(job);
       const int reps = (g_prof_on && co) ? kProfRepeat : 1;
       ProfScope _ps(st, co ? "spread+rspace_forward" : "spread", reps);
       // fused convolution ahead and planes that fit a workgroup: the spread writes the forward (y,z) transform itself
-      PlaneHost ph;
       bool planes = false;
-      ph.slot_values = m->n_channels == 1;  // (bins_build above was handed these very charges)
       if (want_planes) {
-        ph.hat = a.hat_work;
-        ph.keep_mesh = false;
         // MIPME_PLANE_PARTS workgroups per plane (default 2, at most 8; measured 1 / 2 / 3 / 4 / 8: profiles/r05_experiments.txt): a plane's LDS atomics are what its workgroup waits for,
         // and they go through ONE CU's LDS pipe
         ph.parts = plane_spread_parts_setting();
@@ -168,6 +184,8 @@ static int kspace_forward_t(const mipme_kspace_forward_args_t& a, const GatherTa
       for (int r = 0; r < reps; ++r)
         if ((rc = spread_bricks<T>(st, m, N, bins, a.charges, 1.0, a.rho_mesh, counters, co ? job : nullptr, tail != nullptr,
                                    a.out_grad_cell ? cw.cwave : nullptr, &ph, &planes))) return rc;
+      // (the owner-computes brick spread reads the slots' weights and reach codes: nobody has written them yet)
+      MIPME_REQUIRE(!defer || planes, "the binning pass left the slot fill to riders but the plane spread did not run");
       fft_plan_set_forward_done(plan, planes, planes ? ph.parts_used : 1);
       fft_plan_set_forward_ycols(plan, planes && ph.ycols_pending);
     }
@@ -187,10 +205,11 @@ static int kspace_forward_t(const mipme_kspace_forward_args_t& a, const GatherTa
     ConvCell cc{};
     if (a.out_grad_cell) cc = ConvCell{a.G_deriv, cw.cwave, cw.n_waves, cw.wbuf, cw.rows, int(cw.n_riders), nullptr, nullptr, nullptr, nullptr};
     cc.rho_hat_out = a.out_rho_hat;
+    if (slots.n_atoms > 0) cc.slots = &slots;
     STAGE(st, "convolve_xfused", convolve_xfused(plan, st, a.rho_mesh, a.G, a.hat_work, a.phi_mesh, a.dc, 0, m, a.pot,
                                                  a.out_cell_partials, tail ? const_cast<void*>(tail->epart_k) : nullptr, sr_part,
                                                  n_sr_part, nullptr, a.nan_flag,
-                                                 (a.out_grad_cell || a.out_rho_hat) ? &cc : nullptr));
+                                                 (a.out_grad_cell || a.out_rho_hat || cc.slots) ? &cc : nullptr));
   } else {
     STAGE(st, "fft_r2c", fft_forward(plan, st, a.rho_mesh, a.rho_hat));
     STAGE(st, "apply_filter", apply_filter_impl<T>(st, Mh, m->n_channels, a.rho_hat, a.G, a.hat_work, a.dc));
@@ -953,6 +972,8 @@ extern "C" {
 
 const char* mipme_last_error(void) { return g_error; }
 const char* mipme_last_cosched_kernel(void) { return g_last_cosched; }
+int mipme_last_slot_fill(void) { return g_last_slot_fill; }
+int mipme_last_cell_riders(void) { return g_last_cell_riders; }
 int mipme_version(void) { return MIPME_VERSION; }
 
 int mipme_fft_plan_create(int dtype, int nx, int ny, int nz, int batch, mipme_fft_plan** out) {

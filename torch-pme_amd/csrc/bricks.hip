@@ -44,11 +44,54 @@ const void* bins_epart(const mipme_mesh_t* m, int64_t N, int dtype, void* bins, 
   return bins_view(m, N, dtype, bins).epart;
 }
 
+// Will spread_bricks spread this call's charges by planes?  The ONE predicate of spread_bricks and of the route decision in front
+// of the binning pass (bins_defer_slots).  forward: a forward spread that reports back (clear_count and used_planes given).
+bool plane_spread_runs(const mipme_mesh_t* m, int64_t N, int dtype, const mipme_sr_job_t* job, const PlaneHost* ph, bool forward) {
+  const int pcap = plane_list_capacity(m, N, dtype);  // (0 also for: several channels, sparse bricks, deterministic mode, N == 0)
+  const int band_rows = pcap > 0 ? plane_band_rows(m, dtype) : 0;
+  // whole planes, or bands of rows for planes whose tile does not fit the launch's LDS (PlaneArgs::band_rows); the banded
+  // co-scheduled kernels exist for 4-byte pair entries only (what every caller of this package uses): others keep the bricks
+  const bool bands_ok = band_rows == m->ny || !job || (job->shift_format & kShiftFormatMask) == kShiftTable32;
+  return ph && ph->hat && ph->slot_values && !ph->keep_mesh && forward && pcap > 0 && m->n_channels == 1 &&
+         !sparse_bricks(N, make_brick_geom(m).nb) && !deterministic_mode() && N > 0 && band_rows > 0 && bands_ok;
+}
+
+// MIPME_DEFER_SLOTS (default 1; 0: the one-pass binning kernel everywhere; read once per process)
+static bool defer_slots_setting() {
+  static const bool on = env_flag("MIPME_DEFER_SLOTS", true);
+  return on;
+}
+// Deferred slot fill for this call's bins?  Only where the plane spread follows (the owner-computes brick spread reads the slots'
+// weights and reach codes in the very next launch) and below the size from which the binning pass is bound by its stores rather
+// than by latency.  The caller adds what it knows: a fused convolution with single-launch inverse planes, a gather behind it.
+bool bins_defer_slots(const mipme_mesh_t* m, int64_t N, int dtype, const mipme_sr_job_t* job, const PlaneHost* ph) {
+  return defer_slots_setting() && N < kCoalescedBinAtoms && plane_spread_runs(m, N, dtype, job, ph, true);
+}
+// the slot riders of a call whose binning pass ran lean (defer_slots)
+SlotRider bins_slot_rider(const mipme_mesh_t* m, int64_t N, int dtype, void* bins, const void* pos, const void* q) {
+  const BinsView v = bins_view(m, N, dtype, bins);
+  SlotRider r;
+  r.n_atoms = N;
+  r.scheme = m->scheme;
+  r.order = m->order;
+  r.g = make_geom(m);
+  r.pos = pos;
+  r.q = q;
+  r.dst = v.dst;
+  r.rec = v.rec;
+  r.wts = v.wts;
+  r.qs = v.qs;
+  r.codes = v.idx.codes;
+  r.over_base = v.idx.over_base;
+  return r;
+}
+
 // live: the int[nb + 1] counters of the binning pass, ZERO on entry (plan / frame owned); the forward gather zeroes them
 // again.  q + atom_rec (nullable, single channel): also emit the (position, charge) records.  One launch.
+// defer_slots (bins_defer_slots): the lean pass -- the gather's slot data is left to the slot riders (bins_slot_rider).
 template <typename T>
 int bins_build(hipStream_t st, const mipme_mesh_t* m, int64_t n_atoms, const void* pos, void* bins, int* live,
-               const void* q, void* atom_rec, bool plane_lists) {
+               const void* q, void* atom_rec, bool plane_lists, bool defer_slots) {
   const int dtype = dtype_of<T>();
   const Geom g = make_geom(m);
   const BrickGeom bg = make_brick_geom(m);
@@ -85,8 +128,17 @@ int bins_build(hipStream_t st, const mipme_mesh_t* m, int64_t n_atoms, const voi
     MIPME_LAUNCH_CHECK();
     slot_of = slots;
   }
-  T* qs = (q && m->n_channels == 1) ? (T*)v.qs : nullptr;  // the plane spread reads the charge by slot
-  if (n_atoms > 0) {
+  T* qs = (q && m->n_channels == 1) ? (T*)v.qs : nullptr;  // the charge by slot (read by the brick spread's scan; the lean pass only
+                                                           // takes the pointer as its sign that the charges are single-channel)
+  if (defer_slots) {
+    MIPME_REQUIRE(v.idx.plive && qs && !slot_of && n_atoms > 0 && n_atoms < kCoalescedBinAtoms,
+                  "the lean binning pass needs plane lists, single-channel charges and fewer than %lld atoms",
+                  (long long)kCoalescedBinAtoms);
+    MIPME_DISPATCH_STENCIL_B(m->scheme, m->order,
+                             (bin_atoms_lean_kernel<S, N, T><<<blocks, 256, 0, st>>>(g, bg, v.idx, n_atoms, (const T*)pos, v.over_brick,
+                                                                                    (const T*)q, (AtomRecord<T>*)atom_rec, qs, v.dst)));
+    MIPME_LAUNCH_CHECK();
+  } else if (n_atoms > 0) {
     if (n_atoms >= kCoalescedBinAtoms)
       MIPME_DISPATCH_STENCIL_B(m->scheme, m->order,
                                (bin_atoms_kernel<S, N, T, true><<<blocks, 256, 0, st>>>(g, bg, v.idx, n_atoms, (const T*)pos, v.over_brick,
@@ -136,14 +188,9 @@ int spread_bricks(hipStream_t st, const mipme_mesh_t* m, int64_t N, void* bins, 
   PlaneArgs<T> pa;
   size_t plane_lds = 0;
   if (used_planes) *used_planes = false;
-  // whole planes, or bands of rows for planes whose tile does not fit the launch's LDS (PlaneArgs::band_rows); the banded
-  // co-scheduled kernels exist for 4-byte pair entries only (what every caller of this package uses): others keep the bricks
-  const int band_rows = v.idx.pcap > 0 ? plane_band_rows(m, dtype) : 0;
-  const bool bands_ok = band_rows == m->ny || !job || (job->shift_format & kShiftFormatMask) == kShiftTable32;
-  if (ph && ph->hat && ph->slot_values && !ph->keep_mesh && used_planes && clear_count && v.idx.pcap > 0 && sa.C == 1 && !sparse &&
-      !sa.det && N > 0 && band_rows > 0 && bands_ok) {
+  if (plane_spread_runs(m, N, dtype, job, ph, used_planes && clear_count)) {
     size_t need = 0;
-    pa.band_rows = band_rows;
+    pa.band_rows = plane_band_rows(m, dtype);
     pa.bands = m->ny / pa.band_rows;
     plane_lds_layout<T>(pa.band_rows, m->nz, pa, need, pa.bands == 1);
     pa.hat = (Cplx<T>*)ph->hat;
@@ -157,7 +204,7 @@ int spread_bricks(hipStream_t st, const mipme_mesh_t* m, int64_t N, void* bins, 
     // (the row blocks of a co-scheduled launch keep their shift / erfcx tables in the same dynamic region)
     const size_t rows_lds = job ? sizeof(T) * size_t(SPREAD_WAVES) * BRICK_PTS : 0;
     plane_lds = need > rows_lds ? need : rows_lds;
-    sa.qs = (const T*)v.qs;
+    sa.qs = (const T*)v.qs;  // (not read by the plane bodies: they stream plane-list entries; deferred slot fill: not written yet)
     sa.bins.plive = clear_count + bg.nb + 1;
     *used_planes = true;
   }
@@ -389,8 +436,8 @@ int gather_grad_bricks(hipStream_t st, const mipme_mesh_t* m, int64_t N, void* b
   return MIPME_OK;
 }
 
-template int bins_build<float>(hipStream_t, const mipme_mesh_t*, int64_t, const void*, void*, int*, const void*, void*, bool);
-template int bins_build<double>(hipStream_t, const mipme_mesh_t*, int64_t, const void*, void*, int*, const void*, void*, bool);
+template int bins_build<float>(hipStream_t, const mipme_mesh_t*, int64_t, const void*, void*, int*, const void*, void*, bool, bool);
+template int bins_build<double>(hipStream_t, const mipme_mesh_t*, int64_t, const void*, void*, int*, const void*, void*, bool, bool);
 template int spread_bricks<float>(hipStream_t, const mipme_mesh_t*, int64_t, void*, const void*, double, void*, int*,
                                   const mipme_sr_job_t*, bool, double*, const PlaneHost*, bool*);
 template int spread_bricks<double>(hipStream_t, const mipme_mesh_t*, int64_t, void*, const void*, double, void*, int*,

@@ -78,7 +78,7 @@ __device__ __forceinline__ int wrap1(int a, int n) {
 // nx = 64 counters were ~16 per address and +1.5 us on the pass; on 512 counters they are 2 per address, like the bricks'.
 // (kPlaneSub = 8: common.h, next to plan_counter_words)
 struct BinsLayout {
-  size_t snap, over_brick, rec, wts, codes, qs, plist, pover, wmax, epart, det, det_sort_bytes, total;
+  size_t snap, over_brick, rec, wts, codes, qs, plist, pover, wmax, epart, dst, det, det_sort_bytes, total;
   int cap;
   int pcap;  // entries per plane SUB-list (0: no plane lists for this mesh, see plane_list_capacity)
   int64_t slots;  // nb * cap + N
@@ -174,7 +174,7 @@ static inline BinsLayout bins_layout(const mipme_mesh_t* m, int64_t N, int dtype
   l.rec = off;        off += al(sizeof(int4) * size_t(l.slots));
   l.wts = off;        off += al(wts_stride_rt(m->order, s) * s * size_t(l.slots));  // per slot: see wts_stride
   l.codes = off;      off += al(size_t(l.slots));  // per slot: which neighbouring bricks the atom's stencil reaches (reach_code)
-  l.qs = off;         off += al(s * size_t(l.slots));  // per slot: the atom's charge (single channel), for the plane spread
+  l.qs = off;         off += al(s * size_t(l.slots));  // per slot: the atom's charge (single channel), for the brick spread's scan
   // plane lists (plane spread): the slots of the atoms whose stencil reference point m_x is plane p, pcap per plane, and an
   // overflow list (slots of atoms whose plane list was full: normally empty) that every plane also walks
   l.pcap = plane_list_capacity(m, N, dtype);
@@ -185,6 +185,8 @@ static inline BinsLayout bins_layout(const mipme_mesh_t* m, int64_t N, int dtype
   l.wmax = off;       off += al(sizeof(float) * size_t(l.pcap ? (N + 63) / 64 : 0));
   // energy partial sums of the co-scheduled pair sum: 2 doubles per wave of its row workgroups (FusedRowsArgs::epart)
   l.epart = off; off += al(2 * sizeof(double) * kSpreadWaves * (((size_t(N) + kRowsPerSpreadBlock - 1) / kRowsPerSpreadBlock + 1) & ~size_t(1)));
+  // deferred slot fill (bin_atoms_body<LEAN> / slot_rider_body): the destination slot of every atom
+  l.dst = off;        off += al(sizeof(int) * size_t(N));
   l.det = off;
   l.det_sort_bytes = 0;
   if (deterministic_mode()) {  // keys, vals, keys2, vals2, slot_of, over_flag (N words each) + the sort's scratch
@@ -274,12 +276,18 @@ __device__ __forceinline__ void atom_mesh_coords(const Geom& g, bool even, const
 // particle<->mesh kernels of a step only load them -- straight into its slot, and (atom_rec) the (position, charge) record
 // of the fused pair kernels while the position is in registers anyway.
 static constexpr int64_t kCoalescedBinAtoms = 100000;  // atoms from which the binning pass stages its weight rows (see below)
-template <int SCHEME, int N, typename T, bool COALESCE = false>
+// LEAN (deferred slot fill, see slot_rider_body): everything the NEXT launch reads -- counters, overflow bookkeeping, wmax, atom
+// record, plane-list entry (x weights only, no derivatives) -- and the atom's destination slot in slot_dst[i]; the slot's record,
+// weights, charge and reach code are left to the slot riders of the inverse (y,z) plane launch.  qs is passed (it gates wmax) but
+// not written.
+template <int SCHEME, int N, typename T, bool COALESCE = false, bool LEAN = false>
 __device__ __forceinline__ void bin_atoms_body(const Geom& g, const BrickGeom& bg, const BinIndex& bi, int64_t Natoms,
                                                const T* __restrict__ pos, int* __restrict__ over_brick,
                                                int4* __restrict__ rec, T* __restrict__ wts, const T* __restrict__ q,
                                                AtomRecord<T>* __restrict__ atom_rec, unsigned block,
-                                               const int* __restrict__ slot_of = nullptr, T* __restrict__ qs = nullptr) {
+                                               const int* __restrict__ slot_of = nullptr, T* __restrict__ qs = nullptr,
+                                               int* __restrict__ slot_dst = nullptr) {
+  static_assert(!(LEAN && COALESCE), "the lean binning pass has no weight rows to stage");
   const int64_t i = int64_t(block) * blockDim.x + threadIdx.x;
   const bool valid = i < Natoms;
   const int lane = threadIdx.x & 63;
@@ -366,9 +374,13 @@ __device__ __forceinline__ void bin_atoms_body(const Geom& g, const BrickGeom& b
       r.w = q[i];
       atom_rec[i] = r;
     }
-    rec[dst] = make_int4(m[0], m[1], m[2], int(i));
-    if (qs) qs[dst] = q[i];
-    if (bi.codes && dst < bi.over_base) bi.codes[dst] = (unsigned char)reach_code<N>(m, g.nx, g.ny, g.nz);
+    if constexpr (LEAN) {
+      slot_dst[i] = int(dst);
+    } else {
+      rec[dst] = make_int4(m[0], m[1], m[2], int(i));
+      if (qs) qs[dst] = q[i];
+      if (bi.codes && dst < bi.over_base) bi.codes[dst] = (unsigned char)reach_code<N>(m, g.nx, g.ny, g.nz);
+    }
   }
   // The 6N weights of an atom go to its slot, anywhere in the bins: written by the atom's own lane that is 6N four-byte stores
   // to 64 different cache lines per instruction.  Transposed through LDS instead: the wave stages its rows, then lane k of a
@@ -439,6 +451,11 @@ __device__ __forceinline__ void bin_atoms_body(const Geom& g, const BrickGeom& b
       const int64_t dj = __shfl(dst, j < 64 ? j : 0, 64);
       if (sub < PER && k < 6 * N && j < 64 && ((vmask >> j) & 1ull)) wts[dj * W + k] = rows[j * W + k];
     }
+  } else if constexpr (LEAN) {
+    if (!valid) return;
+    T wx[N], dwx[N];
+    weights_1d<SCHEME, N, false, T>(T(x[0]), wx, dwx);
+    if (bi.plive) store_plane_entry(wx);
   } else {
     if (!valid) return;
     T wx[N], wy[N], wz[N], dwx[N], dwy[N], dwz[N];
@@ -457,6 +474,49 @@ __global__ __launch_bounds__(256) void bin_atoms_kernel(Geom g, BrickGeom bg, Bi
                                                        const T* __restrict__ q, AtomRecord<T>* __restrict__ atom_rec,
                                                        const int* __restrict__ slot_of, T* __restrict__ qs) {
   bin_atoms_body<SCHEME, N, T, COALESCE>(g, bg, bi, Natoms, pos, over_brick, rec, wts, q, atom_rec, blockIdx.x, slot_of, qs);
+}
+
+template <int SCHEME, int N, typename T>
+__global__ __launch_bounds__(256) void bin_atoms_lean_kernel(Geom g, BrickGeom bg, BinIndex bi, int64_t Natoms,
+                                                            const T* __restrict__ pos, int* __restrict__ over_brick,
+                                                            const T* __restrict__ q, AtomRecord<T>* __restrict__ atom_rec,
+                                                            T* __restrict__ qs, int* __restrict__ slot_dst) {
+  bin_atoms_body<SCHEME, N, T, false, true>(g, bg, bi, Natoms, pos, over_brick, nullptr, nullptr, q, atom_rec, blockIdx.x, nullptr,
+                                            qs, slot_dst);
+}
+
+// ---- deferred slot fill: riders of the inverse (y,z) plane launch ------------------------------------------------------------
+// What the lean binning pass leaves out is read for the first time by the gather, three launches later, so it is written by
+// rider workgroups of the launch in front of the gather (kfilter.hip yz_planes_kernel: 64 plane workgroups on 256 CUs at 64^3),
+// off the chain of dependent launches.  A rider takes per_rider atoms (at most a workgroup's threads; fewer than the planes' 1024,
+// so that the riders spread over all the CUs the planes leave idle: kSlotRiderAtoms), thread tid the atom rider * per_rider + tid.
+// It recomputes m and the offsets with the
+// very atom_mesh_coords call of the binning pass (bit-identical to what the plane-list entry was made from), and writes the slot
+// slot_dst[i] -- record, 6N weights, charge, reach code -- exactly as the one-pass body does.  No LDS, no barrier, no dependence
+// on another workgroup of the launch: the slot and the counters come from the binning LAUNCH.  Host side: SlotRider (common.h).
+#ifndef MIPME_SLOT_RIDER_ATOMS
+#define MIPME_SLOT_RIDER_ATOMS 256
+#endif
+static constexpr int kSlotRiderAtoms = MIPME_SLOT_RIDER_ATOMS;  // atoms per slot rider (256: one wavefront per SIMD of its CU)
+template <int SCHEME, int N, typename T>
+__device__ __forceinline__ void slot_rider_body(const SlotRider& r, unsigned rider) {
+  if (int(threadIdx.x) >= r.per_rider) return;
+  const int64_t i = int64_t(rider) * r.per_rider + threadIdx.x;
+  if (i >= r.n_atoms) return;
+  const T* __restrict__ pos = static_cast<const T*>(r.pos);
+  const T* __restrict__ q = static_cast<const T*>(r.q);
+  const int64_t dst = r.dst[i];
+  int m[3];
+  double x[3];
+  atom_mesh_coords<T>(r.g, (N % 2) == 0, pos, i, m, x);
+  r.rec[dst] = make_int4(m[0], m[1], m[2], int(i));
+  static_cast<T*>(r.qs)[dst] = q[i];
+  if (dst < r.over_base) r.codes[dst] = (unsigned char)reach_code<N>(m, r.g.nx, r.g.ny, r.g.nz);
+  T wx[N], wy[N], wz[N], dwx[N], dwy[N], dwz[N];
+  weights_1d<SCHEME, N, true, T>(T(x[0]), wx, dwx);
+  weights_1d<SCHEME, N, true, T>(T(x[1]), wy, dwy);
+  weights_1d<SCHEME, N, true, T>(T(x[2]), wz, dwz);
+  store_slot_weights<N, T>(static_cast<T*>(r.wts) + dst * wts_stride<N, T>(), wx, wy, wz, dwx, dwy, dwz);
 }
 
 // ---- deterministic slots (MIPME_DETERMINISTIC) -----------------------------------------------------------------------------
@@ -2108,6 +2168,7 @@ struct BinsView {
   void* wts;
   void* qs;  // per-slot charge (written by the binning pass for single-channel charges)
   double* epart;
+  int* dst;  // per atom: its destination slot (lean binning pass -> slot riders)
 };
 
 static inline BinsView bins_view(const mipme_mesh_t* m, int64_t N, int dtype, void* bins) {
@@ -2135,6 +2196,7 @@ static inline BinsView bins_view(const mipme_mesh_t* m, int64_t N, int dtype, vo
   v.idx.wmax = l.pcap ? (float*)(b + l.wmax) : nullptr;
   v.idx.n_wmax = l.pcap ? int((N + 63) / 64) : 0;
   v.epart = (double*)(b + l.epart);
+  v.dst = (int*)(b + l.dst);
   return v;
 }
 

@@ -15,6 +15,10 @@ void set_error(const char* fmt, ...);
 // name (without template arguments) of the last co-scheduled spread + pair-sum kernel this thread launched or captured
 // (mipme_last_cosched_kernel: what a benchmark labels its dominant launch with)
 void note_cosched_kernel(const char* name);
+// (mipme_last_slot_fill: 0 = the binning pass filled the gather's slots itself; B > 0 = slot riders of B atoms each)
+void note_slot_fill(int rider_atoms);
+// (mipme_last_cell_riders: cell riders on the inverse plane launch that carried the slot riders)
+void note_cell_riders(int n);
 
 #define MIPME_CHECK_HIP(expr)                                                                 \
   do {                                                                                        \
@@ -276,6 +280,24 @@ struct GatherTailHost {
   int elog_cap;
 };
 
+// Deferred slot fill (bricks_device.h bin_atoms_body<LEAN>, slot_rider_body): what the rider workgroups of the inverse (y,z)
+// plane launch need to write the gather's slot data of every atom -- filled by bricks.hip bins_slot_rider, handed to the
+// convolution in ConvCell::slots.  Riders: ceil(n_atoms / per_rider).
+struct SlotRider {
+  int64_t n_atoms = 0;  // 0: none
+  int per_rider = 0;    // atoms per rider workgroup (<= its threads; set by the launcher)
+  int scheme = 0, order = 0;
+  Geom g;
+  const void* pos = nullptr;  // (n_atoms, 3) reals
+  const void* q = nullptr;    // (n_atoms) reals
+  const int* dst = nullptr;   // per atom: its slot, written by the lean binning pass of this call
+  int4* rec = nullptr;
+  void* wts = nullptr;
+  void* qs = nullptr;
+  unsigned char* codes = nullptr;
+  int64_t over_base = 0;
+};
+
 // The cell gradient of an energy step inside the fused convolution (kfilter.hip, convolve_xfused): the x stage stores
 // w = mu |rho^|^2 per k-point, and rider workgroups of the launch behind it form the sums against the filter's derivative table
 // (+ slices of the pair kernel's cell sums and of the x stage's energy sums): one row of 25 doubles per rider
@@ -290,6 +312,7 @@ struct ConvCell {
   const void* rho_hat_in;  // nullable: the general adjoint -- w = mu Re[rho^ conj psi^] instead of mu |rho^|^2
   double* kh_rows;      // nullable: 12 sums K[c][d], H[c] per rider, the rows cellgrad_finalize_kernel reads
   int* ticket;          // ... and its ticket counter, cleared by the first rider
+  const SlotRider* slots = nullptr;  // nullable: slot riders of a forward call with a deferred slot fill (independent of the above)
 };
 
 // Row workgroups of the co-scheduled pair sum that ride on the persistent convolution launch instead of the spread launch:
@@ -299,7 +322,9 @@ struct ConvCell {
 struct PlaneHost {
   void* hat = nullptr;    // (nx, ny, nz/2 + 1) complex: receives the transformed planes
   bool keep_mesh = true;  // the caller reads the real charge mesh afterwards: no plane spread (it does not form it)
-  bool slot_values = false;  // the binning pass of this call wrote the spread's values (single-channel charges) by bin slot
+  bool slot_values = false;  // the values are this call's single-channel charges, which the binning pass files by bin slot (one-pass
+                             // kernel: at once, for the brick spread; deferred slot fill: by the slot riders, after the plane spread,
+                             // which reads its plane-list entries and never the slots)
   // several workgroups per plane, each with a part of the plane's atoms and a transform of its own: part 0 -> hat, part k ->
   // hat_more + (k - 1) * more_stride (complex values); the x stage of the convolution adds them up
   int parts = 1;

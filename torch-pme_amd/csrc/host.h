@@ -99,7 +99,10 @@ int plane_bands(const mipme_mesh_t* m, int dtype);
 const void* bins_epart(const mipme_mesh_t* m, int64_t N, int dtype, void* bins, int64_t* n);
 bool sr_job_fusable(const mipme_sr_job_t* job);
 template <typename T> int bins_build(hipStream_t st, const mipme_mesh_t* m, int64_t n_atoms, const void* pos, void* bins, int* live,
-                                     const void* q, void* atom_rec, bool plane_lists = false);
+                                     const void* q, void* atom_rec, bool plane_lists = false, bool defer_slots = false);
+bool plane_spread_runs(const mipme_mesh_t* m, int64_t N, int dtype, const mipme_sr_job_t* job, const PlaneHost* ph, bool forward);
+bool bins_defer_slots(const mipme_mesh_t* m, int64_t N, int dtype, const mipme_sr_job_t* job, const PlaneHost* ph);
+SlotRider bins_slot_rider(const mipme_mesh_t* m, int64_t N, int dtype, void* bins, const void* pos, const void* q);
 template <typename T> int spread_bricks(hipStream_t st, const mipme_mesh_t* m, int64_t N, void* bins, const void* val, double scale, void* mesh,
                                         int* clear_count, const mipme_sr_job_t* job, bool want_epart, double* cpart, const PlaneHost* ph = nullptr,
                                         bool* used_planes = nullptr);

@@ -15,6 +15,7 @@
 #include "host.h"
 #include "kpot.h"
 #include "fft_lds.h"
+#include "bricks_device.h"  // slot_rider_dispatch: the slot riders of the inverse (y,z) plane launch
 
 namespace mipme {
 
@@ -588,6 +589,27 @@ __global__ __launch_bounds__(1024) void yz_planes_kernel(int ny, int nz, int log
   yz_plane_body<T, INVERSE, YSTAGE>(ny, nz, logny, loglz, real_in, hat, real_out, blockIdx.x, smem_yz);  // plane = (channel, x)
 }
 
+// The inverse planes of a forward call with a deferred slot fill: behind the planes the cell riders (if any), behind those the slot
+// riders (bricks_device.h slot_rider_body) -- block index ranges [n_planes, n_planes + n_riders) and from there to the end of the
+// grid.  The slot riders use no LDS (the dynamic region belongs to the planes and the cell riders) and wait for nobody.  Like
+// everything in this launch they sit behind the skip flag; they exist only on forward calls, where it is clear (yz_planes checks).
+template <int SCHEME, int N, typename T>
+__global__ __launch_bounds__(1024) void yz_planes_slots_kernel(int ny, int nz, int logny, int loglz, Cplx<T>* __restrict__ hat,
+                                                             T* __restrict__ real_out, const int* __restrict__ skip,
+                                                             unsigned n_planes, CellRider rider, SlotRider slots) {
+  MIPME_SKIP_IF_SET(skip);
+  extern __shared__ __attribute__((aligned(16))) char smem_yz[];
+  if (blockIdx.x >= n_planes + unsigned(rider.n_riders)) {  // (uniform)
+    slot_rider_body<SCHEME, N, T>(slots, blockIdx.x - n_planes - unsigned(rider.n_riders));
+    return;
+  }
+  if (blockIdx.x >= n_planes) {  // (uniform)
+    cell_rider_body<T>(rider, blockIdx.x - n_planes, int(blockDim.x), reinterpret_cast<double*>(smem_yz));
+    return;
+  }
+  yz_plane_body<T, true, true>(ny, nz, logny, loglz, nullptr, hat, real_out, blockIdx.x, smem_yz);  // plane = (channel, x)
+}
+
 // y columns of the half-complex mesh for planes that do not fit LDS (split_yz): one workgroup transforms the columns
 // (x, kz0 .. kz0 + KZ) along y in LDS as tile[y][z] -- forward: decimation in frequency, stored back through the bit reversal;
 // inverse: loaded through the bit reversal, decimation in time, conjugate twiddles -- in place, natural order in memory both
@@ -699,7 +721,10 @@ static void yz_launch_shape(const mipme_fft_plan* p, size_t real_bytes, int& log
 // per direction, a launch of their own otherwise
 template <typename T>
 static int yz_planes(mipme_fft_plan* p, hipStream_t st, bool inverse, const void* real_in, void* hat, void* real_out,
-                     const CellRider* rider = nullptr) {
+                     const CellRider* rider = nullptr, const SlotRider* slots = nullptr) {
+  // slot riders (forward call with a deferred slot fill): only on the single inverse launch, and never conditional
+  MIPME_REQUIRE(!slots || (inverse && !p->split_yz && skip_flag_slot() == nullptr),
+                "slot riders need the single-launch inverse planes and a clear skip flag");
   if (p->split_yz) {  // planes beyond one workgroup's LDS: z rows and y columns as two launches
     int rc;
     if (!inverse) {
@@ -724,7 +749,30 @@ static int yz_planes(mipme_fft_plan* p, hipStream_t st, bool inverse, const void
       raised[inverse ? 1 : 0] = true;
     }
   }
-  if (inverse)
+  if (inverse && slots) {
+    // a rider serves at most kSlotRiderAtoms atoms with the first threads of its workgroup: a quarter of the planes' 1024 threads,
+    // so that the riders spread over the CUs the planes leave idle instead of queueing sixteen waves deep on a few of them
+    SlotRider sr = *slots;
+    sr.per_rider = threads < kSlotRiderAtoms ? threads : kSlotRiderAtoms;
+    const unsigned n_slot_riders = unsigned((sr.n_atoms + sr.per_rider - 1) / sr.per_rider);
+    const bool raise = lds > 64 * 1024;
+    int slot_rc = MIPME_OK;
+    MIPME_DISPATCH_STENCIL_B(sr.scheme, sr.order, (slot_rc = [&]() -> int {
+      if (raise) {  // once per instantiation: allow the large dynamic allocation
+        static bool raised_slots = false;
+        if (!raised_slots) {
+          MIPME_CHECK_HIP(hipFuncSetAttribute((const void*)yz_planes_slots_kernel<S, N, T>, hipFuncAttributeMaxDynamicSharedMemorySize, int(kYzMaxLds)));
+          raised_slots = true;
+        }
+      }
+      yz_planes_slots_kernel<S, N, T><<<grid + n_riders + n_slot_riders, threads, lds, st>>>(
+          p->ny, p->nz, logny, loglz, (Cplx<T>*)hat, (T*)real_out, skip_flag_slot(), grid, n_riders ? *rider : CellRider{}, sr);
+      return MIPME_OK;
+    }()));
+    if (slot_rc) return slot_rc;
+    note_slot_fill(sr.per_rider);
+    note_cell_riders(int(n_riders));
+  } else if (inverse)
     yz_planes_kernel<T, true><<<grid + n_riders, threads, lds, st>>>(p->ny, p->nz, logny, loglz, nullptr, (Cplx<T>*)hat, (T*)real_out,
                                                                      skip_flag_slot(), grid, n_riders ? *rider : CellRider{});
   else
@@ -1139,8 +1187,10 @@ static int convolve_xfused_t(mipme_fft_plan* p, hipStream_t st, const void* mesh
     MIPME_XCONV_LAUNCH(0);
 #undef MIPME_XCONV_LAUNCH
   MIPME_LAUNCH_CHECK();
+  const SlotRider* slots = (cc && cc->slots && cc->slots->n_atoms > 0) ? cc->slots : nullptr;
+  MIPME_REQUIRE(!slots || (p->own_yz && p->batch == 1), "slot riders need the plan's own (y,z) plane kernels and a single mesh");
   if (p->own_yz) {
-    int rc = yz_planes<T>(p, st, true, nullptr, hat, mesh_out, riders ? &rider : nullptr);
+    int rc = yz_planes<T>(p, st, true, nullptr, hat, mesh_out, riders ? &rider : nullptr, slots);
     if (rc) return rc;
   } else {
     if (riders) {
