@@ -148,7 +148,7 @@ int mipme_pair_dot(void* stream, int dtype, int idx_dtype, int64_t n_pairs, int 
 
 /* ---- PMECalculator._compute_kspace, calculators/pme.py:88-143 (P3M: calculators/p3m.py:45-84) -- */
 
-/* out_lr[i,c] = 1/2 [ gather(convolve(spread(q)))/V - q*self - 2*bg*Q_c/V ]      (no slab term)
+/* out_lr[i,c] = 1/2 [ gather(convolve(spread(q)))/V - q*self - 2*bg*Q_c/V ]      (no slab term unless args->slab asks for it)
  * Work buffers (caller allocated): rho_mesh, phi_mesh (C,nx,ny,nz); rho_hat, hat_work complex half grids;
  * dc (C).  phi_mesh, rho_hat, dc and out_phi (N,C, nullable: the raw gather/V) are what the backward needs.
  * gather_wait_event (hipEvent_t as void*, nullable) + accumulate_out = 1: the final gather first waits for the event
@@ -220,7 +220,7 @@ typedef struct mipme_kspace_forward_args {
   const mipme_sr_job_t* sr_job;
   void* out_cell_partials;
   /* Tail of an energy + forces step folded into the gather launch (all three nullable together; needs sr_job with force sums,
-   * out_field, no slab term): out_energy (1 real) = sum_a charges_a out_lr_a -- the reduction the caller's (q * V).sum()
+   * out_field; a slab term only through `slab` below): out_energy (1 real) = sum_a charges_a out_lr_a -- the reduction the caller's (q * V).sum()
    * performs (README.rst:112-114) -- and out_grad_positions (N,3) = s q_a (c force_a + field_a), the gradient of that energy
    * w.r.t. the positions times s = grad_seed[0] (device scalar; NULL = 1), c = 1/2 for a full list: what
    * mipme_dot_forward + mipme_sr_rows_finalize would compute in two more launches.  The energy is assembled without any
@@ -270,6 +270,19 @@ typedef struct mipme_kspace_forward_args {
   void* energy_log;
   void* energy_log_cursor;
   int64_t energy_log_capacity;
+  /* 2-D periodic (slab) systems, potentials/coulomb.py:6-40, in the gather tail above: slab = 0 -- off (what a caller compiled
+   * before the field existed passes) -- or the NON-periodic axis + 1.  With z_a = positions[a, axis] (Cartesian), L = |cell[axis]|,
+   * c = 4 pi prefactor / V and the moments Q, M, M2 = sum_a q_a {1, z_a, z_a^2}:
+   *   out_lr[a]              += c/2 (z_a M - (M2 + Q z_a^2)/2 - Q L^2/12)
+   *   out_energy             += c/2 (M^2 - Q M2 - Q^2 L^2/12)
+   *   out_grad_positions[a]  += s c q_a (M - Q z_a) along the axis; out_field[a] likewise per unit s q_a
+   *   out_grad_charges       =  2 s out_lr with the new out_lr;  out_grad_cell [0..8], [18..26] += the term's V and L parts
+   * -- every atom in the gather launch itself; the moments come from ONE small launch ahead of the spread (fp64 block sums added
+   * up in a fixed order: the same bits run after run; scratch: the plan's), so a call with the term has one launch more than the
+   * same call without.  MIPME_EINVAL without the gather tail, for more than one channel, or for a potential that is not 1/r;
+   * every other call adds the term with mipme_slab_forward / mipme_slab_backward. */
+  int32_t slab;
+  int32_t _pad_slab;
 } mipme_kspace_forward_args_t;
 #define MIPME_FWD_RHO_MESH_UNUSED 1
 int mipme_kspace_forward(const mipme_kspace_forward_args_t* args);
@@ -897,6 +910,10 @@ typedef struct {
   void* energy_log;
   void* energy_log_cursor;
   int64_t energy_log_capacity;
+  /* appended with the slab term of the gather tail: as mipme_kspace_forward_args_t.slab (0 = off, else the non-periodic axis + 1;
+   * z_a from the records; six launches per step instead of five) */
+  int32_t slab;
+  int32_t _pad_slab;
 } mipme_md_args_t;
 int mipme_md_supported(const mipme_mesh_t* mesh, const mipme_potential_t* pot, int64_t n_atoms, int dtype);
 int64_t mipme_md_lists_ints(const mipme_mesh_t* mesh, int64_t n_atoms);

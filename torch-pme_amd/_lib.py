@@ -197,6 +197,7 @@ class KspaceForwardArgs(_VersionedArgs):
         ("out_grad_charges", C.c_void_p), ("out_grad_cell", C.c_void_p), ("G_deriv", C.c_void_p), ("cell_work", C.c_void_p),
         ("aux_seed", C.c_void_p), ("out_rho_hat", C.c_void_p), ("flags", C.c_int64),
         ("energy_log", C.c_void_p), ("energy_log_cursor", C.c_void_p), ("energy_log_capacity", C.c_int64),
+        ("slab", C.c_int32), ("_pad_slab", C.c_int32),
     ]
 
 
@@ -247,6 +248,7 @@ class MdArgs(_VersionedArgs):
         ("grad_charges", C.c_void_p), ("grad_cell", C.c_void_p), ("G_deriv", C.c_void_p), ("cell_work", C.c_void_p),
         ("aux_seed", C.c_void_p),
         ("energy_log", C.c_void_p), ("energy_log_cursor", C.c_void_p), ("energy_log_capacity", C.c_int64),
+        ("slab", C.c_int32), ("_pad_slab", C.c_int32),
     ]
 
     def __init__(self, **fields):

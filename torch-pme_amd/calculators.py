@@ -273,7 +273,7 @@ class Calculator(torch.nn.Module):
         slab_axis = None
         is_coulombic = pot_desc.kind == _lib.COULOMB or pot_desc.exponent == 1  # the slab term exists for 1/r only
         if has_kspace and periodic is not None and is_coulombic:
-            slab_axis = ops._slab_axis(periodic.tolist())
+            slab_axis = ops.slab_axis_of(periodic)  # (per tensor and version: a repeated call copies nothing to the host)
         nan_flag = self._nan_flag_ptr() if geom is not None else None
         if nan_flag is not None:
             self.__dict__["_nan_shape"] = [charges.shape[1], *geom.ns]

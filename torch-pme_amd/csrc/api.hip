@@ -113,6 +113,64 @@ static int check_plan(const mipme_fft_plan* plan, int dtype, const mipme_mesh_t*
   return MIPME_OK;
 }
 
+// ---- moments of the slab term of a gather tail (GatherTail, bricks_device.h): Q, M, M2 = sums of q, q z, q z^2 --------------
+// One launch ahead of the spread -- the moments depend on the atoms alone.  Block sums in fp64, then the block that draws the last
+// ticket adds them up in index order and leaves the ticket at zero (as dot_kernel does): the same bits run after run.
+// z = zp[a * zs], q = qp[a * qs]: positions + charges of a calculator call (strides 3, 1) or the (x, y, z, q) records of the live
+// step (4, 4).  work: kSlabWork doubles = {Q, M, M2}, 3 sums per block, the ticket; zero when first used.
+template <typename T>
+__global__ __launch_bounds__(256) void slab_moments_blocks_kernel(int64_t N, const T* __restrict__ zp, int zs,
+                                                                 const T* __restrict__ qp, int qs, double* work) {
+  double acc[3] = {0.0, 0.0, 0.0};
+  for (int64_t a = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; a < N; a += int64_t(gridDim.x) * blockDim.x) {
+    const double z = double(zp[a * zs]), q = double(qp[a * qs]);
+    acc[0] += q;
+    acc[1] += q * z;
+    acc[2] += q * z * z;
+  }
+  __shared__ double red[4][3];
+  __shared__ bool last;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  double* part = work + 3;
+  int* counter = reinterpret_cast<int*>(work + 3 + 3 * kSlabBlocks);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    double v = acc[k];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    if (lane == 0) red[wave][k] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int k = 0; k < 3; ++k)
+      __hip_atomic_store(&part[3 * blockIdx.x + k], (red[0][k] + red[1][k]) + (red[2][k] + red[3][k]), __ATOMIC_RELAXED,
+                         __HIP_MEMORY_SCOPE_AGENT);
+    const int ticket = __hip_atomic_fetch_add(counter, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+    last = ticket == int(gridDim.x) - 1;
+  }
+  __syncthreads();
+  if (!last || wave != 0) return;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    double tot = int(threadIdx.x) < int(gridDim.x)
+                     ? __hip_atomic_load(&part[3 * threadIdx.x + k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+                     : 0.0;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) tot += __shfl_xor(tot, off, 64);
+    if (threadIdx.x == 0) work[k] = tot;
+  }
+  if (threadIdx.x == 0) __hip_atomic_store(counter, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+template <typename T>
+static int slab_moments_blocks(hipStream_t st, int64_t N, const void* zp, int zs, const void* qp, int qs, double* work) {
+  static_assert(kSlabBlocks <= 64, "one wave adds the block sums up");
+  const unsigned blocks = unsigned(std::min<int64_t>(kSlabBlocks, (N + 255) / 256));
+  slab_moments_blocks_kernel<T><<<blocks, 256, 0, st>>>(N, (const T*)zp, zs, (const T*)qp, qs, work);
+  MIPME_LAUNCH_CHECK();
+  return MIPME_OK;
+}
+
 // a: the caller's arguments as mipme_kspace_forward has checked them; tail: its gather tail (NULL: potentials only)
 template <typename T>
 static int kspace_forward_t(const mipme_kspace_forward_args_t& a, const GatherTailHost* tail) {
@@ -144,6 +202,8 @@ static int kspace_forward_t(const mipme_kspace_forward_args_t& a, const GatherTa
       if (armed && counters) (void)zero_async(counters, sizeof(int) * n, st);
     }
   } guard{st, nullptr, plan_counter_words(m->nx, m->ny, m->nz), false};
+  if (tail && tail->slab)  // (one channel: the charges are (N))
+    STAGE(st, "slab_moments", slab_moments_blocks<T>(st, N, (const T*)a.positions + (tail->slab - 1), 3, a.charges, 1, tail->slab_mom));
   if (bins) {
     int* counters = fft_plan_brick_count(plan);
     guard.counters = counters;
@@ -228,7 +288,7 @@ static int kspace_forward_t(const mipme_kspace_forward_args_t& a, const GatherTa
   if (a.out_grad_cell)
     STAGE(st, "cell_finalize",
           cell_tail_finalize_impl<T>(st, m, bg_c, 0.5 * tail->force_scale, cw.n_riders, cw.n_bricks, cw.rows, cw.rpart, a.dc,
-                                     tail->aux_seed ? tail->aux_seed : tail->seed, a.out_grad_cell));
+                                     tail->aux_seed ? tail->aux_seed : tail->seed, a.out_grad_cell, tail));
   return MIPME_OK;
 }
 
@@ -883,6 +943,17 @@ static int load_args(const A* in, A& out, const char* what) {
 
 using namespace mipme;
 
+// `slab` of a step's arguments (0 = off, else the non-periodic axis + 1): the term lives in the gather tail, for one channel and 1/r
+static int check_slab(int slab, const mipme_mesh_t* mesh, const mipme_potential_t* pot, bool has_tail, const char* who) {
+  if (!slab) return MIPME_OK;
+  MIPME_REQUIRE(slab >= 1 && slab <= 3, "%s: slab must be 0 (off) or the non-periodic axis + 1, got %d", who, slab);
+  MIPME_REQUIRE(mesh->n_channels == 1, "%s: the slab term of the gather tail serves one channel, the mesh has %d (use "
+                "mipme_slab_forward / mipme_slab_backward)", who, int(mesh->n_channels));
+  MIPME_REQUIRE(has_tail, "%s: slab rides on the gather tail (out_energy, out_grad_positions); without it use mipme_slab_forward", who);
+  MIPME_REQUIRE(pot && (pot->kind == MIPME_COULOMB || pot->exponent == 1), "%s: the slab term exists for 1/r only", who);
+  return MIPME_OK;
+}
+
 // ---- MD step on live bins (live.hip) -----------------------------------------------------------------------------------------
 static int md_check(const mipme_md_args_t* in, mipme_md_args_t& a, const char* who) {
   MIPME_REQUIRE(in && in->size >= 16 && in->version == 1, "%s: NULL or unversioned argument struct", who);
@@ -935,6 +1006,11 @@ static int md_step_t(const mipme_md_args_t& a) {
   tail.grad_q = a.grad_charges;
   tail.aux_seed = a.aux_seed;
   tail.live_flags = a.host_flags;
+  if (a.slab) {
+    tail_attach_slab(tail, m, a.pot, a.slab);
+    STAGE(st, "slab_moments", slab_moments_blocks<T>(st, a.n_atoms, (const T*)a.records + (a.slab - 1), 4, (const T*)a.records + 3, 4,
+                                                     tail.slab_mom));
+  }
   if (a.energy_log && (rc = tail_attach_energy_log(tail, a.energy_log, a.energy_log_cursor, a.energy_log_capacity,
                                                    "energy_log needs energy_log_cursor")))
     return rc;
@@ -952,7 +1028,7 @@ static int md_step_t(const mipme_md_args_t& a) {
   if (a.grad_cell)
     STAGE(st, "cell_finalize",
           cell_tail_finalize_impl<T>(st, m, bg_c, 0.5, cw.n_riders, cw.n_bricks, cw.rows, cw.rpart, a.dc,
-                                     a.aux_seed ? a.aux_seed : a.grad_seed, a.grad_cell));
+                                     a.aux_seed ? a.aux_seed : a.grad_seed, a.grad_cell, &tail));
   return MIPME_OK;
 }
 
@@ -1048,6 +1124,8 @@ int mipme_kspace_forward(const mipme_kspace_forward_args_t* args_in) {
   int rc = load_args(args_in, a, "mipme_kspace_forward");
   if (rc) return rc;
   if ((rc = validate_mesh(a.mesh))) return rc;
+  // (what the arguments alone decide comes before anything that needs a device)
+  if ((rc = check_slab(a.slab, a.mesh, a.pot, a.out_energy && a.out_grad_positions, "mipme_kspace_forward"))) return rc;
   if ((rc = check_plan(a.plan, a.dtype, a.mesh))) return rc;
   const mipme_mesh_t* mesh = a.mesh;
   MIPME_REQUIRE(a.pot && a.pot->smearing > 0, "Must specify smearing to use a potential with PMECalculator");
@@ -1103,6 +1181,10 @@ int mipme_kspace_forward(const mipme_kspace_forward_args_t* args_in) {
       tail.records = a.out_records;
     }
   }
+  if (a.slab) {
+    tail_attach_slab(tail, mesh, a.pot, a.slab);
+    tail.records = a.out_records;  // z_a of the term
+  }
   DT_SWITCH(a.dtype, kspace_forward_t<float>(a, tp), kspace_forward_t<double>(a, tp));
 }
 
@@ -1140,6 +1222,7 @@ int mipme_md_step(const mipme_md_args_t* args_in) {
   MIPME_REQUIRE(a.cell && a.G && a.rho_mesh && a.hat_work && a.phi_mesh && a.dc && a.row_ptr && a.words && a.potentials &&
                     a.pair_force && a.energy && a.grad_positions, "NULL buffer passed to mipme_md_step");
   MIPME_REQUIRE((a.shift_format & 0xff) == 2, "mipme_md_step reads 4-byte entries (shift_format 2, with or without MIPME_ROWS_PADDED)");
+  if ((rc = check_slab(a.slab, a.mesh, a.pot, true, "mipme_md_step"))) return rc;
   if (a.grad_cell) {
     const int p = a.pot->kind == MIPME_COULOMB ? 1 : a.pot->exponent;
     MIPME_REQUIRE(a.G_deriv && a.cell_work, "grad_cell needs G_deriv (mipme_kfilter_build_deriv) and cell_work");

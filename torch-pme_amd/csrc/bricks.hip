@@ -376,26 +376,38 @@ int gather_bricks(hipStream_t st, const mipme_mesh_t* m, int64_t N, void* bins, 
                        : make_gather_tail<T>(*th, (const double*)v.epart, int((N + 64 / kRowLanes - 1) / (64 / kRowLanes)),
                                              th->records, nullptr);
     MIPME_REQUIRE(!tail.rpart || tail.rec4, "the cell sums of the gather need the atom records");
+    // the slab term: the same kernels compiled with it (SLAB), so that the launches without it carry no branch for it
+    const bool slab = th->slab != 0;
+    MIPME_REQUIRE(!slab || (tail.rec4 && tail.slab_mom), "the slab term of the gather needs the atom records and the moments");
+#define MIPME_GATHER_TAIL_LAUNCH(THREADS_V, DENSE_V, SLAB_V)                                                                       \
+  gather_tail_kernel<N, T, THREADS_V, DENSE_V, SLAB_V><<<brick_grid(bg), THREADS_V, 0, st>>>(                                       \
+      g, bg, v.idx, v.rec, (const T*)v.wts, (const T*)mesh, (const T*)q, (const T*)qsum, T(1.0 / m->volume), T(self_c), T(bg_c), \
+      (T*)out, (T*)raw, (T*)field, tail, (int*)nan_flag)
     if (sparse_bricks(N, bg.nb))
-      MIPME_DISPATCH_STENCIL_B(m->scheme, m->order,
-                               ((void)S, gather_tail_kernel<N, T, GATHER_THREADS_SPARSE><<<brick_grid(bg), GATHER_THREADS_SPARSE, 0, st>>>(
-                                   g, bg, v.idx, v.rec, (const T*)v.wts, (const T*)mesh, (const T*)q, (const T*)qsum,
-                                   T(1.0 / m->volume), T(self_c), T(bg_c), (T*)out, (T*)raw, (T*)field, tail, (int*)nan_flag)));
+      MIPME_DISPATCH_STENCIL_B(m->scheme, m->order, ((void)S, [&] {
+        if (slab)
+          MIPME_GATHER_TAIL_LAUNCH(GATHER_THREADS_SPARSE, false, true);
+        else
+          MIPME_GATHER_TAIL_LAUNCH(GATHER_THREADS_SPARSE, false, false);
+      }()));
     else
       MIPME_DISPATCH_STENCIL_B(m->scheme, m->order, ((void)S, [&] {
         // more bricks than two workgroups per CU hold at once: the build that admits three (see MIPME_GATHER_TAIL_WAVES)
         if constexpr (sizeof(T) == 4 && N <= 5) {
           if (bg.nb > 2 * 256) {
-            gather_tail_kernel<N, T, GATHER_THREADS, true><<<brick_grid(bg), GATHER_THREADS, 0, st>>>(
-                g, bg, v.idx, v.rec, (const T*)v.wts, (const T*)mesh, (const T*)q, (const T*)qsum, T(1.0 / m->volume), T(self_c),
-                T(bg_c), (T*)out, (T*)raw, (T*)field, tail, (int*)nan_flag);
+            if (slab)
+              MIPME_GATHER_TAIL_LAUNCH(GATHER_THREADS, true, true);
+            else
+              MIPME_GATHER_TAIL_LAUNCH(GATHER_THREADS, true, false);
             return;
           }
         }
-        gather_tail_kernel<N, T><<<brick_grid(bg), GATHER_THREADS, 0, st>>>(
-            g, bg, v.idx, v.rec, (const T*)v.wts, (const T*)mesh, (const T*)q, (const T*)qsum, T(1.0 / m->volume), T(self_c),
-            T(bg_c), (T*)out, (T*)raw, (T*)field, tail, (int*)nan_flag);
+        if (slab)
+          MIPME_GATHER_TAIL_LAUNCH(GATHER_THREADS, false, true);
+        else
+          MIPME_GATHER_TAIL_LAUNCH(GATHER_THREADS, false, false);
       }()));
+#undef MIPME_GATHER_TAIL_LAUNCH
     MIPME_LAUNCH_CHECK();
     return MIPME_OK;
   }

@@ -1735,7 +1735,18 @@ struct GatherTail {
   double* elog = nullptr;
   int* elog_cursor = nullptr;
   int elog_cap = 0, elog_stride = 1;
+  // 2-D periodic (slab) term, read by the SLAB instantiations only (potentials/coulomb.py:6-40; z = r_a[slab_axis] Cartesian):
+  //   V_a += c0/2 (z M - (M2 + Q z^2)/2 - Q L^2/12),  field_a[axis] += c0 (M - Q z)  (per unit charge, so that grad_positions
+  //   and every other consumer of the field get the term),  E += c0/2 (M^2 - Q M2 - Q^2 L^2/12)
+  // slab_mom = {Q, M, M2} in fp64 from the moments launch ahead of the spread; rec4 supplies z
+  const double* slab_mom = nullptr;
+  double slab_c0 = 0.0, slab_L = 0.0;
+  int slab_axis = 0;
 };
+template <typename T>
+__device__ __forceinline__ T slab_coord(const AtomRecord<T>& r, int axis) {
+  return axis == 0 ? r.x : (axis == 1 ? r.y : r.z);
+}
 // The device form of a host-side tail.  What differs between the launches stays with the caller: where the pair kernel's energy
 // partial sums are (per wave in the bins buffer, or th.epart_k + th.n_k once the x stage of the convolution has reduced them),
 // the atom records of the cell sums, and the flag word of a live step.
@@ -1760,6 +1771,12 @@ static GatherTail<T> make_gather_tail(const GatherTailHost& th, const double* ep
   tail.elog = th.elog;
   tail.elog_cursor = th.elog_cursor;
   tail.elog_cap = th.elog_cap;
+  if (th.slab) {
+    tail.slab_mom = th.slab_mom;
+    tail.slab_c0 = th.slab_c0;
+    tail.slab_L = th.slab_L;
+    tail.slab_axis = th.slab - 1;
+  }
   return tail;
 }
 
@@ -1785,7 +1802,7 @@ __device__ __forceinline__ void tail_rpart(double (&r3)[3], double* __restrict__
   }
 }
 
-template <typename T, int THREADS>
+template <typename T, int THREADS, bool SLAB = false>
 __device__ __forceinline__ void tail_energy(const GatherTail<T>& tail, const T* __restrict__ qsum, T inv_vol, T self_c,
                                             T bg_c) {
   __shared__ double tred[THREADS / 64][3];
@@ -1810,6 +1827,10 @@ __device__ __forceinline__ void tail_energy(const GatherTail<T>& tail, const T* 
       for (int k = 0; k < 3; ++k) t[k] += tred[w][k];
     const double Q = double(qsum[0]);
     double e = t[0] + 0.5 * double(inv_vol) * t[2] - 0.5 * double(self_c) * t[1] - double(bg_c) * double(inv_vol) * Q * Q;
+    if constexpr (SLAB) {
+      const double sQ = tail.slab_mom[0], sM = tail.slab_mom[1], sM2 = tail.slab_mom[2];
+      e += 0.5 * tail.slab_c0 * (sM * sM - sQ * sM2 - sQ * sQ * tail.slab_L * tail.slab_L / 12.0);
+    }
     if (tail.live_flags && (__hip_atomic_load(tail.live_flags, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) & 2)) e = __builtin_nan("");
     tail.energy[0] = T(e);
     if (tail.elog) {
@@ -1820,7 +1841,7 @@ __device__ __forceinline__ void tail_energy(const GatherTail<T>& tail, const T* 
   }
 }
 
-template <int N, bool FIELD, typename T, bool TAIL = false, int THREADS = GATHER_THREADS>
+template <int N, bool FIELD, typename T, bool TAIL = false, int THREADS = GATHER_THREADS, bool SLAB = false>
 __device__ __forceinline__ void gather_brick_body(const Geom& g, const BrickGeom& bg, int C, const BinIndex& bins,
                                                   const int4* __restrict__ rec, const T* __restrict__ wts,
                                                   const T* __restrict__ mesh, const T* __restrict__ q,
@@ -1830,6 +1851,7 @@ __device__ __forceinline__ void gather_brick_body(const Geom& g, const BrickGeom
                                                   int* __restrict__ nan_flag = nullptr) {
   static_assert(N <= kGatherLanes, "one lane per z point of the stencil");
   static_assert(!TAIL || FIELD, "the tail needs the mesh field");
+  static_assert(!SLAB || TAIL, "the slab term rides in the tail");
   constexpr int LANES = kGatherLanes;
   constexpr int GROUPS = THREADS / LANES;
   constexpr int TL = BRICK + N - 1;
@@ -1851,7 +1873,18 @@ __device__ __forceinline__ void gather_brick_body(const Geom& g, const BrickGeom
   if constexpr (TAIL) {
     if (tail->seed) seed = tail->seed[0];
     seed_aux = tail->aux_seed ? tail->aux_seed[0] : seed;
-    if (block == 0) tail_energy<T, THREADS>(*tail, qsum, inv_vol, self_c, bg_c);  // uniform per workgroup
+    if (block == 0) tail_energy<T, THREADS, SLAB>(*tail, qsum, inv_vol, self_c, bg_c);  // uniform per workgroup
+  }
+  // SLAB: the term's coefficients, uniform over the launch -- formed in double from the moments, used in the working type:
+  //   field += fA - fB z,   V += z (pA - pB z) + pK
+  T fA = T(0), fB = T(0), pA = T(0), pB = T(0), pK = T(0);
+  if constexpr (SLAB) {
+    const double sQ = tail->slab_mom[0], sM = tail->slab_mom[1], sM2 = tail->slab_mom[2], c0 = tail->slab_c0;
+    fA = T(c0 * sM);
+    fB = T(c0 * sQ);
+    pA = T(0.5 * c0 * sM);
+    pB = T(0.25 * c0 * sQ);
+    pK = T(-0.5 * c0 * (0.5 * sM2 + sQ * tail->slab_L * tail->slab_L / 12.0));
   }
   double r3[3] = {0.0, 0.0, 0.0};
   if (beg == end && n_over == 0) {
@@ -1914,7 +1947,7 @@ __device__ __forceinline__ void gather_brick_body(const Geom& g, const BrickGeom
       AtomRecord<T> r_early{T(0), T(0), T(0), T(0)};
       if constexpr (TAIL) {
         f_early = tail->force[3 * int64_t(a.w) + (l < 3 ? l : 0)];
-        if (tail->rpart) r_early = tail->rec4[a.w];
+        if (SLAB || tail->rpart) r_early = tail->rec4[a.w];
       }
       if (it == 0) __syncthreads();  // tile staged (uniform: every thread runs the first pass)
       const int rx = a.x - ox, ry = a.y - oy, rz = a.z - oz;
@@ -1944,10 +1977,14 @@ __device__ __forceinline__ void gather_brick_body(const Geom& g, const BrickGeom
           // lanes 0..2 own one Cartesian component each: field (kept for other consumers) and the assembled gradient
           const int k3 = l < 3 ? l : 0;
           const T fc = T(g.inv[3 * k3]) * fx + T(g.inv[3 * k3 + 1]) * fy + T(g.inv[3 * k3 + 2]) * fz;
+          T fs = fc;  // SLAB: + the term's field along its axis (the cell sums below take the mesh part alone)
+          if constexpr (SLAB) {
+            if (l == tail->slab_axis) fs += fA - fB * slab_coord(r_early, tail->slab_axis);
+          }
           if (l < 3 && valid) {
             const int64_t o = int64_t(a.w);
-            field[3 * o + l] = fc;
-            tail->grad_pos[3 * o + l] = seed * q_early * (tail->force_scale * f_early + fc);
+            field[3 * o + l] = fs;
+            tail->grad_pos[3 * o + l] = seed * q_early * (tail->force_scale * f_early + fs);
             if (tail->rpart) {
               const double gp = double(seed_aux * q_early * fc);
               r3[0] += double(r_early.x) * gp;
@@ -1967,7 +2004,11 @@ __device__ __forceinline__ void gather_brick_body(const Geom& g, const BrickGeom
         const int64_t o = int64_t(a.w) * C + c;
         if (q) {
           const T phi = acc * inv_vol;
-          const T lr = T(0.5) * (phi - self_c * q_early - T(2) * bg_c * inv_vol * qsum[c]);
+          T lr = T(0.5) * (phi - self_c * q_early - T(2) * bg_c * inv_vol * qsum[c]);
+          if constexpr (SLAB) {
+            const T z = slab_coord(r_early, tail->slab_axis);
+            lr += z * (pA - pB * z) + pK;
+          }
           const T v_final = accumulate ? out_early + lr : lr;
           out[o] = v_final;
           if constexpr (TAIL) {
@@ -2012,7 +2053,7 @@ __global__ __launch_bounds__(GATHER_THREADS) void gather_brick_kernel(Geom g, Br
 #ifndef MIPME_GATHER_TAIL_WAVES
 #define MIPME_GATHER_TAIL_WAVES 6
 #endif
-template <int N, typename T, int THREADS = GATHER_THREADS, bool DENSE = false>
+template <int N, typename T, int THREADS = GATHER_THREADS, bool DENSE = false, bool SLAB = false>
 __global__ __launch_bounds__(THREADS, DENSE ? MIPME_GATHER_TAIL_WAVES : 1) void gather_tail_kernel(Geom g, BrickGeom bg, BinIndex bins,
                                                              const int4* __restrict__ rec, const T* __restrict__ wts,
                                                              const T* __restrict__ mesh, const T* __restrict__ q,
@@ -2022,8 +2063,8 @@ __global__ __launch_bounds__(THREADS, DENSE ? MIPME_GATHER_TAIL_WAVES : 1) void 
   MIPME_WG_STAMP_GATHER(0);
   const unsigned b = brick_of(bg, blockIdx.x);
   if (b < unsigned(bg.nb))
-    gather_brick_body<N, true, T, true, THREADS>(g, bg, 1, bins, rec, wts, mesh, q, qsum, inv_vol, self_c, bg_c, true, out, raw,
-                                                 field, b, &tail, nan_flag);
+    gather_brick_body<N, true, T, true, THREADS, SLAB>(g, bg, 1, bins, rec, wts, mesh, q, qsum, inv_vol, self_c, bg_c, true, out,
+                                                       raw, field, b, &tail, nan_flag);
 #if MIPME_WG_TIMELINE_GATHER
   __syncthreads();
 #endif

@@ -278,7 +278,16 @@ struct GatherTailHost {
   double* elog;
   int* elog_cursor;
   int elog_cap;
+  // 2-D periodic (slab) term in the tail (mipme.h, slab): 0 = off, else the non-periodic axis + 1; c0 = prefactor 4 pi / V,
+  // L = |cell[axis]|, mom = {Q, M, M2} = sums of q, q z, q z^2 (fp64, written by the moments launch ahead of the spread; the
+  // blocks' partial sums and the ticket of that launch follow them: kSlabWork doubles in all)
+  int slab;
+  double slab_c0, slab_L;
+  double* slab_mom;
 };
+// block sums of the slab moments: at most kSlabBlocks blocks, the one that draws the last ticket adds them up in index order
+static constexpr int kSlabBlocks = 64;
+static constexpr int kSlabWork = 3 + 3 * kSlabBlocks + 1;
 
 // Deferred slot fill (bricks_device.h bin_atoms_body<LEAN>, slot_rider_body): what the rider workgroups of the inverse (y,z)
 // plane launch need to write the gather's slot data of every atom -- filled by bricks.hip bins_slot_rider, handed to the

@@ -74,7 +74,8 @@ template <typename T> int cellgrad_finalize_impl(hipStream_t st, const mipme_mes
                                                  const void* rho_dc, const void* psi_dc, const void* energy_scale, void* grad_cell,
                                                  int64_t kgrid_blocks, const void* field, const void* q);
 template <typename T> int cell_tail_finalize_impl(hipStream_t st, const mipme_mesh_t* m, double bg, double pair_scale, int64_t n_rows,
-                                                  int64_t n_bricks, const void* rows, const void* rpart, const void* dc, const void* seed, void* out);
+                                                  int64_t n_bricks, const void* rows, const void* rpart, const void* dc, const void* seed, void* out,
+                                                  const GatherTailHost* slab = nullptr);
 
 // ---- rspace.hip: pair-list kernels -------------------------------------------------------------------------------------------
 template <typename T, typename I> int rspace_forward_impl(hipStream_t st, int64_t P, int64_t N, int C, const void* pairs, const void* dist, const void* q,
@@ -148,9 +149,19 @@ inline int tail_attach_plan_scratch(GatherTailHost& tail, mipme_fft_plan* plan) 
   void* scratch = nullptr;
   tail.n_k = xconv_blocks(plan);
   tail.sr_reduced = 1;
-  const int rc = fft_plan_tail_scratch(plan, 3 * int64_t(sizeof(double)) * tail.n_k, &scratch);
+  // (+ the moments of a slab term and the scratch of their launch: the size of the plan's buffer cannot change later)
+  const int rc = fft_plan_tail_scratch(plan, int64_t(sizeof(double)) * (3 * tail.n_k + kSlabWork), &scratch);
   tail.epart_k = scratch;
+  tail.slab_mom = scratch ? (double*)scratch + 3 * tail.n_k : nullptr;
   return rc;
+}
+
+// The slab term of a gather tail (mipme.h, slab = axis + 1; the caller has checked the range, one channel and 1/r)
+inline void tail_attach_slab(GatherTailHost& tail, const mipme_mesh_t* m, const mipme_potential_t* pot, int slab) {
+  const double* a = m->cell + 3 * (slab - 1);
+  tail.slab = slab;
+  tail.slab_c0 = pot->prefactor * 4.0 * 3.14159265358979323846 / m->volume;
+  tail.slab_L = std::sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
 }
 
 // The energy of a gather tail also goes to a log (mipme.h, energy_log): needs the log's cursor and a capacity the device's int

@@ -1617,11 +1617,19 @@ int kfilter_deriv_impl(hipStream_t st, const mipme_mesh_t* m, const mipme_potent
 // out: 27 reals: mesh part, pair part, their sum.  Column sums: 25 groups of 16 lanes (rider rows) and 9 groups of 32 lanes
 // (brick rows), sixteen loads in flight per lane -- a plain accumulation loop is a chain of dependent cold loads (the inputs
 // were written by other XCDs a moment ago): 6.7 us for this kernel --, then 18 threads for the 3x3 algebra.
-template <typename T>
+// SLAB: + the slab term of the step (GatherTail), which depends on the cell through V and L = |a_axis| alone (z is Cartesian):
+//   gA[a][b] += -s E_slab Ai[b][a] - [a == axis] s c0 Q^2 L / 12 * A[a][b] / L,   E_slab = c0/2 (M^2 - Q M2 - Q^2 L^2 / 12)
+struct SlabCell {
+  const double* mom;  // {Q, M, M2}
+  double c0, L;
+  int axis;
+};
+template <typename T, bool SLAB = false>
 __global__ __launch_bounds__(1024) void cell_tail_finalize_kernel(mipme_mesh_t m, double bg, double pair_scale, int n_rows,
                                                                  int n_bricks, const double* __restrict__ rows,
                                                                  const double* __restrict__ rpart, const T* __restrict__ dc,
-                                                                 const T* __restrict__ seed, T* __restrict__ out) {
+                                                                 const T* __restrict__ seed, T* __restrict__ out,
+                                                                 SlabCell sc) {
   __shared__ double gs[34], geo[18], s[31], res[18];
   {
     const int t = threadIdx.x;
@@ -1712,6 +1720,12 @@ __global__ __launch_bounds__(1024) void cell_tail_finalize_kernel(mipme_mesh_t m
       }
       const double norm = sqrt(A[3 * a] * A[3 * a] + A[3 * a + 1] * A[3 * a + 1] + A[3 * a + 2] * A[3 * a + 2]);
       v += dLdV * V * Ai[3 * b + a] + es * s[9 + a] / (norm * double(nsa)) * A[3 * a + b];
+      if constexpr (SLAB) {
+        const double sQ = sc.mom[0], sM = sc.mom[1], sM2 = sc.mom[2];
+        const double e_slab = 0.5 * sc.c0 * (sM * sM - sQ * sM2 - sQ * sQ * sc.L * sc.L / 12.0);
+        v -= sd * e_slab * Ai[3 * b + a];
+        if (a == sc.axis) v -= sd * sc.c0 * sQ * sQ / 12.0 * A[3 * a + b];
+      }
       out[threadIdx.x] = T(v);
       res[threadIdx.x] = v;
     } else {
@@ -1729,9 +1743,15 @@ __global__ __launch_bounds__(1024) void cell_tail_finalize_kernel(mipme_mesh_t m
 
 template <typename T>
 int cell_tail_finalize_impl(hipStream_t st, const mipme_mesh_t* m, double bg, double pair_scale, int64_t n_rows,
-                            int64_t n_bricks, const void* rows, const void* rpart, const void* dc, const void* seed, void* out) {
-  cell_tail_finalize_kernel<T><<<1, 1024, 0, st>>>(*m, bg, pair_scale, int(n_rows), int(n_bricks), (const double*)rows,
-                                                  (const double*)rpart, (const T*)dc, (const T*)seed, (T*)out);
+                            int64_t n_bricks, const void* rows, const void* rpart, const void* dc, const void* seed, void* out,
+                            const GatherTailHost* slab) {
+  if (slab && slab->slab)
+    cell_tail_finalize_kernel<T, true><<<1, 1024, 0, st>>>(*m, bg, pair_scale, int(n_rows), int(n_bricks), (const double*)rows,
+                                                          (const double*)rpart, (const T*)dc, (const T*)seed, (T*)out,
+                                                          SlabCell{slab->slab_mom, slab->slab_c0, slab->slab_L, slab->slab - 1});
+  else
+    cell_tail_finalize_kernel<T><<<1, 1024, 0, st>>>(*m, bg, pair_scale, int(n_rows), int(n_bricks), (const double*)rows,
+                                                    (const double*)rpart, (const T*)dc, (const T*)seed, (T*)out, SlabCell{});
   MIPME_LAUNCH_CHECK();
   return MIPME_OK;
 }
@@ -1739,9 +1759,9 @@ int cell_tail_finalize_impl(hipStream_t st, const mipme_mesh_t* m, double bg, do
 template int kfilter_deriv_impl<float>(hipStream_t, const mipme_mesh_t*, const mipme_potential_t*, void*);
 template int kfilter_deriv_impl<double>(hipStream_t, const mipme_mesh_t*, const mipme_potential_t*, void*);
 template int cell_tail_finalize_impl<float>(hipStream_t, const mipme_mesh_t*, double, double, int64_t, int64_t, const void*,
-                                            const void*, const void*, const void*, void*);
+                                            const void*, const void*, const void*, void*, const GatherTailHost*);
 template int cell_tail_finalize_impl<double>(hipStream_t, const mipme_mesh_t*, double, double, int64_t, int64_t, const void*,
-                                             const void*, const void*, const void*, void*);
+                                             const void*, const void*, const void*, void*, const GatherTailHost*);
 template int kfilter_build_impl<float>(hipStream_t, const mipme_mesh_t*, const mipme_potential_t*, void*);
 template int kfilter_build_impl<double>(hipStream_t, const mipme_mesh_t*, const mipme_potential_t*, void*);
 template int apply_filter_impl<float>(hipStream_t, int64_t, int, const void*, const void*, void*, void*);

@@ -409,7 +409,8 @@ __global__ __launch_bounds__(SPREAD_THREADS, sizeof(T) == 4 ? (CELL ? MIPME_CELL
 // kLiveMargin points outside the brick, so the halo tile is that much wider on every side; and the charge comes from the (x, y, z,
 // q) record.  (The first version evaluated the weights here, in each of the 8 lanes of an atom: 12.2 us against 7.4; now the spread,
 // which evaluates them anyway for its staging, leaves them in the bins for its home atoms.)
-template <int N, typename T>
+// SLAB: the 2-D periodic term in the same pass, as in gather_brick_body<SLAB> (bricks_device.h GatherTail).
+template <int N, typename T, bool SLAB = false>
 __global__ __launch_bounds__(GATHER_THREADS, (sizeof(T) == 4 && N <= 5) ? MIPME_GATHER_TAIL_WAVES : 1) void live_gather_tail_kernel(Geom g, BrickGeom bg, BinIndex bins,
                                                                          const int4* __restrict__ rec_now,
                                                                          const T* __restrict__ wts,
@@ -433,7 +434,18 @@ __global__ __launch_bounds__(GATHER_THREADS, (sizeof(T) == 4 && N <= 5) ? MIPME_
   T seed = T(1);
   if (tail.seed) seed = tail.seed[0];
   const T seed_aux = tail.aux_seed ? tail.aux_seed[0] : seed;
-  if (block == 0) tail_energy<T, THREADS>(tail, qsum, inv_vol, self_c, bg_c);  // uniform per workgroup
+  if (block == 0) tail_energy<T, THREADS, SLAB>(tail, qsum, inv_vol, self_c, bg_c);  // uniform per workgroup
+  // SLAB: the term's coefficients, uniform over the launch -- formed in double from the moments, used in the working type:
+  //   field += fA - fB z,   V += z (pA - pB z) + pK
+  T fA = T(0), fB = T(0), pA = T(0), pB = T(0), pK = T(0);
+  if constexpr (SLAB) {
+    const double sQ = tail.slab_mom[0], sM = tail.slab_mom[1], sM2 = tail.slab_mom[2], c0 = tail.slab_c0;
+    fA = T(c0 * sM);
+    fB = T(c0 * sQ);
+    pA = T(0.5 * c0 * sM);
+    pB = T(0.25 * c0 * sQ);
+    pK = T(-0.5 * c0 * (0.5 * sM2 + sQ * tail.slab_L * tail.slab_L / 12.0));
+  }
   double r3[3] = {0.0, 0.0, 0.0};
   if (beg == end && n_over == 0) {
     if (tail.rpart && threadIdx.x < 9) tail.rpart[9 * int64_t(block) + threadIdx.x] = 0.0;
@@ -516,10 +528,14 @@ __global__ __launch_bounds__(GATHER_THREADS, (sizeof(T) == 4 && N <= 5) ? MIPME_
     const T i0 = T(l == 1 ? g.inv[3] : (l == 2 ? g.inv[6] : g.inv[0])), i1 = T(l == 1 ? g.inv[4] : (l == 2 ? g.inv[7] : g.inv[1])),
             i2 = T(l == 1 ? g.inv[5] : (l == 2 ? g.inv[8] : g.inv[2]));
     const T fc = i0 * fx + i1 * fy + i2 * fz;
+    T fs = fc;  // SLAB: + the term's field along its axis (the cell sums below take the mesh part alone)
+    if constexpr (SLAB) {
+      if (l == tail.slab_axis) fs += fA - fB * slab_coord(r_early, tail.slab_axis);
+    }
     if (l < 3 && valid) {
       const int64_t o = int64_t(a.w);
-      if (field) field[3 * o + l] = fc;
-      tail.grad_pos[3 * o + l] = seed * q_early * (tail.force_scale * f_early + fc);
+      if (field) field[3 * o + l] = fs;
+      tail.grad_pos[3 * o + l] = seed * q_early * (tail.force_scale * f_early + fs);
       if (tail.rpart) {
         const double gp = double(seed_aux * q_early * fc);
         r3[0] += double(r_early.x) * gp;
@@ -530,7 +546,11 @@ __global__ __launch_bounds__(GATHER_THREADS, (sizeof(T) == 4 && N <= 5) ? MIPME_
     const T acc = group_sum_b<LANES, T>(sA * wzv);
     if (l == 0 && valid) {
       const T phi = acc * inv_vol;
-      const T lr = T(0.5) * (phi - self_c * q_early - T(2) * bg_c * inv_vol * qsum[0]);
+      T lr = T(0.5) * (phi - self_c * q_early - T(2) * bg_c * inv_vol * qsum[0]);
+      if constexpr (SLAB) {
+        const T z = slab_coord(r_early, tail.slab_axis);
+        lr += z * (pA - pB * z) + pK;
+      }
       out[a.w] = out_early + lr;
       if (tail.grad_q) tail.grad_q[a.w] = T(2) * seed_aux * (out_early + lr);
       if (nan_flag && lr != lr) *nan_flag = 1;
@@ -655,10 +675,18 @@ int live_gather(hipStream_t st, const mipme_mesh_t* m, int64_t N, const void* re
   // (the pair kernel's energy partial sums: pre-reduced by the x stage of the convolution)
   const GatherTail<T> tail =
       make_gather_tail<T>(*th, (const double*)th->epart_k + th->n_k, int(th->n_k), rec4, th->live_flags);
-  MIPME_DISPATCH_ORDER(m->order, (live_gather_tail_kernel<N, T><<<brick_grid(bg), GATHER_THREADS, 0, st>>>(
-                                     g, bg, v.idx, ll.rec_now, (const T*)v.wts, (const AtomRecord<T>*)rec4, (const T*)mesh,
-                                     (const T*)qsum, T(1.0 / m->volume), T(self_c), T(bg_c), (T*)out, (T*)field, tail,
-                                     (int*)nan_flag)));
+  if (th->slab) {  // the same kernel compiled with the slab term, so that the launch without it carries no branch for it
+    MIPME_REQUIRE(tail.slab_mom, "the slab term of the live gather needs the moments");
+    MIPME_DISPATCH_ORDER(m->order, (live_gather_tail_kernel<N, T, true><<<brick_grid(bg), GATHER_THREADS, 0, st>>>(
+                                       g, bg, v.idx, ll.rec_now, (const T*)v.wts, (const AtomRecord<T>*)rec4, (const T*)mesh,
+                                       (const T*)qsum, T(1.0 / m->volume), T(self_c), T(bg_c), (T*)out, (T*)field, tail,
+                                       (int*)nan_flag)));
+  } else {
+    MIPME_DISPATCH_ORDER(m->order, (live_gather_tail_kernel<N, T><<<brick_grid(bg), GATHER_THREADS, 0, st>>>(
+                                       g, bg, v.idx, ll.rec_now, (const T*)v.wts, (const AtomRecord<T>*)rec4, (const T*)mesh,
+                                       (const T*)qsum, T(1.0 / m->volume), T(self_c), T(bg_c), (T*)out, (T*)field, tail,
+                                       (int*)nan_flag)));
+  }
   MIPME_LAUNCH_CHECK();
   return MIPME_OK;
 }

@@ -35,8 +35,9 @@ class _LiveStep:
     every kernel of the step reads; the atom -> mesh-brick bookkeeping (bins, per-brick atom lists) is rebuilt only when the
     neighbour list is (``rebin``), while every weight is evaluated from the current positions in every step."""
 
-    def __init__(self, calculator, charges, cell, positions, charge_gradient=False, cell_gradient=False):
+    def __init__(self, calculator, charges, cell, positions, charge_gradient=False, cell_gradient=False, slab_axis=None):
         lib = self.lib = _lib.load()
+        self.slab = 0 if slab_axis is None else int(slab_axis) + 1  # mipme_md_args_t.slab
         device, dtype = positions.device, positions.dtype
         N = positions.shape[0]
         self.device, self.dtype, self.n_atoms = device, dtype, N
@@ -96,7 +97,7 @@ class _LiveStep:
             G_deriv=_lib.ptr(self.G_deriv), cell_work=_lib.ptr(self.cell_work), aux_seed=self.one.data_ptr(),
             energy_log=None if self.log is None else self.log.values.data_ptr(),
             energy_log_cursor=None if self.log is None else self.log.cursor.data_ptr(),
-            energy_log_capacity=0 if self.log is None else self.log.capacity)
+            energy_log_capacity=0 if self.log is None else self.log.capacity, slab=self.slab)
 
     def rebin(self):
         with _lib.on_device(self.device):
@@ -203,6 +204,13 @@ class GraphedEnergyForces:
         (cell-list binning + the walk that writes the rows): no list tensors, no sort, no re-capture of the step -- the MD form
         of the reference's "new list every call" (``examples/02-neighbor-lists-usage.py:97-164``).
     :param periodic: per-axis periodicity of the neighbour list made for ``neighbors=<cutoff>``
+    :param slab_correction: add the 2-D periodic (slab) term of the reference (``potentials/coulomb.py:6-40``) for the one axis
+        that ``periodic`` marks as not periodic: potentials, energy, forces, ``dE/dcharges`` and ``dE/dcell`` then describe a
+        system that repeats in the other two directions only.  The term rides in the gather launch of the step (one small
+        launch ahead of the spread forms the moments ``sum q z`` and ``sum q z^2``); the axis is fixed here, so a replay has no
+        host round trip.  ``periodic`` must have exactly two true entries and the potential must be 1/r.  The mesh part stays
+        periodic along that axis too: leaving a vacuum gap in the cell is the caller's business, as in the reference.  Off by
+        default -- ``periodic`` alone only shapes the neighbour list
     :param live_bins: (``neighbors=`` form) also keep the atom -> mesh-brick bookkeeping across steps and rebuild it in
         :meth:`refresh`, evaluating every mesh weight on the fly from the current positions (``mipme_md_step``: five launches
         per step instead of six, no per-step binning pass, no per-brick candidate scan).  Valid while no atom has moved more
@@ -222,9 +230,23 @@ class GraphedEnergyForces:
     def __init__(self, calculator, charges, cell, positions, neighbor_indices=None, neighbor_shifts=None, warmup: int = 3,
                  cell_gradient: bool = False, store_distances: bool = False, neighbors=None,
                  periodic=(True, True, True), live_bins: bool | None = None, charge_gradient: bool = False,
-                 energy_log=None, epilogue=None):
+                 energy_log=None, epilogue=None, slab_correction: bool = False):
         _refuse_spline(calculator, "GraphedEnergyForces" + (" (`neighbors=` included)" if neighbors is not None else ""))
         self.calc = calculator
+        self._slab_axis = self._periodic = None
+        if slab_correction:
+            flags = [bool(p) for p in periodic]
+            if len(flags) != 3 or sum(flags) != 2:
+                raise ValueError(f"`slab_correction` needs exactly two periodic axes, got periodic={tuple(flags)}")
+            desc = calculator.potential._descriptor()
+            if not (desc.kind == _lib.COULOMB or desc.exponent == 1):
+                raise ValueError("`slab_correction`: the slab term exists for 1/r only (CoulombPotential, or "
+                                 "InversePowerLawPotential(exponent=1))")
+            if calculator.potential.smearing is None:
+                raise ValueError("`slab_correction` belongs to the mesh part: the potential needs a smearing")
+            self._slab_axis = flags.index(False)
+            # the calculator looks the axis up per (tensor, version): the warm-up pays the one host copy, the capture none
+            self._periodic = torch.tensor(flags, dtype=torch.bool, device=positions.device)
         self.energy_log = _as_energy_log(energy_log, 1, positions.device)
         self._epilogue = epilogue
         self.store_distances = bool(store_distances)
@@ -255,7 +277,8 @@ class GraphedEnergyForces:
         if neighbors is not None and live_bins is not False and hasattr(calculator, "_kspace_setup") \
                 and calculator.potential.smearing is not None:
             try:
-                live = _LiveStep(calculator, self.q, self.cell, self.pos, self.charge_gradient, self.cell_gradient)
+                live = _LiveStep(calculator, self.q, self.cell, self.pos, self.charge_gradient, self.cell_gradient,
+                                 slab_axis=self._slab_axis)
                 live.rebin()  # trial: a very non-uniform system overflows the per-brick lists -> keep the binned step
                 torch.cuda.current_stream(device).synchronize()
                 live.check()
@@ -442,7 +465,10 @@ class GraphedEnergyForces:
         fused = self._fused_contract
         with ops.seed_promise(self._minus_one, charges=fused and self.charge_gradient, cell=fused and self.cell_gradient,
                               aux_seed=self._one, energy_log=log):
-            V = self.calc(self.q, self.cell, self.pos, self.pairs, d)
+            if self._periodic is None:
+                V = self.calc(self.q, self.cell, self.pos, self.pairs, d)
+            else:
+                V = self.calc(self.q, self.cell, self.pos, self.pairs, d, periodic=self._periodic)
         self._tail = getattr(V.grad_fn, "tail", None)
         E = ops.weighted_sum(V, self.q)
         E.backward(self._minus_one)

@@ -823,6 +823,28 @@ def _slab_axis(periodic_host):
     return p.index(False)
 
 
+_SLAB_AXES: "OrderedDict" = OrderedDict()
+
+
+def slab_axis_of(periodic):
+    """:func:`_slab_axis` of a ``periodic`` tensor, remembered per (tensor identity, version): the first call with a tensor
+    copies its three flags to the host -- a copy the host waits for --, every later call with the same, unchanged tensor
+    copies nothing (and so may run inside a stream capture).  An in-place change of the tensor bumps its version and is
+    looked at again."""
+    if periodic is None:
+        return None
+    key = id(periodic)
+    hit = _SLAB_AXES.get(key)
+    if hit is not None and hit[0]() is periodic and hit[1] == periodic._version:
+        return hit[2]
+    axis = _slab_axis(periodic.tolist())
+    _SLAB_AXES[key] = (weakref.ref(periodic), periodic._version, axis)
+    _SLAB_AXES.move_to_end(key)
+    while len(_SLAB_AXES) > 16:
+        _SLAB_AXES.popitem(last=False)
+    return axis
+
+
 class LazyPairGradient(torch.Tensor):
     """``dL/d(neighbor_distances)`` of a calculator call whose pair part ran in the fused distance + pair kernels.
 
@@ -1014,7 +1036,10 @@ class _PMEFunction(torch.autograd.Function):
                     if nbytes > 0:
                         bins = torch.empty((nbytes,), dtype=torch.uint8, device=device)
                 # speculative: the mesh force per unit gE q_a, formed by the same gather (see the backward's energy mode)
-                if ENERGY_FAST_PATH and bins is not None and Cn == 1 and ctx.needs_input_grad[2] and slab_axis is None:
+                # (a slab term: only the gather tail folds it into the field -- 1/r, one channel; decided below)
+                p_eff = 1 if pot_desc.kind == _lib.COULOMB else pot_desc.exponent
+                slab_fusable = slab_axis is None or (Cn == 1 and p_eff == 1)
+                if ENERGY_FAST_PATH and bins is not None and Cn == 1 and ctx.needs_input_grad[2] and slab_fusable:
                     field = torch.empty((N, 3), dtype=dtype, device=device)
                 # the binning pass can emit the (position, charge) records of the fused pair kernel for free
                 records_out = None
@@ -1023,7 +1048,6 @@ class _PMEFunction(torch.autograd.Function):
                 # co-scheduled pair sum: the spread launch also carries the row workgroups of the fused distance + pair kernel
                 # (mipme_sr_job_t); the gather then adds the mesh part to the potentials the pair sum wrote
                 ni = ctx.needs_input_grad
-                p_eff = 1 if pot_desc.kind == _lib.COULOMB else pot_desc.exponent
                 cosched = bool(COSCHEDULE and records_out is not None and mask is None and (fused["fmt"] & 0xFF) == 1 and N > 0)
                 # the 4-byte entry stream is read by the co-scheduled kernel only (mipme.h, shift_format 2): use it when the
                 # library will co-schedule -- force sums wanted, 1/r or 1/r^6 with a smearing and no exclusion radius
@@ -1040,8 +1064,7 @@ class _PMEFunction(torch.autograd.Function):
                 symmetric = (not full_list) or bool(topo is not None and topo.fmt_flags)
                 want_q, want_cell, aux_seed = TAIL_REQUEST
                 tail_q = bool(ni[0] or want_q) and symmetric
-                tail_cell = (bool(ni[1] or ni[12] or want_cell) and ent32 is not None and not write_dist and slab_axis is None
-                             and src_cell is not None)
+                tail_cell = (bool(ni[1] or ni[12] or want_cell) and ent32 is not None and not write_dist and src_cell is not None)
                 tail_ok = bool(
                     TAIL_FUSION and cosched and field is not None and fused["force"] is not None and ENERGY_FAST_PATH
                     and not ni[3] and (tail_q or not ni[0]) and (tail_cell or not (ni[1] or ni[12])) and rho_hat is None
@@ -1049,6 +1072,11 @@ class _PMEFunction(torch.autograd.Function):
                     and (not lazy or tail_q or tail_cell))  # (lazy distances: only for what the tail adds to this node)
                 if not tail_ok:
                     tail_q = tail_cell = False
+                # the slab term rides in the gather tail (mipme_kspace_forward_args_t.slab) or, for every other call, in the
+                # launches of its own behind the step -- and then without the speculative field, which would lack the term
+                slab_in_tail = slab_axis is not None and tail_ok
+                if slab_axis is not None and not tail_ok:
+                    field = None
                 if not tail_cell:
                     if want_pair_partials:
                         # the pair part's cell sums from the generic pair body (no co-scheduled launch with them)
@@ -1116,6 +1144,7 @@ class _PMEFunction(torch.autograd.Function):
                     energy_log=None if tail is None or "log" not in tail else tail["log"].values.data_ptr(),
                     energy_log_cursor=None if tail is None or "log" not in tail else tail["log"].cursor.data_ptr(),
                     energy_log_capacity=0 if tail is None or "log" not in tail else tail["log"].capacity,
+                    slab=slab_axis + 1 if slab_in_tail else 0,
                 )
                 _call("kspace_forward", lib.mipme_kspace_forward, C.byref(args))
                 if records_out is not None:
@@ -1124,7 +1153,7 @@ class _PMEFunction(torch.autograd.Function):
                     src.pending = False
                     if _BETS:
                         _ON_LOST.append(lambda src=src: setattr(src, "pending", True))
-                if slab_axis is not None:
+                if slab_axis is not None and not slab_in_tail:
                     moments = torch.empty((6 * Cn,), dtype=torch.float64, device=device)
                     _call(
                         "slab_forward", lib.mipme_slab_forward, st, dt, slab_axis, C.byref(md), pot_desc.prefactor, N,
@@ -1147,6 +1176,8 @@ class _PMEFunction(torch.autograd.Function):
         #: the pair part's gradient leaves through the neighbor_distances slot as a LazyPairGradient (see pme_potential)
         ctx.lazy = bool(lazy) and fused is not None
         ctx.geom, ctx.pot_desc, ctx.full_list, ctx.slab_axis = geom, pot_desc, full_list, slab_axis
+        #: the gather tail of the forward carries the slab term: potentials, energy, field and the tail's gradients include it
+        ctx.slab_in_tail = slab_in_tail = bool(geom is not None and slab_axis is not None and tail is not None)
         ctx.topo = topo
         ctx.fused = fused  # plain tensors made here, none of them an input or output of this node
         # E = weighted_sum(out, charges) can be differentiated without this node (see _EnergyDirectSum) when its gradient is
@@ -1156,7 +1187,7 @@ class _PMEFunction(torch.autograd.Function):
             tail["grad_cell"] is not None or not (ni[1] or ni[12]))
         ctx.energy_direct = bool(
             ENERGY_FAST_PATH and Cn == 1 and fused is not None and fused["force"] is not None and src_positions is positions
-            and (covered or not (ni[0] or ni[1] or ni[12])) and not ni[3] and slab_axis is None
+            and (covered or not (ni[0] or ni[1] or ni[12])) and not ni[3] and (slab_axis is None or slab_in_tail)
             and (geom is None or field is not None) and not lazy
         )
         ctx.src_cell_is_cell = src_cell is cell
@@ -1230,7 +1261,7 @@ class _PMEFunction(torch.autograd.Function):
                             break
                     if flag_np[0] == 1:
                         sr_scale = res[:1]
-            if sr_scale is not None and ctx.slab_axis is None:
+            if sr_scale is not None and (ctx.slab_axis is None or ctx.slab_in_tail):
                 gscale = sr_scale
             # what the forward's gather tail already holds for exactly this upstream gradient (mipme.h, out_grad_charges /
             # out_grad_cell): dE/dq = 2 V and dE/dcell (mesh part, pair part) per unit of the tail's seed
