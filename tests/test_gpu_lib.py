@@ -395,10 +395,12 @@ def test_scaled_match_verdicts(dtype, n):
     assert verdict(torch.zeros_like(q), False)[0] == 0
 
 
-def test_custom_kspace_kernel_runs_the_same_convolution():
-    """lib.KSpaceFilter with a user-defined lib.KSpaceKernel (reference lib/kspace_filter.py:7-35: the customisable filter):
-    tabulated from kernel_from_k_sq on generate_kvectors_for_mesh, it gives what the built-in potential's device-built table
-    gives, and what numpy's rfftn / irfftn give with the same table."""
+@pytest.mark.parametrize("scheme", ["pme", "p3m"])
+def test_custom_kspace_kernel_runs_the_same_convolution(scheme):
+    """lib.KSpaceFilter / P3MKSpaceFilter with a user-defined lib.KSpaceKernel (reference lib/kspace_filter.py:7-35: the
+    customisable filter): tabulated from kernel_from_k_sq on generate_kvectors_for_mesh -- times the influence function 1 / U^2
+    for P3M, 3 nodes (lib/kspace_filter.py:294-329) -- it gives what the built-in potential's device-built table gives, and what
+    numpy's rfftn / irfftn give with the same table."""
     from torchpme_amd import lib
 
     cell = torch.tensor([[9.0, 0, 0], [1.0, 10.0, 0], [0.5, -0.7, 11.0]], dtype=torch.float64, device="cuda")
@@ -410,10 +412,16 @@ def test_custom_kspace_kernel_runs_the_same_convolution():
             return pot.lr_from_k_sq(k_sq)
 
     mesh = torch.randn((2, *ns), dtype=torch.float64, device="cuda")
-    ref = lib.KSpaceFilter(cell, ns, pot)(mesh)
-    mine = lib.KSpaceFilter(cell, ns, Mine())(mesh)
+    def make(kernel):
+        return lib.KSpaceFilter(cell, ns, kernel) if scheme == "pme" else lib.P3MKSpaceFilter(cell, ns, 3, kernel)
+
+    ref = make(pot)(mesh)
+    mine = make(Mine())(mesh)
     assert float((ref - mine).abs().max()) <= 1e-10 * float(ref.abs().max())
     k = lib.generate_kvectors_for_mesh(cell, ns)
     G = pot.lr_from_k_sq((k * k).sum(-1)).cpu().numpy()
+    if scheme == "p3m":  # U^2 = prod_c sinc(k_c h_c / 2)^(2 * 3), h_c = |a_c| / n_c (np.sinc(x) = sin(pi x) / (pi x))
+        h = np.linalg.norm(cell.cpu().numpy(), axis=1) / np.array(ns)
+        G = G / np.prod(np.sinc(k.cpu().numpy() * h / (2 * np.pi)), axis=-1) ** 6
     want = np.fft.irfftn(np.fft.rfftn(mesh.cpu().numpy(), axes=(1, 2, 3)) * G, s=ns, axes=(1, 2, 3)) * np.prod(ns)
     assert np.abs(mine.cpu().numpy() - want).max() <= 1e-10 * np.abs(want).max()

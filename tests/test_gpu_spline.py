@@ -218,7 +218,7 @@ def test_filter_table_kernel_matches_the_tensor_expression(scheme, name, system)
     geom = analytic._geometry(calc, cell)
     if system == "ortho":
         assert tuple(geom.ns) == (16, 32, 32)
-    want = analytic.filter_table(calc, cell, geom.ns, geom)
+    want = analytic.filter_table(calc.potential, geom.scheme, geom.order, cell, geom.ns, geom)
     got = splines.build_filter(geom, pot._splines()[1], pot._prefactor_float(), F64, DEV)
     assert got.shape == want.shape == (geom.ns[0], geom.ns[1], geom.ns[2] // 2 + 1)
     scale = want.abs().max()
@@ -369,7 +369,8 @@ def test_subclass_with_short_range_part_reproduces_coulomb():
     calc_s, calc_c = tpa.P3MCalculator(spline_pot, **kw), tpa.P3MCalculator(coulomb, **kw)
     V_s, V_c = calc_s(q, cell, pos, idx, d), calc_c(q, cell, pos, idx, d)
     geom = analytic._geometry(calc_s, cell)
-    dG = (analytic.filter_table(calc_s, cell, geom.ns, geom) - analytic.filter_table(calc_c, cell, geom.ns, geom)).abs()
+    dG = (analytic.filter_table(calc_s.potential, geom.scheme, geom.order, cell, geom.ns, geom)
+          - analytic.filter_table(calc_c.potential, geom.scheme, geom.order, cell, geom.ns, geom)).abs()
     mu = analytic._multiplicity(geom, F64, DEV)
     bound = (dG * mu).sum() / torch.abs(torch.det(cell)) * q.abs().sum(dim=0)
     np.testing.assert_allclose(bound.cpu().numpy(), [0.871, 0.782], rtol=2e-3)  # the measured values of the docstring

@@ -100,10 +100,10 @@ def filter_section(reps):
         geom = analytic._geometry(calcs[0], cell)
         assert tuple(geom.ns) == (n, n, n), geom.ns
         a = combined.build_tables(geom, plan, torch.float64, dev)
-        b = torch.stack([analytic.filter_table(c, cell, geom.ns, geom) for c in calcs])
+        b = torch.stack([analytic.filter_table(c.potential, geom.scheme, geom.order, cell, geom.ns, geom) for c in calcs])
         err = float(((a - b).abs().amax(dim=(1, 2, 3)) / b.abs().amax(dim=(1, 2, 3))).max())
         ms_k = timed(lambda: combined.build_tables(geom, plan, torch.float64, dev), reps)
-        ms_t = timed(lambda: [analytic.filter_table(c, cell, geom.ns, geom) for c in calcs], reps)
+        ms_t = timed(lambda: [analytic.filter_table(c.potential, geom.scheme, geom.order, cell, geom.ns, geom) for c in calcs], reps)
         print(f"{n}^3: mipme_combined_kfilter_build {ms_k:8.3f} | analytic.filter_table per term (tensor ops) {ms_t:8.3f} | "
               f"rel. difference {err:.1e}", flush=True)
 

@@ -87,10 +87,10 @@ def filter_section(reps):
         assert tuple(geom.ns) == (n, n, n), geom.ns
         krn, pref = pot._splines()[1], pot._prefactor_float()
         a = splines.build_filter(geom, krn, pref, torch.float64, dev)
-        b = analytic.filter_table(calc, cell, geom.ns, geom)
+        b = analytic.filter_table(calc.potential, geom.scheme, geom.order, cell, geom.ns, geom)
         err = float((a - b).abs().max() / b.abs().max())
         ms_k = timed(lambda: splines.build_filter(geom, krn, pref, torch.float64, dev), reps)
-        ms_t = timed(lambda: analytic.filter_table(calc, cell, geom.ns, geom), reps)
+        ms_t = timed(lambda: analytic.filter_table(calc.potential, geom.scheme, geom.order, cell, geom.ns, geom), reps)
         print(f"{n}^3: mipme_spline_kfilter_build {ms_k:8.3f} | analytic.filter_table (tensor ops) {ms_t:8.3f} | rel. difference {err:.1e}",
               flush=True)
 

@@ -364,10 +364,11 @@ def _sinc_pi(y: torch.Tensor) -> torch.Tensor:
     return torch.where(small, series, torch.sin(ys) / ys)
 
 
-def filter_table(calculator, cell: torch.Tensor, ns, geom=None) -> torch.Tensor:
-    """G(k) on the rfft half grid as a differentiable function of the cell, in float64: ``kernel_from_k_sq(|k|^2)`` (PME,
+def filter_table(kernel, scheme, order, cell: torch.Tensor, ns, geom=None) -> torch.Tensor:
+    """G(k) on the rfft half grid as a differentiable function of the cell, in float64: ``kernel.kernel_from_k_sq(|k|^2)`` (PME,
     ``lib/kspace_filter.py:97-120``), divided by the squared Fourier transform of the charge assignment function for P3M
-    (mode 0: ``prod_d sinc(k_d h_d / 2 pi)^(2 n)`` with h_d = |a_d| / n_d, zero where that vanishes; ``:293-329,349-361``)."""
+    (mode 0: ``prod_d sinc(k_d h_d / 2 pi)^(2 n)`` with h_d = |a_d| / n_d and n = ``order``, zero where that vanishes;
+    ``:293-329,349-361``)."""
     from .calculators import _reciprocal_and_det
 
     c64 = cell.to(torch.float64)
@@ -386,15 +387,42 @@ def filter_table(calculator, cell: torch.Tensor, ns, geom=None) -> torch.Tensor:
         fz = _constant(geom, "fz", torch.float64, cell.device, lambda: freq(ns[2], True))
         recip = (2 * torch.pi) * _reciprocal_and_det(c64)[0]
         k = fx[:, None, None, None] * recip[0] + fy[None, :, None, None] * recip[1] + fz[None, None, :, None] * recip[2]
-    G = calculator.potential.kernel_from_k_sq((k * k).sum(dim=-1))
-    if calculator._scheme == _lib.P3M:
+    G = kernel.kernel_from_k_sq((k * k).sum(dim=-1))
+    if scheme == _lib.P3M:
         nst = (_mesh_sizes(geom, torch.float64, cell.device) if geom is not None else
                torch.tensor([float(n) for n in ns], dtype=torch.float64, device=cell.device))
         kh = k * (torch.linalg.norm(c64, dim=1) / nst)
-        U2 = torch.prod(_sinc_pi(0.5 * kh), dim=-1) ** (2 * calculator.interpolation_nodes)
+        U2 = torch.prod(_sinc_pi(0.5 * kh), dim=-1) ** (2 * order)
         dead = U2 == 0
         G = torch.where(dead, torch.zeros_like(G), G / torch.where(dead, torch.ones_like(U2), U2))
     return G
+
+
+def _own_spline_kernel(kernel) -> bool:
+    """Whether ``kernel`` is a spline potential whose filter is its own kernel spline (not a subclass that redefines it)."""
+    from .potentials import Potential, SplinePotential
+
+    return (isinstance(kernel, SplinePotential) and type(kernel).lr_from_k_sq is SplinePotential.lr_from_k_sq
+            and type(kernel).kernel_from_k_sq is Potential.kernel_from_k_sq)
+
+
+def constant_table(kernel, geom, cell: torch.Tensor, dtype, device) -> torch.Tensor:
+    """G(k) of ``kernel`` on the half grid of ``geom`` as a constant of ``cell``, in ``dtype``: the one place that knows which
+    device kernel tabulates which kernel object.  A served combination: its members' tables contracted with the weights as they
+    are now.  Anything without a device kernel (a combination the kernels do not serve, a subclass that redefines its filter,
+    a bare :class:`lib.KSpaceKernel`): :func:`filter_table` without a graph -- correct, and slower."""
+    from . import combined, splines
+
+    if _own_spline_kernel(kernel):
+        return splines.build_filter(geom, kernel._splines()[1], kernel._prefactor_float(), dtype, device)
+    comb = combined.plan(kernel)
+    if comb is not None:
+        tables = combined.build_tables(geom, comb, dtype, device)
+        return torch.tensordot(kernel.weights.detach().to(dtype=dtype, device=device), tables, dims=1).contiguous()
+    if getattr(kernel, "_kind", None) is not None:  # a potential with a C descriptor
+        return ops.build_filter(geom, kernel._descriptor(), dtype, device)
+    with torch.no_grad():
+        return filter_table(kernel, geom.scheme, geom.order, cell.detach(), geom.ns).to(dtype).contiguous()
 
 
 def potentials(calculator, charges, cell, positions, neighbor_indices, neighbor_distances, periodic=None, node_mask=None,
@@ -502,65 +530,51 @@ def _ewald_kspace(pot, charges, positions, kvectors) -> torch.Tensor:
     return acc
 
 
-def _geometry(calculator, cell):
-    """Mesh sizes need the cell on the host (as in the reference, ``lib/kvectors.py:5-21``): one copy per cell tensor and
-    version, remembered on the calculator -- a training loop over the same structure does not wait for the device every call."""
+def _per_cell(calculator, slot, cell, key, make):
+    """``make()`` once per (cell tensor, version, key), remembered on the calculator as ``(weakref, version, key, value)`` under
+    ``slot`` -- a training loop over the same structure builds nothing twice."""
     import weakref
 
-    c = calculator.__dict__.get("_analytic_geom")
-    key = (calculator.mesh_spacing, calculator._scheme, calculator.interpolation_nodes)
+    c = calculator.__dict__.get(slot)
     if c is not None and c[0]() is cell and c[1] == cell._version and c[2] == key:
         return c[3]
-    cell_host = cell.detach().to("cpu", torch.float64).numpy()
-    ns = ops.ns_mesh_from_cell(cell_host, calculator.mesh_spacing)
-    geom = ops.MeshGeometry(cell_host, ns, calculator._scheme, calculator.interpolation_nodes)
+    value = make()
     try:
-        calculator.__dict__["_analytic_geom"] = (weakref.ref(cell), cell._version, key, geom)
+        calculator.__dict__[slot] = (weakref.ref(cell), cell._version, key, value)
     except TypeError:  # (a tensor subclass without weak references: no cache)
         pass
-    return geom
+    return value
+
+
+def _geometry(calculator, cell):
+    """Mesh sizes need the cell on the host (as in the reference, ``lib/kvectors.py:5-21``): one copy per cell tensor and
+    version -- a training loop over the same structure does not wait for the device every call."""
+
+    def make():
+        cell_host = cell.detach().to("cpu", torch.float64).numpy()
+        ns = ops.ns_mesh_from_cell(cell_host, calculator.mesh_spacing)
+        return ops.MeshGeometry(cell_host, ns, calculator._scheme, calculator.interpolation_nodes)
+
+    key = (calculator.mesh_spacing, calculator._scheme, calculator.interpolation_nodes)
+    return _per_cell(calculator, "_analytic_geom", cell, key, make)
 
 
 def _spline_filter(calculator, pot, cell, geom, dtype):
-    """G(k) of a spline potential for a cell that needs no gradient, from ``mipme_spline_kfilter_build``: cached on the
-    calculator per (cell tensor, version, tables of the potential, prefactor, mesh key, dtype), as ``_kspace_setup`` does."""
-    import weakref
-
-    from . import splines
-
-    krn = pot._splines()[1]
-    pref = pot._prefactor_float()
-    key = (id(pot), pot._tables_version, pref, calculator.mesh_spacing, calculator._scheme, calculator.interpolation_nodes,
-           dtype, cell.device)
-    c = calculator.__dict__.get("_spline_G")
-    if c is not None and c[0]() is cell and c[1] == cell._version and c[2] == key:
-        return c[3]
-    G = splines.build_filter(geom, krn, pref, dtype, cell.device)
-    try:
-        calculator.__dict__["_spline_G"] = (weakref.ref(cell), cell._version, key, G)
-    except TypeError:  # (a tensor subclass without weak references: no cache)
-        pass
-    return G
+    """G(k) of a spline potential for a cell that needs no gradient (``mipme_spline_kfilter_build``), per tables of the
+    potential, prefactor, mesh key and dtype, as ``_kspace_setup`` does."""
+    key = (id(pot), pot._tables_version, pot._prefactor_float(), calculator.mesh_spacing, calculator._scheme,
+           calculator.interpolation_nodes, dtype, cell.device)
+    return _per_cell(calculator, "_spline_G", cell, key, lambda: constant_table(pot, geom, cell, dtype, cell.device))
 
 
 def _combined_tables(calculator, plan_, cell, geom, dtype):
-    """The members' filter tables G_t(k) of a combined potential for a cell that needs no gradient, from
-    ``mipme_combined_kfilter_build``: cached on the calculator per (cell tensor, version, member parameters, mesh key, dtype),
-    exactly as :func:`_spline_filter` does.  The weights are not part of the key: they are contracted with the tables per call."""
-    import weakref
-
+    """The members' filter tables G_t(k) of a combined potential for a cell that needs no gradient
+    (``mipme_combined_kfilter_build``), per member parameters, mesh key and dtype.  The weights are not part of the key: they are
+    contracted with the tables per call."""
     from . import combined
 
     key = (plan_.key, calculator.mesh_spacing, calculator._scheme, calculator.interpolation_nodes, dtype, cell.device)
-    c = calculator.__dict__.get("_combined_G")
-    if c is not None and c[0]() is cell and c[1] == cell._version and c[2] == key:
-        return c[3]
-    tables = combined.build_tables(geom, plan_, dtype, cell.device)
-    try:
-        calculator.__dict__["_combined_G"] = (weakref.ref(cell), cell._version, key, tables)
-    except TypeError:  # (a tensor subclass without weak references: no cache)
-        pass
-    return tables
+    return _per_cell(calculator, "_combined_G", cell, key, lambda: combined.build_tables(geom, plan_, dtype, cell.device))
 
 
 def _mesh_kspace(calculator, charges, cell, positions, inv_cell) -> torch.Tensor:
@@ -570,10 +584,6 @@ def _mesh_kspace(calculator, charges, cell, positions, inv_cell) -> torch.Tensor
     ns = geom.ns
     u = _mesh_sizes(geom, dtype, positions.device) * (positions @ inv_cell)
     pot = calculator.potential
-    from .potentials import Potential, SplinePotential
-
-    own_kernel = (isinstance(pot, SplinePotential) and type(pot).lr_from_k_sq is SplinePotential.lr_from_k_sq
-                  and type(pot).kernel_from_k_sq is Potential.kernel_from_k_sq)
     from . import combined
 
     comb = combined.plan(pot)
@@ -581,11 +591,11 @@ def _mesh_kspace(calculator, charges, cell, positions, inv_cell) -> torch.Tensor
         # G = sum_t w_t G_t: the tables are constants of this cell (cached), the contraction carries the weight gradient
         tables = _combined_tables(calculator, comb, cell, geom, dtype)
         G = (pot.weights.to(dtype=dtype, device=tables.device).reshape(-1, 1, 1, 1) * tables).sum(dim=0)  # tensordot(w, tables)
-    elif own_kernel and not (cell.requires_grad and torch.is_grad_enabled()):
+    elif _own_spline_kernel(pot) and not (cell.requires_grad and torch.is_grad_enabled()):
         G = _spline_filter(calculator, pot, cell, geom, dtype)  # a constant of this cell: built by its own kernel, cached
     else:  # (a spline potential: kernel_from_k_sq is the device node of splines.py, differentiable to any order in k^2; a
         # combined one: the weighted sum of the members' tensor lr_from_k_sq)
-        G = filter_table(calculator, cell, ns, geom).to(dtype)
+        G = filter_table(pot, calculator._scheme, calculator.interpolation_nodes, cell, ns, geom).to(dtype)
     zero = (0, 0, 0)
     rho = _Spread.apply(u, charges, geom, zero)
     phi = _Convolve.apply(rho, G, geom)

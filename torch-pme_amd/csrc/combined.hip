@@ -3,9 +3,9 @@
 //   combined_sr_kernel        the n-th derivative w.r.t. d of every term's pair function in ONE pass over the distances, written
 //                             per term (n_terms, n_points) or contracted with device-resident weights (n_points,).  What the
 //                             autograd node of combined.py is made of: its backward is the same kernel one order up
-//   combined_kfilter_kernel   G_t(k) of every term on the rfft half grid, (n_terms, nx, ny, nz/2+1): the k-vector and the P3M factor
-//                             1 / U^2 once per point (kvector_dev of kpot.h, which kfilter.hip's eval_point calls too, and that
-//                             function's sinc product), lr_kernel_dev of kpot.h once per term
+//   combined_kfilter_kernel   G_t(k) of every term on the rfft half grid, (n_terms, nx, ny, nz/2+1): |k|^2 and the P3M factor
+//                             1 / U^2 once per point (kgrid_point of kgrid.h, as in kfilter.hip and spline.hip),
+//                             lr_kernel_dev of kpot.h once per term
 //
 // Pair function of a term, x = d^2 / 2 sigma^2:   v = pref Q(p/2, x) / d^p  (range separated)   or   v = pref / d^p  (direct).
 // With A = 2 x^(p/2) e^-x / Gamma(p/2) = 2 x dens(x)  (dQ/dx = -dens, dA/dx = A (p / 2x - 1))  and  (p)_n = p (p+1) ... (p+n-1):
@@ -21,6 +21,7 @@
 #include <cmath>
 
 #include "host.h"
+#include "kgrid.h"
 #include "kpot.h"
 #include "srpot.h"
 
@@ -118,62 +119,29 @@ __global__ __launch_bounds__(kCombBlock) void combined_sr_kernel(CombTerms c, in
   }
 }
 
-// ---- G_t(k): the geometry of kfilter.hip's eval_point<false>, then one lr_kernel_dev per term
-struct CombKGeom {
-  double inv[9];  // inverse cell
-  double h[3];    // |a_c| / n_c
-  int nx, ny, nzh;
-  int scheme, order;
-};
-
+// ---- G_t(k): one lr_kernel_dev per term at every point of the half grid
 struct CombKPots {
   int n_terms;
   KPot kp[MIPME_COMBINED_MAX_TERMS];
 };
 
 template <typename T>
-__global__ __launch_bounds__(kCombBlock) void combined_kfilter_kernel(CombKGeom g, CombKPots c, T* __restrict__ G) {
+__global__ __launch_bounds__(kCombBlock) void combined_kfilter_kernel(KGeom g, CombKPots c, T* __restrict__ G) {
   const int64_t Mh = int64_t(g.nx) * g.ny * g.nzh;
   const int64_t stride = int64_t(gridDim.x) * blockDim.x;
   for (int64_t pt = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; pt < Mh; pt += stride) {
-    const int iz = int(pt % g.nzh);
-    const int64_t r = pt / g.nzh;
-    const int iy = int(r % g.ny);
-    const int ix = int(r / g.ny);
-    const int f[3] = {ix < (g.nx + 1) / 2 ? ix : ix - g.nx, iy < (g.ny + 1) / 2 ? iy : iy - g.ny, iz};
-    double k[3];
-    const double k2 = kvector_dev(g.inv, f, k);  // (shared with kfilter.hip's eval_point: the same bits by construction)
-    double inv = 1.0;  // 1 / U^2; 0 where U^2 = 0 (G = 0 there)
-    bool dead = false;
-    if (g.scheme == MIPME_P3M) {
-      double s = 1.0;
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        const double ta = 0.5 * k[a] * g.h[a];
-        s *= (ta == 0.0) ? 1.0 : sin(ta) / ta;
-      }
-      double U2 = 1.0;
-      const double s2 = s * s;
-      for (int i = 0; i < g.order; ++i) U2 *= s2;
-      dead = U2 == 0.0;
-      inv = dead ? 0.0 : 1.0 / U2;
-    }
+    double inv;
+    bool dead;
+    const double k2 = kgrid_point(g, pt, inv, dead);
     for (int t = 0; t < c.n_terms; ++t) {
       double v, dv;
       lr_kernel_dev(c.kp[t], k2, v, dv);
-      if (g.scheme == MIPME_P3M) v = dead ? 0.0 : v * inv;
-      G[int64_t(t) * Mh + pt] = T(v);
+      G[int64_t(t) * Mh + pt] = T(dead ? 0.0 : v * inv);
     }
   }
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------
-static unsigned combined_grid(int64_t n) {
-  // one pass of 256-thread blocks up to 8 per CU of a 256-CU device, grid-stride beyond (spline_grid of spline.hip)
-  const int64_t blocks = (n + kCombBlock - 1) / kCombBlock;
-  return unsigned(std::max<int64_t>(1, std::min<int64_t>(blocks, 2048)));
-}
-
 static int exponent_of(const mipme_potential_t& t) { return t.kind == MIPME_COULOMB ? 1 : t.exponent; }
 
 // what both entry points refuse; *smeared: whether the combination is range separated (set by its first term)
@@ -201,7 +169,7 @@ template <typename T>
 static int combined_sr_impl(hipStream_t st, const CombTerms& c, bool smeared, int64_t n, const void* d, const void* w, void* out) {
   const T *dp = (const T*)d, *wp = (const T*)w;
   T* op = (T*)out;
-  const unsigned grid = combined_grid(n);
+  const unsigned grid = stride_grid(n, kCombBlock);
   if (smeared) {
     if (wp)
       combined_sr_kernel<T, true, true><<<grid, kCombBlock, 0, st>>>(c, n, dp, wp, op);
@@ -219,20 +187,9 @@ static int combined_sr_impl(hipStream_t st, const CombTerms& c, bool smeared, in
 
 template <typename T>
 static int combined_kfilter_impl(hipStream_t st, const mipme_mesh_t* m, const CombKPots& c, void* G) {
-  CombKGeom g;
-  for (int i = 0; i < 9; ++i) g.inv[i] = m->inv_cell[i];
-  const int ns[3] = {m->nx, m->ny, m->nz};
-  for (int a = 0; a < 3; ++a) {
-    const double* v = m->cell + 3 * a;
-    g.h[a] = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]) / double(ns[a]);
-  }
-  g.nx = m->nx;
-  g.ny = m->ny;
-  g.nzh = m->nz / 2 + 1;
-  g.scheme = m->scheme;
-  g.order = m->order;
+  const KGeom g = make_kgeom(m);
   const int64_t Mh = int64_t(g.nx) * g.ny * g.nzh;
-  combined_kfilter_kernel<T><<<combined_grid(Mh), kCombBlock, 0, st>>>(g, c, (T*)G);
+  combined_kfilter_kernel<T><<<stride_grid(Mh, kCombBlock), kCombBlock, 0, st>>>(g, c, (T*)G);
   MIPME_LAUNCH_CHECK();
   return MIPME_OK;
 }
@@ -278,9 +235,7 @@ int mipme_combined_kfilter_build(void* stream, int dtype, const mipme_mesh_t* me
   bool smeared = true;
   int rc = check_combined(comb, "mipme_combined_kfilter_build", true, &smeared);
   if (rc) return rc;
-  MIPME_REQUIRE(mesh != nullptr && mesh->nx > 0 && mesh->ny > 0 && mesh->nz > 0, "mipme_combined_kfilter_build: invalid mesh");
-  MIPME_REQUIRE(mesh->scheme == MIPME_LAGRANGE || (mesh->scheme == MIPME_P3M && mesh->order >= 1 && mesh->order <= 5),
-                "`interpolation_nodes` is %d but only values from 1 to 5 for method 'P3M' are allowed", int(mesh->order));
+  if ((rc = validate_mesh(mesh))) return rc;
   MIPME_REQUIRE(out != nullptr, "mipme_combined_kfilter_build: NULL pointer");
   CombKPots c;
   c.n_terms = comb->n_terms;

@@ -24,6 +24,11 @@ constexpr int dtype_of() {
     return MIPME_EINVAL;                                        \
   } while (0)
 
+// grid of a grid-stride kernel over n items: one pass of `block`-thread blocks up to 8 per CU of a 256-CU device (block = 256)
+inline unsigned stride_grid(int64_t n, int block) {
+  return unsigned(std::max<int64_t>(1, std::min<int64_t>((n + block - 1) / block, 2048)));
+}
+
 // ---- mesh.hip: particle <-> mesh without bins -------------------------------------------------------------------------------
 template <typename T> int spread_impl(hipStream_t st, const mipme_mesh_t* m, int64_t n_atoms, const void* pos, const void* val, double scale,
                                       void* mesh);

@@ -5,7 +5,8 @@
 // (lib/kspace_filter.py:97-197), P3MKSpaceFilter.update/_compute_influence/_charge_assignment
 // (lib/kspace_filter.py:293-329,349-361) and Potential.lr_from_k_sq (potentials/coulomb.py:122-142,
 // potentials/inversepowerlaw.py:109-141, lib/math.py:85-104).  The reference materialises the
-// (nx,ny,nz/2+1,3) k-vector grid and k^2; here every thread derives its k-vector from its index.
+// (nx,ny,nz/2+1,3) k-vector grid and k^2; here every thread derives its k-vector from its index (kgrid.h: the one
+// index -> k, |k|^2, 1/U^2 of this file's tables and of those of spline.hip and combined.hip).
 #include <hipfft/hipfft.h>
 
 #include <cmath>
@@ -13,38 +14,12 @@
 #include <new>
 
 #include "host.h"
+#include "kgrid.h"
 #include "kpot.h"
 #include "fft_lds.h"
 #include "bricks_device.h"  // slot_rider_dispatch: the slot riders of the inverse (y,z) plane launch
 
 namespace mipme {
-
-struct KGeom {
-  double inv[9];  // inverse cell
-  double h[3];    // |a_c| / n_c (P3M charge-assignment spacing, kspace_filter.py:308-311)
-  int nx, ny, nz, nzh;
-  int scheme, order;
-};
-
-
-static inline KGeom make_kgeom(const mipme_mesh_t* m) {
-  KGeom g;
-  for (int i = 0; i < 9; ++i) g.inv[i] = m->inv_cell[i];
-  const int ns[3] = {m->nx, m->ny, m->nz};
-  for (int c = 0; c < 3; ++c) {
-    const double* a = m->cell + 3 * c;
-    g.h[c] = std::sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]) / double(ns[c]);
-  }
-  g.nx = m->nx;
-  g.ny = m->ny;
-  g.nz = m->nz;
-  g.nzh = m->nz / 2 + 1;
-  g.scheme = m->scheme;
-  g.order = m->order;
-  return g;
-}
-
-__device__ inline int fft_freq(int i, int n) { return i < (n + 1) / 2 ? i : i - n; }
 
 struct KPoint {
   double k[3];
@@ -54,7 +29,8 @@ struct KPoint {
   double alpha, beta[3];
 };
 
-template <bool DERIV>
+// Filter value and derivatives at the k-point (ix, iy, iz): the cell gradient's k-grid sums and the derivative table.  (The
+// table G itself needs none of the derivatives: kfilter_kernel, from kgrid_point of kgrid.h.)
 __device__ inline void eval_point(const KGeom& g, const KPot& kp, int ix, int iy, int iz, KPoint& o) {
   o.f[0] = fft_freq(ix, g.nx);
   o.f[1] = fft_freq(iy, g.ny);
@@ -64,29 +40,23 @@ __device__ inline void eval_point(const KGeom& g, const KPot& kp, int ix, int iy
   lr_kernel_dev(kp, k2, v, dv);
   if (g.scheme == MIPME_LAGRANGE) {
     o.G = v;
-    if constexpr (DERIV) {
-      o.alpha = 2.0 * dv;
+    o.alpha = 2.0 * dv;
 #pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        o.dGdk[c] = 2.0 * o.k[c] * dv;
-        o.dGdh[c] = 0.0;
-        o.beta[c] = 0.0;
-      }
+    for (int c = 0; c < 3; ++c) {
+      o.dGdk[c] = 2.0 * o.k[c] * dv;
+      o.dGdh[c] = 0.0;
+      o.beta[c] = 0.0;
     }
     return;
   }
-  // (one sincos per axis when the derivatives are wanted: the double-precision sin / cos of libm are ~250 instructions each, and
-  // the cell-gradient sums of the x stage evaluate this for every k-point of the half grid -- most of that kernel's extra 19 us)
+  // the sinc product of p3m_inv_u2 (kgrid.h) with ONE sincos per axis, the cosine being wanted too: the double-precision sin / cos
+  // of libm are ~250 instructions each, and the cell-gradient sums of the x stage evaluate this for every k-point of the half
+  // grid -- most of that kernel's extra 19 us
   double s = 1.0, t[3], sn[3], cs[3];
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
     t[c] = 0.5 * o.k[c] * g.h[c];
-    if constexpr (DERIV) {
-      sincos(t[c], &sn[c], &cs[c]);
-    } else {
-      sn[c] = sin(t[c]);
-      cs[c] = 0.0;
-    }
+    sincos(t[c], &sn[c], &cs[c]);
     s *= (t[c] == 0.0) ? 1.0 : sn[c] / t[c];
   }
   double U2 = 1.0;
@@ -94,27 +64,23 @@ __device__ inline void eval_point(const KGeom& g, const KPot& kp, int ix, int iy
   for (int i = 0; i < g.order; ++i) U2 *= s2;
   if (U2 == 0.0) {
     o.G = 0.0;
-    if constexpr (DERIV) {
-      o.alpha = 0.0;
+    o.alpha = 0.0;
 #pragma unroll
-      for (int c = 0; c < 3; ++c) o.dGdk[c] = o.dGdh[c] = o.beta[c] = 0.0;
-    }
+    for (int c = 0; c < 3; ++c) o.dGdk[c] = o.dGdh[c] = o.beta[c] = 0.0;
     return;
   }
   const double inv = 1.0 / U2;
   o.G = v * inv;
-  if constexpr (DERIV) {
-    o.alpha = 2.0 * dv * inv;
+  o.alpha = 2.0 * dv * inv;
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const double tc = t[c];
-      // d/dt ln(sin t / t) = cot t - 1/t
-      const double L = fabs(tc) < 1e-4 ? (-tc / 3.0 - tc * tc * tc / 45.0) : (cs[c] / sn[c] - 1.0 / tc);
-      const double w = o.G * double(2 * g.order) * L;
-      o.dGdk[c] = 2.0 * o.k[c] * dv * inv - w * 0.5 * g.h[c];
-      o.dGdh[c] = -w * 0.5 * o.k[c];
-      o.beta[c] = 0.5 * w;
-    }
+  for (int c = 0; c < 3; ++c) {
+    const double tc = t[c];
+    // d/dt ln(sin t / t) = cot t - 1/t
+    const double L = fabs(tc) < 1e-4 ? (-tc / 3.0 - tc * tc * tc / 45.0) : (cs[c] / sn[c] - 1.0 / tc);
+    const double w = o.G * double(2 * g.order) * L;
+    o.dGdk[c] = 2.0 * o.k[c] * dv * inv - w * 0.5 * g.h[c];
+    o.dGdh[c] = -w * 0.5 * o.k[c];
+    o.beta[c] = 0.5 * w;
   }
 }
 
@@ -123,13 +89,11 @@ __global__ __launch_bounds__(256) void kfilter_kernel(KGeom g, KPot kp, T* __res
   const int64_t Mh = int64_t(g.nx) * g.ny * g.nzh;
   const int64_t t = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
   if (t >= Mh) return;
-  const int iz = int(t % g.nzh);
-  const int64_t r = t / g.nzh;
-  const int iy = int(r % g.ny);
-  const int ix = int(r / g.ny);
-  KPoint o;
-  eval_point<false>(g, kp, ix, iy, iz, o);
-  G[t] = T(o.G);
+  double inv, v, dv;
+  bool dead;
+  const double k2 = kgrid_point(g, t, inv, dead);
+  lr_kernel_dev(kp, k2, v, dv);
+  G[t] = T(dead ? 0.0 : v * inv);
 }
 
 // Derivative table of the filter, 4 reals per half-grid point {alpha, beta_x, beta_y, beta_z}:
@@ -143,12 +107,10 @@ __global__ __launch_bounds__(256) void kfilter_deriv_kernel(KGeom g, KPot kp, T*
   const int64_t Mh = int64_t(g.nx) * g.ny * g.nzh;
   const int64_t t = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
   if (t >= Mh) return;
-  const int iz = int(t % g.nzh);
-  const int64_t r = t / g.nzh;
-  const int iy = int(r % g.ny);
-  const int ix = int(r / g.ny);
+  int ix, iy, iz;
+  half_grid_index(g, t, ix, iy, iz);
   KPoint o;
-  eval_point<true>(g, kp, ix, iy, iz, o);
+  eval_point(g, kp, ix, iy, iz, o);
   D[4 * t + 0] = T(o.alpha);
   D[4 * t + 1] = T(o.beta[0]);
   D[4 * t + 2] = T(o.beta[1]);
@@ -189,10 +151,8 @@ __global__ __launch_bounds__(256) void apply_filter_cellgrad_kernel(KGeom g, KPo
 #pragma unroll
   for (int i = 0; i < 12; ++i) acc[i] = 0.0;
   if (t < Mh) {
-    const int iz = int(t % g.nzh);
-    const int64_t r = t / g.nzh;
-    const int iy = int(r % g.ny);
-    const int ix = int(r / g.ny);
+    int ix, iy, iz;
+    half_grid_index(g, t, ix, iy, iz);
     const T gk = G[t];
     double dLdG = 0.0;
     for (int c = 0; c < C; ++c) {
@@ -208,7 +168,7 @@ __global__ __launch_bounds__(256) void apply_filter_cellgrad_kernel(KGeom g, KPo
     const bool edge = (iz == 0) || ((g.nz % 2 == 0) && (iz == g.nz / 2));
     dLdG *= edge ? 1.0 : 2.0;
     KPoint p;
-    eval_point<true>(g, kp, ix, iy, iz, p);
+    eval_point(g, kp, ix, iy, iz, p);
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
 #pragma unroll
@@ -799,7 +759,7 @@ static int yz_planes(mipme_fft_plan* p, hipStream_t st, bool inverse, const void
 #endif
 static constexpr int kXPad = MIPME_X_PAD;  // elements of padding per LDS row of the x stage
 // CELLSUMS: 0 = none; 1 = the 12 k-grid sums of the cell gradient with the filter's derivatives evaluated in place (double
-// precision, eval_point<true>), one 12-value row per tile (general autograd nodes).
+// precision, eval_point), one 12-value row per tile (general autograd nodes).
 // The ENERGY STEP's cell gradient takes nothing but one store per k-point from this kernel: wbuf (nullable) receives
 // w = mu |rho^|^2 on the half grid, and the sums against the filter's derivative table are formed by rider workgroups of the
 // NEXT launch (cell_rider_body below) -- the x stage is one tile per CU at 64^3, a chain of latencies, and whatever is put on
@@ -951,7 +911,7 @@ __device__ __forceinline__ void xconv_tile_body(int nx, int ny, int nzh, int log
         const bool edge = (iz == 0) || ((kg.nz % 2 == 0) && (iz == kg.nz / 2));
         const double dLdG = (double(v.re) * double(v.re) + double(v.im) * double(v.im)) * (edge ? 1.0 : 2.0);
         KPoint p;
-        eval_point<true>(kg, kp, kx, ky, iz, p);
+        eval_point(kg, kp, kx, ky, iz, p);
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
 #pragma unroll
@@ -1117,7 +1077,7 @@ static int convolve_xfused_t(mipme_fft_plan* p, hipStream_t st, const void* mesh
   int threads = (p->nx >> 2) << kzs;  // one 4-point group per thread and pass
   threads = threads < 64 ? 64 : (threads > 256 ? 256 : threads);
   // with the cell sums evaluated in place every element of the tile costs ~700 double-precision instructions
-  // (eval_point<true>): at 64^3 that was four elements per thread in ONE wave per SIMD, a serial stream with nothing to overlap
+  // (eval_point): at 64^3 that was four elements per thread in ONE wave per SIMD, a serial stream with nothing to overlap
   // its latencies -- 256 threads (0.1217 -> 0.1170 ms for energy + forces + dE/dcell as a graph; 512 threads with launch bounds
   // to match: 0.1252).  The energy step (cc) leaves them to the riders of the next launch.
   if (cell_partials) threads = 256;

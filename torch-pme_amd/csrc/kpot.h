@@ -72,15 +72,4 @@ __device__ inline void lr_kernel_dev(const KPot& kp, double k2, double& v, doubl
   dv_dk2 = kp.c0 * (-(ez + kp.a * f) / z) * kp.hs2;
 }
 
-// k = 2 pi A^-T f for the integer frequencies f (inv: the inverse cell, row major) into k[3]; returns |k|^2.  The multiply-adds
-// are written out, not left to the compiler's contraction: every kernel that tabulates a filter calls this, so their tables
-// agree bit for bit whatever gets fused around the call.
-__device__ __forceinline__ double kvector_dev(const double* inv, const int* f, double* k) {
-#pragma unroll
-  for (int c = 0; c < 3; ++c)
-    k[c] = 2.0 * kPi * __builtin_fma(double(f[2]), inv[3 * c + 2],
-                                     __builtin_fma(double(f[1]), inv[3 * c + 1], double(f[0]) * inv[3 * c + 0]));
-  return __builtin_fma(k[2], k[2], __builtin_fma(k[0], k[0], k[1] * k[1]));
-}
-
 }  // namespace mipme

@@ -5,8 +5,9 @@
 //                             what the backward passes of the autograd node in splines.py are made of)
 //   spline_recip_kernel       x < x0 ? Z(x) : R(1/x) and its first derivative in one pass (CubicSplineReciprocal.forward:
 //                             a searchsorted, ten gathers and two where() over the list in the reference)
-//   spline_kfilter_kernel     G(k) = prefactor * spline(|k|^2) [/ U^2(k)] on the rfft half grid, the k-vector derived from the
-//                             index as in kfilter.hip (KSpaceFilter.update / P3MKSpaceFilter.update with a spline kernel)
+//   spline_kfilter_kernel     G(k) = prefactor * spline(|k|^2) [/ U^2(k)] on the rfft half grid; |k|^2 and 1 / U^2 from the index by
+//                             kgrid_point of kgrid.h, as in kfilter.hip and combined.hip (KSpaceFilter.update /
+//                             P3MKSpaceFilter.update with a spline kernel)
 //
 // One thread per argument, grid-stride.  The spline is evaluated in double precision whatever the argument's type; the result
 // is stored in the argument's type.  A table of up to kLdsKnots knots is staged in LDS (3 arrays of doubles; 2048 knots are
@@ -16,12 +17,12 @@
 #include <cmath>
 
 #include "host.h"
+#include "kgrid.h"
 
 namespace mipme {
 
 constexpr int kLdsKnots = 2048;
 constexpr int kSplineBlock = 256;
-constexpr double kSplinePi = 3.14159265358979323846;
 
 struct SplineTab {
   const double* x;
@@ -155,16 +156,9 @@ __global__ __launch_bounds__(kSplineBlock) void spline_recip_kernel(SplineTab t,
   }
 }
 
-// ---- G(k) from a spline in k^2: the geometry of kfilter.hip's eval_point (a copy: that file's device code stays as it is)
-struct SplineKGeom {
-  double inv[9];  // inverse cell
-  double h[3];    // |a_c| / n_c
-  int nx, ny, nzh;
-  int scheme, order;
-};
-
+// ---- G(k) from a spline in k^2
 template <typename T, bool RECIP, bool LDS>
-__global__ __launch_bounds__(kSplineBlock) void spline_kfilter_kernel(SplineKGeom g, SplineTab t, ZeroCubic z, double prefactor,
+__global__ __launch_bounds__(kSplineBlock) void spline_kfilter_kernel(KGeom g, SplineTab t, ZeroCubic z, double prefactor,
                                                                      T* __restrict__ G) {
   extern __shared__ double spline_lds[];
   const double *xk, *yk, *dk;
@@ -172,36 +166,16 @@ __global__ __launch_bounds__(kSplineBlock) void spline_kfilter_kernel(SplineKGeo
   const int64_t Mh = int64_t(g.nx) * g.ny * g.nzh;
   const int64_t stride = int64_t(gridDim.x) * blockDim.x;
   for (int64_t p = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; p < Mh; p += stride) {
-    const int iz = int(p % g.nzh);
-    const int64_t r = p / g.nzh;
-    const int iy = int(r % g.ny);
-    const int ix = int(r / g.ny);
-    const int f[3] = {ix < (g.nx + 1) / 2 ? ix : ix - g.nx, iy < (g.ny + 1) / 2 ? iy : iy - g.ny, iz};
-    double k[3], k2 = 0.0;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      k[c] = 2.0 * kSplinePi * (f[0] * g.inv[3 * c + 0] + f[1] * g.inv[3 * c + 1] + f[2] * g.inv[3 * c + 2]);
-      k2 += k[c] * k[c];
-    }
+    double inv;
+    bool dead;
+    const double k2 = kgrid_point(g, p, inv, dead);
     double v, unused = 0.0;
     if constexpr (RECIP)
       recip_at<false>(t, z, xk, yk, dk, k2, v, unused);
     else
       v = spline_at<0>(t, xk, yk, dk, k2);
     v *= prefactor;
-    if (g.scheme == MIPME_P3M) {  // G / U^2, U^2 = prod_c sinc(k_c h_c / 2)^(2 order); G = 0 where U^2 = 0
-      double s = 1.0;
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        const double tc = 0.5 * k[c] * g.h[c];
-        s *= (tc == 0.0) ? 1.0 : sin(tc) / tc;
-      }
-      const double s2 = s * s;
-      double U2 = 1.0;
-      for (int i = 0; i < g.order; ++i) U2 *= s2;
-      v = (U2 == 0.0) ? 0.0 : v / U2;
-    }
-    G[p] = T(v);
+    G[p] = T(dead ? 0.0 : v * inv);
   }
 }
 
@@ -222,12 +196,6 @@ static int make_tab(const mipme_spline_t* sp, const char* who, SplineTab& t, Zer
   return MIPME_OK;
 }
 
-static unsigned spline_grid(int64_t n) {
-  // one pass of 256-thread blocks up to 8 per CU of a 256-CU device, grid-stride beyond
-  const int64_t blocks = (n + kSplineBlock - 1) / kSplineBlock;
-  return unsigned(std::max<int64_t>(1, std::min<int64_t>(blocks, 2048)));
-}
-
 template <typename T>
 static int spline_eval_impl(hipStream_t st, const SplineTab& t, int order, int64_t n, const void* x, void* out) {
   const T* xp = (const T*)x;
@@ -235,9 +203,9 @@ static int spline_eval_impl(hipStream_t st, const SplineTab& t, int order, int64
 #define SPLINE_EVAL_CASE(M)                                                                                            \
   case M:                                                                                                              \
     if (t.n <= kLdsKnots)                                                                                              \
-      spline_eval_kernel<T, M, true><<<spline_grid(n), kSplineBlock, size_t(3) * sizeof(double) * size_t(t.n), st>>>(t, n, xp, op); \
+      spline_eval_kernel<T, M, true><<<stride_grid(n, kSplineBlock), kSplineBlock, size_t(3) * sizeof(double) * size_t(t.n), st>>>(t, n, xp, op); \
     else                                                                                                               \
-      spline_eval_kernel<T, M, false><<<spline_grid(n), kSplineBlock, 0, st>>>(t, n, xp, op);                           \
+      spline_eval_kernel<T, M, false><<<stride_grid(n, kSplineBlock), kSplineBlock, 0, st>>>(t, n, xp, op);                           \
     break;
   switch (order) {
     SPLINE_EVAL_CASE(0)
@@ -255,7 +223,7 @@ static int spline_recip_impl(hipStream_t st, const SplineTab& t, const ZeroCubic
   const T* xp = (const T*)x;
   T *op = (T*)out, *dp = (T*)dout;
   const size_t lds = size_t(3) * sizeof(double) * size_t(t.n);
-  const unsigned grid = spline_grid(n);
+  const unsigned grid = stride_grid(n, kSplineBlock);
   if (t.n <= kLdsKnots) {
     if (dp)
       spline_recip_kernel<T, true, true><<<grid, kSplineBlock, lds, st>>>(t, z, n, xp, op, dp);
@@ -274,21 +242,10 @@ static int spline_recip_impl(hipStream_t st, const SplineTab& t, const ZeroCubic
 template <typename T>
 static int spline_kfilter_impl(hipStream_t st, const mipme_mesh_t* m, const SplineTab& t, const ZeroCubic& z, bool recip,
                                double prefactor, void* G) {
-  SplineKGeom g;
-  for (int i = 0; i < 9; ++i) g.inv[i] = m->inv_cell[i];
-  const int ns[3] = {m->nx, m->ny, m->nz};
-  for (int c = 0; c < 3; ++c) {
-    const double* a = m->cell + 3 * c;
-    g.h[c] = std::sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]) / double(ns[c]);
-  }
-  g.nx = m->nx;
-  g.ny = m->ny;
-  g.nzh = m->nz / 2 + 1;
-  g.scheme = m->scheme;
-  g.order = m->order;
+  const KGeom g = make_kgeom(m);
   const int64_t Mh = int64_t(g.nx) * g.ny * g.nzh;
   const size_t lds = size_t(3) * sizeof(double) * size_t(t.n);
-  const unsigned grid = spline_grid(Mh);
+  const unsigned grid = stride_grid(Mh, kSplineBlock);
   T* Gp = (T*)G;
   if (t.n <= kLdsKnots) {
     if (recip)
@@ -344,9 +301,7 @@ int mipme_spline_kfilter_build(void* stream, int dtype, const mipme_mesh_t* mesh
   ZeroCubic z;
   const int rc = make_tab(spline, "mipme_spline_kfilter_build", t, z);
   if (rc) return rc;
-  MIPME_REQUIRE(mesh != nullptr && mesh->nx > 0 && mesh->ny > 0 && mesh->nz > 0, "mipme_spline_kfilter_build: invalid mesh");
-  MIPME_REQUIRE(mesh->scheme == MIPME_LAGRANGE || (mesh->scheme == MIPME_P3M && mesh->order >= 1 && mesh->order <= 5),
-                "`interpolation_nodes` is %d but only values from 1 to 5 for method 'P3M' are allowed", int(mesh->order));
+  if (const int mrc = validate_mesh(mesh)) return mrc;
   MIPME_REQUIRE(G != nullptr, "mipme_spline_kfilter_build: NULL pointer");
   hipStream_t st = (hipStream_t)stream;
   DT_SWITCH(dtype, spline_kfilter_impl<float>(st, mesh, t, z, spline->reciprocal != 0, spline->prefactor, G),

@@ -12,8 +12,8 @@ import ctypes as C
 
 import torch
 
-from . import _lib, combined, ops, splines
-from .potentials import CombinedPotential, Potential, SplinePotential
+from . import _lib, ops
+from .potentials import Potential
 from .splines import CubicSpline, CubicSplineReciprocal, compute_second_derivatives, compute_spline_ft  # noqa: F401
 
 
@@ -157,8 +157,8 @@ def generate_kvectors_for_mesh(cell: torch.Tensor, ns) -> torch.Tensor:
 class KSpaceKernel(torch.nn.Module):
     """Interface of a reciprocal-space kernel (reference ``lib/kspace_filter.py:7-35``): subclasses return the filter values
     for a tensor of squared k-vector norms.  The built-in potentials implement it as ``lr_from_k_sq``; a :class:`KSpaceFilter`
-    given any other subclass tabulates ``kernel_from_k_sq`` once per cell with tensor operations and runs the same convolution
-    kernels on the table."""
+    given any other subclass tabulates ``kernel_from_k_sq`` once per cell with tensor operations (divided by the influence
+    function's U^2 in a :class:`P3MKSpaceFilter`) and runs the same convolution kernels on the table."""
 
     def kernel_from_k_sq(self, k_sq: torch.Tensor) -> torch.Tensor:
         raise NotImplementedError(f"kernel_from_k_sq is not implemented for '{self.__class__.__name__}'")
@@ -169,7 +169,8 @@ class KSpaceFilter:
 
     Only the un-normalised convention used by the calculators (``fft_norm="backward"``,
     ``ifft_norm="forward"``) is implemented; ``kernel`` is a built-in :class:`Potential` (G built by the device kernel) or any
-    :class:`KSpaceKernel` (G tabulated from ``kernel_from_k_sq`` on :func:`generate_kvectors_for_mesh`).
+    :class:`KSpaceKernel` (G tabulated from ``kernel_from_k_sq`` on :func:`generate_kvectors_for_mesh`):
+    ``analytic.constant_table`` decides.
 
     A :class:`CombinedPotential` kernel: G is the members' tables contracted with the weights as they are when the filter is
     built or updated.  The filter does not follow later changes of the weights; call :meth:`update` after an optimizer step."""
@@ -203,29 +204,9 @@ class KSpaceFilter:
         self._geom = ops.MeshGeometry(
             self.cell.detach().to("cpu", torch.float64).numpy(), self.ns_mesh, self._scheme, self._order
         )
-        if isinstance(self.kernel, SplinePotential):  # G from the spline's own kernel (the fused ones do not know it)
-            self._kfilter = splines.build_filter(self._geom, self.kernel._splines()[1], self.kernel._prefactor_float(),
-                                                 self.cell.dtype, self.cell.device)
-        elif isinstance(self.kernel, CombinedPotential) and combined.plan(self.kernel) is not None:
-            # the members' tables from csrc/combined.hip, contracted with the weights as they are now
-            tables = combined.build_tables(self._geom, combined.plan(self.kernel), self.cell.dtype, self.cell.device)
-            self._kfilter = torch.tensordot(self.kernel.weights.detach().to(dtype=tables.dtype, device=tables.device), tables,
-                                            dims=1).contiguous()
-        elif isinstance(self.kernel, CombinedPotential):
-            # a combination the kernels do not serve (a spline member, a nested one, more than 8 terms ...): tabulated from the
-            # members' tensor lr_from_k_sq, as the calculators do -- correct, and slower
-            from types import SimpleNamespace
+        from . import analytic  # (imports this module)
 
-            from . import analytic
-
-            shim = SimpleNamespace(potential=self.kernel, _scheme=self._scheme, interpolation_nodes=self._order)
-            with torch.no_grad():
-                self._kfilter = analytic.filter_table(shim, self.cell.detach(), self.ns_mesh).to(self.cell.dtype).contiguous()
-        elif isinstance(self.kernel, Potential):
-            self._kfilter = ops.build_filter(self._geom, self.kernel._descriptor(), self.cell.dtype, self.cell.device)
-        else:  # a custom KSpaceKernel: tabulated with tensor operations, then the same convolution kernels
-            k = generate_kvectors_for_mesh(self.cell.detach(), self.ns_mesh)
-            self._kfilter = self.kernel.kernel_from_k_sq((k * k).sum(-1)).to(self.cell.dtype).contiguous()
+        self._kfilter = analytic.constant_table(self.kernel, self._geom, self.cell, self.cell.dtype, self.cell.device)
 
     def forward(self, mesh_values: torch.Tensor) -> torch.Tensor:
         if mesh_values.dim() != 4:
