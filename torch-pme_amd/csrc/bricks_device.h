@@ -152,12 +152,36 @@ __device__ __forceinline__ void store_slot_weights(T* __restrict__ wr, const T (
 // weights (44 B of a 120-byte row) and charge behind it: three dependent levels, ~7 gather instructions of 64 cache lines each
 // per wavefront and batch.  The entries of a list are contiguous, so consecutive lanes now stream consecutive 32-byte entries
 // (four lanes to a 128-byte line), there is no index to wait for, and the 2 N weights are 2 x ~25 FMAs (weights_1d).
+// FAT entries (fp32, N <= 5: plane_entry_fat): every atom is scattered by the workgroups of N planes, which evaluated the same 2 N
+// weights N times, on the CUs that bound the co-scheduled launch (docs/KERNELS.md "Plane-list entries").  The binning pass has the
+// two offsets in registers and stores the weights instead: word 0 as above, words 1 .. 1 + N the products charge * w_x[t], then
+// w_y[0..N) and w_z[0..N) -- 1 + 3 N words, at N = 5 exactly 64 bytes, two entries to a 128-byte line.  The format is a
+// compile-time property of (N, T): fp64 entries would be 128 bytes (round 6 lost 0.5 us at cfg2 to a wider fp64 entry) and
+// N = 6, 7 would hold 24 registers per entry in flight; both keep the entry with the offsets.  plane_entry_words,
+// plane_entry_bytes_rt and bins_layout are the only places that know the size.
+#ifndef MIPME_PLANE_FAT_F64
+#define MIPME_PLANE_FAT_F64 0  // (measurement builds: fat entries in fp64 too, tools/build_variant.sh)
+#endif
+#ifndef MIPME_PLANE_FAT_F32
+#define MIPME_PLANE_FAT_F32 1
+#endif
+static constexpr int kPlaneFatMaxOrder = 5;
+constexpr bool plane_entry_fat_rt(int order, size_t elem) {
+  return order <= kPlaneFatMaxOrder && (elem == 4 ? MIPME_PLANE_FAT_F32 != 0 : MIPME_PLANE_FAT_F64 != 0);
+}
+template <int N, typename T>
+constexpr bool plane_entry_fat() {
+  return plane_entry_fat_rt(N, sizeof(T));
+}
 template <int N, typename T>
 constexpr int plane_entry_words() {
   constexpr int V = 16 / int(sizeof(T));
-  return (3 + N + V - 1) / V * V;
+  return ((plane_entry_fat<N, T>() ? 1 + 3 * N : 3 + N) + V - 1) / V * V;
 }
-static inline size_t plane_entry_bytes_rt(int order, size_t elem) { return ((3 + size_t(order)) * elem + 15) / 16 * 16; }
+static inline size_t plane_entry_bytes_rt(int order, size_t elem) {
+  const size_t words = plane_entry_fat_rt(order, elem) ? 1 + 3 * size_t(order) : 3 + size_t(order);
+  return (words * elem + 15) / 16 * 16;
+}
 static constexpr int kPlanePackBits = 10;  // my, mz < 1024 (the plane tiles are far smaller), mx < 2048
 
 static int plane_list_capacity(const mipme_mesh_t* m, int64_t N, int dtype);
@@ -277,7 +301,7 @@ __device__ __forceinline__ void atom_mesh_coords(const Geom& g, bool even, const
 // of the fused pair kernels while the position is in registers anyway.
 static constexpr int64_t kCoalescedBinAtoms = 100000;  // atoms from which the binning pass stages its weight rows (see below)
 // LEAN (deferred slot fill, see slot_rider_body): everything the NEXT launch reads -- counters, overflow bookkeeping, wmax, atom
-// record, plane-list entry (x weights only, no derivatives) -- and the atom's destination slot in slot_dst[i]; the slot's record,
+// record, plane-list entry (x weights, for a fat entry y and z too; no derivatives) -- and the atom's destination slot in slot_dst[i]; the slot's record,
 // weights, charge and reach code are left to the slot riders of the inverse (y,z) plane launch.  qs is passed (it gates wmax) but
 // not written.
 template <int SCHEME, int N, typename T, bool COALESCE = false, bool LEAN = false>
@@ -387,10 +411,15 @@ __device__ __forceinline__ void bin_atoms_body(const Geom& g, const BrickGeom& b
   // group of 6N lanes writes value k of one atom -- contiguous 24N-byte segments, two atoms per instruction at N = 5
   // (1 029 000 atoms: 95 -> ... us for this kernel).
   constexpr int W = wts_stride<N, T>();
-  // the atom's plane-list entry (plane_entry_words): written once the x weights are known
+  // the atom's plane-list entry (plane_entry_words): written once the x weights are known.  A fat entry's y / z weights are
+  // evaluated HERE, by the call plane_item_make makes for the other format on the same offsets, in the lean, the one-pass and
+  // the staged form alike: the derivative-carrying evaluation the one-pass forms hold for the slot is contracted differently by
+  // the compiler and differs from it in the last bit (measured: potentials of the two routes 5e-7 apart), and the routes are
+  // tested bit for bit against each other (tests/test_gpu_deferred_slots.py)
   auto store_plane_entry = [&](const T (&wx)[N]) __attribute__((always_inline)) {
     if (!valid || pl_slot < 0) return;
     constexpr int EW = plane_entry_words<N, T>(), V = 16 / int(sizeof(T));
+    constexpr bool FAT = plane_entry_fat<N, T>();
     struct alignas(16) Chunk {
       T e[V];
     };
@@ -405,13 +434,27 @@ __device__ __forceinline__ void bin_atoms_body(const Geom& g, const BrickGeom& b
       v[0] = __int_as_float(packed);
     else
       v[0] = __longlong_as_double((long long)packed);
-    v[1] = T(x[1]);
-    v[2] = T(x[2]);
     const T qa = q[i];
+    if constexpr (FAT) {
+      T wy[N], wz[N], unused[N];
+      T oy = T(x[1]), oz = T(x[2]);
+      asm volatile("" : "+v"(oy), "+v"(oz));  // (opaque copies: not merged with the slot's evaluation of the same offsets)
+      weights_1d<SCHEME, N, false, T>(oy, wy, unused);
+      weights_1d<SCHEME, N, false, T>(oz, wz, unused);
 #pragma unroll
-    for (int t = 0; t < N; ++t) v[3 + t] = qa * wx[t];
+      for (int t = 0; t < N; ++t) {
+        v[1 + t] = qa * wx[t];
+        v[1 + N + t] = wy[t];
+        v[1 + 2 * N + t] = wz[t];
+      }
+    } else {
+      v[1] = T(x[1]);
+      v[2] = T(x[2]);
 #pragma unroll
-    for (int t = 3 + N; t < EW; ++t) v[t] = T(0);
+      for (int t = 0; t < N; ++t) v[3 + t] = qa * wx[t];
+    }
+#pragma unroll
+    for (int t = FAT ? 1 + 3 * N : 3 + N; t < EW; ++t) v[t] = T(0);
     Chunk* d = reinterpret_cast<Chunk*>(e);
 #pragma unroll
     for (int k = 0; k < EW / V; ++k) {
@@ -1341,8 +1384,11 @@ __device__ __forceinline__ void plane_raw_load(PlaneRaw<N, T>& r, bool ok, const
 #pragma unroll
     for (int u = 0; u < V; ++u) r.w[k * V + u] = c.e[u];
   }
+  // (the fat format needs no zeroing: a lane without an atom has stencil row -1, which picks no product, see entry_of)
+  if constexpr (!plane_entry_fat<N, T>()) {
 #pragma unroll
-  for (int t = 3; t < EW; ++t) r.w[t] = ok ? r.w[t] : T(0);
+    for (int t = 3; t < EW; ++t) r.w[t] = ok ? r.w[t] : T(0);
+  }
 }
 template <typename T>
 __device__ __forceinline__ int plane_raw_packed(T w0) {
@@ -1352,19 +1398,30 @@ __device__ __forceinline__ int plane_raw_packed(T w0) {
     return int(__double_as_longlong(w0));
 }
 
-// entry -> item of stencil row tt: the y / z weights from their offsets (the same weights_1d the binning pass evaluates for the
-// gather's rows), the product charge * w_x[tt] picked from the entry
+// entry -> item of stencil row tt: the product charge * w_x[tt] picked from the entry (tt outside [0, N): none, vx = 0); the y / z
+// weights copied from a fat entry, else evaluated from their offsets (the same weights_1d call the binning pass makes for a fat
+// entry and for the gather's rows)
 template <int SCHEME, int N, typename T>
 __device__ __forceinline__ void plane_item_make(PlaneItem<N, T>& it, const PlaneRaw<N, T>& r, int tt, T scale) {
+  constexpr bool FAT = plane_entry_fat<N, T>();
   const int packed = plane_raw_packed(r.w[0]);
   it.my = (packed >> kPlanePackBits) & ((1 << kPlanePackBits) - 1);
   it.mz = packed & ((1 << kPlanePackBits) - 1);
-  T qwx[N], unused[N];
+  T qwx[N];
 #pragma unroll
-  for (int t = 0; t < N; ++t) qwx[t] = r.w[3 + t];
+  for (int t = 0; t < N; ++t) qwx[t] = r.w[(FAT ? 1 : 3) + t];
   it.vx = pick<N, T>(qwx, tt) * scale;
-  weights_1d<SCHEME, N, false, T>(r.w[1], it.wy, unused);
-  weights_1d<SCHEME, N, false, T>(r.w[2], it.wz, unused);
+  if constexpr (FAT) {
+#pragma unroll
+    for (int t = 0; t < N; ++t) {
+      it.wy[t] = r.w[1 + N + t];
+      it.wz[t] = r.w[1 + 2 * N + t];
+    }
+  } else {
+    T unused[N];
+    weights_1d<SCHEME, N, false, T>(r.w[1], it.wy, unused);
+    weights_1d<SCHEME, N, false, T>(r.w[2], it.wz, unused);
+  }
 }
 
 // one atom's N x N points of the plane (natural layout acc[y * nz + z]): the products in the working precision (as the bricks
@@ -1522,37 +1579,67 @@ __device__ __forceinline__ void plane_spread_yz_body(const SpreadArgs<T>& args, 
   const int lo = int(int64_t(total) * part / pa.parts), hi = int(int64_t(total) * (part + 1) / pa.parts);
   const int n_batches = (hi - lo + nthr - 1) / nthr;
   // this lane's entry of batch b: its stencil row tt and the entry's index in the list array (-1: none) -- arithmetic on the
-  // prologue's list lengths, no load: the entries of batches b + 1 and b + 2 are in flight while batch b is scattered
+  // prologue's list lengths, no load: the entries of the next batches are in flight while batch b is scattered.
+  // Which list holds entry gidx of the sequence: the number of boundaries lst[1 .. NL) at or below gidx.  A wavefront's entries
+  // are consecutive (g0 .. g0 + 63, g0 its lane 0's), so that number is wave-uniform up to the few boundaries inside the span:
+  // with lst[] held one value per lane (read from LDS once) the list l0 of lane 0 is one ballot, and the boundaries behind it
+  // are walked by a uniform loop that ends at the first one beyond the span -- at most NL - 1 steps (lists may be empty: a span
+  // can cross all of them), typically one or two.  A scan of all NL - 1 boundaries per lane was ~78 vector instructions, 20
+  // LDS reads and 5 dependent LDS round trips per batch, in front of the address of the next entry load.
+  constexpr bool FAT = plane_entry_fat<N, T>();
+  const int lane = tid & 63;
+  const int lst_lane = lane <= NL ? lst[lane] : 0x7fffffff;
   auto entry_of = [&](int b, int& tt) __attribute__((always_inline)) -> int64_t {
     const int gidx = lo + b * nthr + tid;
-    int l = 0;
-    for (int u = 1; u < NL; ++u) l += gidx >= lst[u] ? 1 : 0;
+    const int g0 = __builtin_amdgcn_readfirstlane(gidx);
+    const int l0 = __builtin_popcountll(__builtin_amdgcn_ballot_w64(lane >= 1 && lane < NL && lst_lane <= g0));
+    int l = l0, first = __builtin_amdgcn_readlane(lst_lane, l0);  // first = lst[l]
+    for (int u = l0 + 1; u < NL; ++u) {
+      const int bnd = __builtin_amdgcn_readlane(lst_lane, u);
+      if (bnd > g0 + 63) break;
+      l += gidx >= bnd ? 1 : 0;
+      first = gidx >= bnd ? bnd : first;
+    }
     tt = l / SUBS;
-    if (b >= n_batches || gidx >= hi) return -1;
-    return int64_t(list_of(l)) * bins.pcap + (gidx - lst[l]);
+    if (b >= n_batches || gidx >= hi) {
+      if constexpr (FAT) tt = -1;  // (picks no product: the entry loaded in its place gives vx = 0, see plane_raw_load)
+      return -1;
+    }
+    return int64_t(list_of(l)) * bins.pcap + (gidx - first);
   };
+  // Entries in flight: two batches ahead, or one where an entry is fat (16 registers at N = 5: three raw entries would not leave
+  // the fp32 kernels their 64; round 5 measured no difference between the two depths)
+  constexpr int DEPTH = FAT ? 1 : 2;
   int tt0 = 0, tt1 = 0;
   PlaneRaw<N, T> r0, r1;
   {
-    const int64_t e0 = entry_of(0, tt0), e1 = entry_of(1, tt1);
+    const int64_t e0 = entry_of(0, tt0);
     plane_raw_load<N, T>(r0, e0 >= 0, plist, e0);
-    plane_raw_load<N, T>(r1, e1 >= 0, plist, e1);
+    if constexpr (DEPTH == 2) {
+      const int64_t e1 = entry_of(1, tt1);
+      plane_raw_load<N, T>(r1, e1 >= 0, plist, e1);
+    }
   }
   for (int b = 0; b < n_batches; ++b) {
-    int tt2 = 0;
-    const int64_t e2 = entry_of(b + 2, tt2);
-    PlaneRaw<N, T> r2;
-    plane_raw_load<N, T>(r2, e2 >= 0, plist, e2);  // (past the last batch: entry 0, never used)
+    int ttn = 0;
+    const int64_t en = entry_of(b + DEPTH, ttn);
+    PlaneRaw<N, T> rn;
+    plane_raw_load<N, T>(rn, en >= 0, plist, en);  // (past the last batch: entry 0, never used)
     PlaneItem<N, T> cur;
     plane_item_make<SCHEME, N, T>(cur, r0, tt0, args.scale);
     if (cur.vx != T(0)) {
       guard_item(cur);
       plane_item_scatter<N, T, BANDED>(acc, g, cur, fx_scale, row_lo, rows);
     }
-    r0 = r1;
-    tt0 = tt1;
-    r1 = r2;
-    tt1 = tt2;
+    if constexpr (DEPTH == 2) {
+      r0 = r1;
+      tt0 = tt1;
+      r1 = rn;
+      tt1 = ttn;
+    } else {
+      r0 = rn;
+      tt0 = ttn;
+    }
   }
   if (part == 0) {  // the plane overflow list (atoms whose plane list was full: normally none)
     const int oc = bins.plive[g.nx * kPlaneSub];
