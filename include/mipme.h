@@ -314,7 +314,10 @@ int mipme_fft_r2c(mipme_fft_plan* plan, void* stream, int dtype, const mipme_mes
  *   backward: grad_positions[f] = grad_scale[f] q_a (c force_a + field_a)   (c = 1/2 for a full list)
  * Requirements (checked; MIPME_EINVAL otherwise): brick kernels support the mesh, <= 1024 bricks, potential 1/r or 1/r^6
  * with a smearing, table shift format, power-of-two nx.  The brick counters of a frame must be zero before its first
- * use; every forward leaves them zero again. */
+ * use; every forward leaves them zero again.
+ * The rest of the first-order contract -- dE/dcharges and dE/dcell of every frame from the same launches (+ one launch of cell
+ * riders and one finalize launch per BATCH) -- is attached to a built table by mipme_frames_table_contract and evaluated by
+ * mipme_frames_step, declared behind mipme_frames_backward. */
 typedef struct mipme_frame {
   int64_t n_atoms;
   const void* positions;      /* (N,3) */
@@ -357,6 +360,46 @@ int mipme_frames_forward(mipme_fft_plan* plan, void* stream, int dtype, int n_fr
                          void* rho_mesh_all, void* hat_work_all, void* phi_mesh_all, void* dc_all);
 int mipme_frames_backward(void* stream, int dtype, int n_frames, const mipme_frame_t* frames, const void* device_table,
                           const void* grad_scale);
+
+/* The first-order contract of a frame batch: with use_tail for every frame, the gather tail of the step also writes
+ *   grad_charges[f] (N_f reals)  = 2 s V_f                      (s = aux_seed[0]; NULL: each frame's grad_seed)
+ *   grad_cell[f]    (27 reals)   = s dE_f/dcell: mesh part, pair part, their sum, as mipme_kspace_forward_args_t.out_grad_cell
+ * mipme_frames_table_contract patches a HOST table built by mipme_frames_table_build (before the upload, like
+ * mipme_frames_table_energy_log; call it again with NULL arrays to take the contract off).  grad_charges / grad_cell: arrays of
+ * n_frames device pointers, each array nullable as a whole.  The cell gradient needs G_deriv -- the frames' derivative tables
+ * (mipme_kfilter_build_deriv), G_deriv_stride reals apart, 0 = shared -- and cell_work = float64[n_frames * cell_work_stride]
+ * with cell_work_stride >= mipme_frames_cell_work(mesh, n_atoms) of every frame (it grows with the mesh and with n_atoms: ask
+ * with the largest frame).  The library lays the buffer out itself: the x stage's w = mu |rho^|^2 of all frames at its head,
+ * behind it every frame's rider rows, gather sums and pair sums.
+ * mipme_frames_step is mipme_frames_forward with a size- and version-checked argument struct; with cell_gradient != 0 it runs
+ * the instantiations of the pair sum that also form the cell sums, stores w in the x stage, and appends the riders of all frames
+ * (grid: riders x frames) and ONE finalize launch (a workgroup per frame).  cell_work: the buffer given to the table.
+ * Refused with MIPME_EINVAL before anything is launched (both entry points): NULL pieces, a frame without use_tail, and for
+ * the cell gradient a shift format other than 2 or a frame with dist_out. */
+int64_t mipme_frames_cell_work(const mipme_mesh_t* mesh, int64_t n_atoms);
+int mipme_frames_table_contract(int dtype, int n_frames, const mipme_frame_t* frames, const mipme_potential_t* pot, void* host_table,
+                                int64_t host_table_bytes, void* const* grad_charges, void* const* grad_cell, const void* G_deriv,
+                                int64_t G_deriv_stride, void* cell_work, int64_t cell_work_stride, const void* aux_seed);
+#define MIPME_FRAMES_STEP_VERSION 1
+typedef struct {
+  uint32_t size, version;   /* sizeof(mipme_frames_step_args_t), MIPME_FRAMES_STEP_VERSION */
+  struct mipme_fft_plan* plan;  /* batch = n_frames */
+  void* stream;
+  int32_t dtype, n_frames;
+  const mipme_frame_t* frames;
+  const mipme_potential_t* pot;
+  const void* device_table; /* the uploaded table (mipme_frames_table_bytes bytes) */
+  const void* G;            /* n_frames filter tables, G_stride reals apart (0 = shared) */
+  int64_t G_stride;
+  void* rho_mesh_all;
+  void* hat_work_all;
+  void* phi_mesh_all;
+  void* dc_all;
+  void* cell_work;          /* as given to mipme_frames_table_contract; nullable without cell_gradient */
+  int32_t cell_gradient;    /* != 0: the table carries grad_cell */
+  int32_t _pad;
+} mipme_frames_step_args_t;
+int mipme_frames_step(const mipme_frames_step_args_t* args);
 
 int mipme_fft_plan_xfused(const mipme_fft_plan* plan);
 

@@ -34,6 +34,7 @@ EXPORTS = (
     "mipme_pack_pair_shifts", "mipme_pair_distance_forward_packed", "mipme_fft_plan_xfused", "mipme_fft_plan_kgrid_blocks", "mipme_fft_r2c",
     "mipme_ewald_filter", "mipme_ewald_structure", "mipme_ewald_potential", "mipme_ewald_backward",
     "mipme_frames_table_bytes", "mipme_frames_table_build", "mipme_frames_forward", "mipme_frames_backward",
+    "mipme_frames_cell_work", "mipme_frames_table_contract", "mipme_frames_step",
     "mipme_scaled_match", "mipme_scaled_match_work", "mipme_scaled_match_wide", "mipme_md_supported", "mipme_md_lists_ints", "mipme_md_rebin", "mipme_md_step", "mipme_set_skip_flag", "mipme_energy_select", "mipme_energy_select_sum", "mipme_energy_select_contract",
     "mipme_kfilter_build_deriv", "mipme_cell_tail_work", "mipme_values_equal", "mipme_checksum", "mipme_checksum_words",
     "mipme_spread_jet", "mipme_gather_jet", "mipme_gather_jet3", "mipme_pair_sum", "mipme_pair_sum_rows", "mipme_pair_dot", "mipme_pair_diff", "mipme_pair_scatter",
@@ -255,6 +256,25 @@ class MdArgs(_VersionedArgs):
         C.Structure.__init__(self, size=C.sizeof(type(self)), version=1, **fields)
 
 
+FRAMES_STEP_VERSION = 1
+
+
+class FramesStepArgs(_VersionedArgs):
+    """``mipme_frames_step_args_t`` (version ``MIPME_FRAMES_STEP_VERSION``)"""
+
+    _fields_ = [
+        ("size", C.c_uint32), ("version", C.c_uint32),
+        ("plan", C.c_void_p), ("stream", C.c_void_p), ("dtype", C.c_int32), ("n_frames", C.c_int32),
+        ("frames", C.POINTER(Frame)), ("pot", C.POINTER(PotentialDesc)), ("device_table", C.c_void_p),
+        ("G", C.c_void_p), ("G_stride", C.c_int64),
+        ("rho_mesh_all", C.c_void_p), ("hat_work_all", C.c_void_p), ("phi_mesh_all", C.c_void_p), ("dc_all", C.c_void_p),
+        ("cell_work", C.c_void_p), ("cell_gradient", C.c_int32), ("_pad", C.c_int32),
+    ]
+
+    def __init__(self, **fields):
+        C.Structure.__init__(self, size=C.sizeof(type(self)), version=FRAMES_STEP_VERSION, **fields)
+
+
 #: OR-ed into a shift format: rows written by ``mipme_nl_stream`` (``row_ptr`` int32[3N+1], every neighbour once per row)
 ROWS_PADDED = 0x100
 FWD_RHO_MESH_UNUSED = 1  # mipme_kspace_forward_args_t.flags: the caller never reads rho_mesh after the call
@@ -331,6 +351,8 @@ def _declare(lib):
         "mipme_dot_backward": [vp, ci, i64, vp, vp, vp, vp, vp],
         "mipme_energy_log_push": [vp, ci, ci, vp, vp, vp, ci],
         "mipme_frames_table_energy_log": [ci, ci, vp, i64, vp, vp, ci],
+        "mipme_frames_table_contract": [ci, ci, C.POINTER(Frame), PP, vp, i64, C.POINTER(vp), C.POINTER(vp), vp, i64, vp, i64, vp],
+        "mipme_frames_step": [C.POINTER(FramesStepArgs)],
         "mipme_scaled_match": [vp, ci, i64, vp, vp, vp, vp],
         "mipme_scaled_match_work": [i64],
         "mipme_scaled_match_wide": [vp, ci, i64, vp, vp, vp, vp, vp],
@@ -390,6 +412,8 @@ def _declare(lib):
     lib.mipme_fft_plan_xfused.argtypes = [vp]
     lib.mipme_fft_plan_kgrid_blocks.restype = i64
     lib.mipme_fft_plan_kgrid_blocks.argtypes = [vp]
+    lib.mipme_frames_cell_work.restype = i64
+    lib.mipme_frames_cell_work.argtypes = [MP, i64]
     lib.mipme_frames_table_bytes.restype = i64
     lib.mipme_frames_table_bytes.argtypes = [ci, ci]
     lib.mipme_profile_enable.restype = ci

@@ -1,45 +1,13 @@
 // Independent frames in one launch (include/mipme.h: mipme_frames_*; SURVEY 8(e): the frames a rank owns).
-// Device bodies: bricks_device.h (the single-frame kernels' bodies, blockIdx.y = frame).
-#include "bricks_device.h"
+// Device bodies: bricks_device.h (the single-frame kernels' bodies, blockIdx.y = frame); the per-frame record: frames_device.h.
+// The instantiations of the pair sum that also form the cell sums live in frames_cell.hip, a translation unit of their own, so that
+// the kernels of this file -- all the flags-off step launches -- compile to what they were (tools/device_digest.py --kernels).
+#include "frames_device.h"
 
 namespace mipme {
 // ---- independent frames in one launch (include/mipme.h: mipme_frames_*) -----------------------------------------
 // blockIdx.y = frame; every kernel reads its frame's arguments from a device-resident table (built once per batch), so a
 // step of F frames is as many launches as a step of one frame.  The bodies are the single-frame kernels' bodies.
-template <typename T>
-struct FrameDev {
-  // binning
-  Geom g;
-  BrickGeom bg;
-  int64_t N;
-  const T* pos;
-  const T* q;
-  BinIndex bins;  // live = the frame's brick counters
-  int* over_brick;
-  int4* rec;
-  T* wts;
-  AtomRecord<T>* atom_rec;
-  int even;
-  // spread + pair sum
-  SpreadArgs<T> spread;
-  FusedRowsArgs<T> rows;
-  unsigned n_row_blocks;
-  // gather
-  const T* phi_mesh;
-  const T* dc;
-  T inv_vol, self_c, bg_c;
-  T* out;
-  T* field;
-  // energy, forces
-  T* energy;
-  const T* force;
-  T* grad_pos;
-  T force_scale;  // 1/2 for a full list
-  // gather tail (energy + forces in the gather launch)
-  GatherTail<T> tail;
-  bool use_tail;
-};
-
 template <int SCHEME, int N, typename T>
 __global__ __launch_bounds__(256) void frames_bin_atoms_kernel(const FrameDev<T>* __restrict__ table) {
   const FrameDev<T>& f = table[blockIdx.y];
@@ -92,7 +60,6 @@ __global__ __launch_bounds__(SPREAD_THREADS, (sizeof(T) == 4 && COMPACT) ? 6 : 1
     cosched_row_block<T, PFAST, COMPACT, false>(f.rows, blockIdx.x - n_items, smem_fp);
   }
 }
-
 template <int N, typename T>
 __global__ __launch_bounds__(GATHER_THREADS) void frames_gather_kernel(const FrameDev<T>* __restrict__ table) {
   const FrameDev<T>& f = table[blockIdx.y];
@@ -252,7 +219,8 @@ static int frames_table_build_t(int n_frames, const mipme_frame_t* fr, const mip
     d.force = (const T*)f.force;
     d.grad_pos = (T*)f.grad_positions;
     d.force_scale = f.full_list ? T(0.5) : T(1);
-    // energy + forces only (no grad_q, no cell sums); epart_k / n_k per batch entry: set by the gather kernel (plan scratch)
+    // energy + forces; grad_q and the cell sums: mipme_frames_table_contract.  epart_k / n_k per batch entry: set by the gather
+    // kernel (plan scratch)
     GatherTailHost th{};
     th.force = f.force;
     th.force_scale = f.full_list ? 0.5 : 1.0;
@@ -267,10 +235,19 @@ static int frames_table_build_t(int n_frames, const mipme_frame_t* fr, const mip
   return MIPME_OK;
 }
 
+// the frames table: n_frames FrameDev<T>, then n_frames FrameCellRec (filled by mipme_frames_table_contract, zero otherwise)
+template <typename T>
+static FrameCellRec* frames_cell_recs(const void* table, int n_frames) {
+  static_assert(sizeof(FrameDev<T>) % 8 == 0, "the cell records follow the frame records");
+  return (FrameCellRec*)((char*)const_cast<void*>(table) + size_t(n_frames) * sizeof(FrameDev<T>));
+}
+
+// cell_work (nullable): the batch's cell gradient -- the CELL instantiations of the pair sum, the x stage's store of w, and behind
+// the convolution the riders of every frame in one launch and the finalize launch (the contract is in the table already)
 template <typename T>
 static int frames_forward_t(mipme_fft_plan* plan, hipStream_t st, int n_frames, const mipme_frame_t* fr, const void* table,
                             const void* G, int64_t G_stride, void* rho_all, void* hat_all, void* phi_all, void* dc_all,
-                            int pfast) {
+                            int pfast, void* cell_work = nullptr) {
   const FrameDev<T>* tb = (const FrameDev<T>*)table;
   const mipme_mesh_t* m = &fr[0].mesh;
   const BrickGeom bg = make_brick_geom(m);
@@ -289,6 +266,7 @@ static int frames_forward_t(mipme_fft_plan* plan, hipStream_t st, int n_frames, 
   bool planes = fft_plan_plane_forward_ok_batched(plan);
   for (int k = 0; k < n_frames && planes; ++k) planes = frame_plane_lists(fr[k], dtype_of<T>());
   fft_plan_begin_step(plan);
+  int rc0 = MIPME_OK;
   if (!planes) note_cosched_kernel("frames_spread_rows_kernel");
   if (planes) {
     PlaneArgs<T> pa;
@@ -314,7 +292,9 @@ static int frames_forward_t(mipme_fft_plan* plan, hipStream_t st, int n_frames, 
 #define MIPME_FRAMES_PLANES(PF, CO) \
   MIPME_DISPATCH_STENCIL_B(m->scheme, m->order, (frames_plane_rows_kernel<S, N, T, PF, CO><<<dim3(pgrid_x, F), SPREAD_THREADS, plds, st>>>(tb, pa, Mh)))
     note_cosched_kernel("frames_plane_rows_kernel");
-    if (pfast == 1 && compact)
+    if (cell_work) {  // (4-byte entries: mipme_frames_step has checked them for every frame; frames_cell.hip)
+      if ((rc0 = frames_cell_plane_rows<T>(st, m->scheme, m->order, pfast, dim3(pgrid_x, F), plds, tb, pa, Mh))) return rc0;
+    } else if (pfast == 1 && compact)
       MIPME_FRAMES_PLANES(1, true);
     else if (pfast == 1)
       MIPME_FRAMES_PLANES(1, false);
@@ -324,6 +304,8 @@ static int frames_forward_t(mipme_fft_plan* plan, hipStream_t st, int n_frames, 
       MIPME_FRAMES_PLANES(6, false);
 #undef MIPME_FRAMES_PLANES
     fft_plan_set_forward_done(plan, true, pa.parts);
+  } else if (cell_work) {
+    if ((rc0 = frames_cell_spread_rows<T>(st, m->scheme, m->order, pfast, dim3(grid_x, F), lds, tb))) return rc0;
   } else if (pfast == 1 && compact)
     MIPME_DISPATCH_STENCIL_B(m->scheme, m->order,
                              ((void)S, frames_spread_rows_kernel<N, T, 1, true><<<dim3(grid_x, F), SPREAD_THREADS, lds, st>>>(tb)));
@@ -343,13 +325,27 @@ static int frames_forward_t(mipme_fft_plan* plan, hipStream_t st, int n_frames, 
   void* epart_k = nullptr;
   int rc;
   if (all_tail && (rc = fft_plan_tail_scratch(plan, int64_t(sizeof(double)) * n_k * n_frames, &epart_k))) return rc;
-  rc = convolve_xfused(plan, st, rho_all, G, hat_all, phi_all, dc_all, G_stride, nullptr, nullptr, nullptr, epart_k, nullptr, 0, nullptr, nullptr, nullptr);
+  // the cell gradient takes one store per k-point from the x stage: w = mu |rho^|^2 of batch entry c at wbuf + c * Mh, the head of
+  // the batch's cell_work (frames_cell_layout)
+  ConvCell cc{};
+  cc.wbuf = cell_work;
+  rc = convolve_xfused(plan, st, rho_all, G, hat_all, phi_all, dc_all, G_stride, nullptr, nullptr, nullptr, epart_k, nullptr, 0, nullptr, nullptr,
+                       cell_work ? &cc : nullptr);
   if (rc) return rc;
+  const FrameCellRec* recs = frames_cell_recs<T>(table, n_frames);
+  if (cell_work) {
+    // the riders of all frames in a launch of their own, grid (riders, frames): the batched inverse planes before them fill the
+    // device already (profiles/frames_contract_times.txt)
+    MIPME_REQUIRE(all_tail, "the cell gradient of a frame batch rides on the gather tail of every frame");
+    const int n_riders = int(cell_work_layout(m, 1, nullptr).n_riders);
+    if ((rc = frames_cell_riders<T>(st, recs, n_frames, n_riders, m->nx, m->ny, m->nz / 2 + 1, (const double*)epart_k, int(n_k)))) return rc;
+  }
   if (all_tail) {  // energy + forces of every frame in the gather launch
     MIPME_DISPATCH_STENCIL_B(m->scheme, m->order,
                              ((void)S, frames_gather_tail_kernel<N, T><<<dim3(unsigned(bg.nb), F), GATHER_THREADS, 0, st>>>(
                                  tb, (const double*)epart_k, int(n_k))));
     MIPME_LAUNCH_CHECK();
+    if (cell_work) return frames_cell_finalize<T>(st, recs, n_frames);
     return MIPME_OK;
   }
   MIPME_DISPATCH_STENCIL_B(m->scheme, m->order,
@@ -377,11 +373,129 @@ static int frames_table_energy_log_t(int n_frames, void* host_table, void* log, 
   return MIPME_OK;
 }
 
+// What every entry point of the contract refuses, per frame, before anything is launched
+static int frames_contract_check(int n_frames, const mipme_frame_t* fr, bool cell) {
+  for (int k = 0; k < n_frames; ++k) {
+    MIPME_REQUIRE(fr[k].use_tail, "frame %d: dE/dcharges and dE/dcell ride on the gather tail (mipme_frame_t.use_tail)", k);
+    if (!cell) continue;
+    MIPME_REQUIRE(fr[k].shift_format == kShiftTable32,
+                  "frame %d: the cell gradient needs 4-byte entries (shift format 2), got format %d", k, fr[k].shift_format);
+    MIPME_REQUIRE(!fr[k].dist_out, "frame %d: the cell gradient and the distance by-product (dist_out) exclude each other", k);
+  }
+  return MIPME_OK;
+}
+
+template <typename T>
+static int frames_table_contract_t(int n_frames, const mipme_frame_t* fr, const mipme_potential_t* pot, void* host_table,
+                                   void* const* grad_charges, void* const* grad_cell, const void* G_deriv, int64_t G_deriv_stride,
+                                   void* cell_work, int64_t cell_work_stride, const void* aux_seed) {
+  static_assert(kRowsPerSpreadBlock == 32 && SPREAD_THREADS / 64 == 8, "frames_cell_stride (host.h) sizes cwave by these");
+  SRPot s;
+  int rc = make_srpot(pot, s);
+  if (rc) return rc;
+  MIPME_REQUIRE(!grad_cell || rows_cell_supported<T>(fast_rs_exponent(s), fr[0].shift_format, nullptr),
+                "the cell gradient of a frame batch covers 1/r and 1/r^6 with 4-byte entries");
+  double self_c, bg_c;
+  correction_terms(pot, self_c, bg_c);
+  FrameDev<T>* d = (FrameDev<T>*)host_table;
+  FrameCellRec* recs = frames_cell_recs<T>(host_table, n_frames);
+  for (int k = 0; k < n_frames; ++k) {
+    const mipme_frame_t& f = fr[k];
+    GatherTail<T>& tail = d[k].tail;
+    tail.grad_q = grad_charges ? (T*)grad_charges[k] : nullptr;
+    tail.aux_seed = (const T*)aux_seed;
+    tail.rpart = nullptr;
+    tail.rec4 = nullptr;
+    d[k].rows.cpart = nullptr;
+    recs[k] = FrameCellRec{};
+    if (!grad_cell) continue;
+    const CellWork cw = frames_cell_layout(&f.mesh, f.n_atoms, n_frames, k, cell_work, cell_work_stride, sizeof(T));
+    tail.rpart = cw.rpart;
+    tail.rec4 = (const AtomRecord<T>*)f.records;  // (x, y, z, q) of every atom, written by the binning pass of the step
+    d[k].rows.cpart = cw.cwave;
+    FrameCellRec& r = recs[k];
+    r.mesh = f.mesh;
+    r.bg = bg_c;
+    r.pair_scale = f.full_list ? 0.25 : 0.5;  // 0.5 x the force scale
+    r.wbuf = cw.wbuf;
+    r.dG4 = (const T*)G_deriv + int64_t(k) * G_deriv_stride;
+    r.cwave = cw.cwave;
+    r.rows = cw.rows;
+    r.rpart = cw.rpart;
+    r.dc = f.dc;
+    r.seed = aux_seed ? aux_seed : f.grad_seed;
+    r.out = grad_cell[k];
+    r.n_waves = int(cw.n_waves);
+    r.n_riders = int(cw.n_riders);
+    r.n_bricks = int(cw.n_bricks);
+  }
+  return MIPME_OK;
+}
+
 extern "C" {
 
 int64_t mipme_frames_table_bytes(int dtype, int n_frames) {
   if (n_frames <= 0) return 0;
-  return int64_t(n_frames) * int64_t(dtype == MIPME_F32 ? sizeof(FrameDev<float>) : sizeof(FrameDev<double>));
+  return int64_t(n_frames) * int64_t((dtype == MIPME_F32 ? sizeof(FrameDev<float>) : sizeof(FrameDev<double>)) + sizeof(FrameCellRec));
+}
+
+int64_t mipme_frames_cell_work(const mipme_mesh_t* mesh, int64_t n_atoms) {
+  if (!mesh || validate_mesh(mesh) || n_atoms <= 0) return 0;
+  return frames_cell_stride(mesh, n_atoms);
+}
+
+int mipme_frames_table_contract(int dtype, int n_frames, const mipme_frame_t* frames, const mipme_potential_t* pot, void* host_table,
+                                int64_t host_table_bytes, void* const* grad_charges, void* const* grad_cell, const void* G_deriv,
+                                int64_t G_deriv_stride, void* cell_work, int64_t cell_work_stride, const void* aux_seed) {
+  int rc = frames_check(dtype, n_frames, frames);
+  if (rc) return rc;
+  MIPME_REQUIRE(pot && host_table && host_table_bytes >= mipme_frames_table_bytes(dtype, n_frames),
+                "invalid arguments to mipme_frames_table_contract");
+  if ((rc = frames_contract_check(n_frames, frames, grad_cell != nullptr))) return rc;
+  for (int k = 0; k < n_frames; ++k) {
+    MIPME_REQUIRE(!grad_charges || grad_charges[k], "frame %d: NULL grad_charges", k);
+    MIPME_REQUIRE(!grad_cell || grad_cell[k], "frame %d: NULL grad_cell", k);
+  }
+  if (grad_cell) {
+    MIPME_REQUIRE(G_deriv && cell_work && G_deriv_stride >= 0, "the cell gradient needs the frames' derivative tables (G_deriv) and cell_work");
+    for (int k = 0; k < n_frames; ++k)
+      MIPME_REQUIRE(cell_work_stride >= frames_cell_stride(&frames[k].mesh, frames[k].n_atoms),
+                    "frame %d: cell_work_stride = %lld is below mipme_frames_cell_work() = %lld", k, (long long)cell_work_stride,
+                    (long long)frames_cell_stride(&frames[k].mesh, frames[k].n_atoms));
+  }
+  DT_SWITCH(dtype,
+            frames_table_contract_t<float>(n_frames, frames, pot, host_table, grad_charges, grad_cell, G_deriv, G_deriv_stride,
+                                           cell_work, cell_work_stride, aux_seed),
+            frames_table_contract_t<double>(n_frames, frames, pot, host_table, grad_charges, grad_cell, G_deriv, G_deriv_stride,
+                                            cell_work, cell_work_stride, aux_seed));
+}
+
+int mipme_frames_step(const mipme_frames_step_args_t* a) {
+  MIPME_REQUIRE(a, "NULL argument struct passed to mipme_frames_step");
+  MIPME_REQUIRE(a->size == sizeof(mipme_frames_step_args_t), "mipme_frames_step_args_t: size %u, this library expects %zu", a->size,
+                sizeof(mipme_frames_step_args_t));
+  MIPME_REQUIRE(a->version == MIPME_FRAMES_STEP_VERSION, "mipme_frames_step_args_t: version %u, this library expects %d", a->version,
+                MIPME_FRAMES_STEP_VERSION);
+  int rc = frames_check(a->dtype, a->n_frames, a->frames);
+  if (rc) return rc;
+  MIPME_REQUIRE(a->plan && a->pot && a->device_table && a->G && a->rho_mesh_all && a->hat_work_all && a->phi_mesh_all && a->dc_all &&
+                    a->G_stride >= 0,
+                "NULL buffer passed to mipme_frames_step");
+  MIPME_REQUIRE(!a->cell_gradient || a->cell_work, "mipme_frames_step: the cell gradient needs cell_work");
+  if ((rc = frames_contract_check(a->n_frames, a->frames, a->cell_gradient != 0))) return rc;
+  MIPME_REQUIRE(fft_plan_xfused(a->plan) && fft_plan_batch(a->plan) == a->n_frames,
+                "mipme_frames_step needs a plan with batch = n_frames and a power-of-two nx");
+  SRPot s;
+  if ((rc = make_srpot(a->pot, s))) return rc;
+  const int pfast = fast_rs_exponent(s);
+  MIPME_REQUIRE(pfast == 1 || pfast == 6, "the frames path covers 1/r and 1/r^6 with a smearing");
+  hipStream_t st = (hipStream_t)a->stream;
+  void* cw = a->cell_gradient ? a->cell_work : nullptr;
+  DT_SWITCH(a->dtype,
+            frames_forward_t<float>(a->plan, st, a->n_frames, a->frames, a->device_table, a->G, a->G_stride, a->rho_mesh_all,
+                                    a->hat_work_all, a->phi_mesh_all, a->dc_all, pfast, cw),
+            frames_forward_t<double>(a->plan, st, a->n_frames, a->frames, a->device_table, a->G, a->G_stride, a->rho_mesh_all,
+                                     a->hat_work_all, a->phi_mesh_all, a->dc_all, pfast, cw));
 }
 
 int mipme_frames_table_build(int dtype, int n_frames, const mipme_frame_t* frames, const mipme_potential_t* pot,

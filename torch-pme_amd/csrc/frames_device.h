@@ -1,0 +1,47 @@
+// The per-frame record of the frame batches (frames.hip, frames_cell.hip): every kernel of a batch reads its frame's arguments from
+// a device-resident table of these, built once per batch (mipme_frames_table_build / mipme_frames_table_contract).
+#pragma once
+#include "bricks_device.h"
+
+namespace mipme {
+template <typename T>
+struct FrameDev {
+  // binning
+  Geom g;
+  BrickGeom bg;
+  int64_t N;
+  const T* pos;
+  const T* q;
+  BinIndex bins;  // live = the frame's brick counters
+  int* over_brick;
+  int4* rec;
+  T* wts;
+  AtomRecord<T>* atom_rec;
+  int even;
+  // spread + pair sum
+  SpreadArgs<T> spread;
+  FusedRowsArgs<T> rows;
+  unsigned n_row_blocks;
+  // gather
+  const T* phi_mesh;
+  const T* dc;
+  T inv_vol, self_c, bg_c;
+  T* out;
+  T* field;
+  // energy, forces
+  T* energy;
+  const T* force;
+  T* grad_pos;
+  T force_scale;  // 1/2 for a full list
+  // gather tail (energy + forces in the gather launch)
+  GatherTail<T> tail;
+  bool use_tail;
+};
+
+// frames_cell.hip: the co-scheduled launches of a batch whose pair sum also forms the cell sums (FusedRowsArgs::cpart of every
+// frame; 4-byte entries, 1/r or 1/r^6: rows_cell_supported) -- the plane route and the brick route
+template <typename T> int frames_cell_plane_rows(hipStream_t st, int scheme, int order, int pfast, dim3 grid, size_t lds,
+                                                 const FrameDev<T>* table, const PlaneArgs<T>& pa, int64_t frame_stride);
+template <typename T> int frames_cell_spread_rows(hipStream_t st, int scheme, int order, int pfast, dim3 grid, size_t lds, const FrameDev<T>* table);
+
+}  // namespace mipme

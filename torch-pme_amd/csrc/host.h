@@ -202,4 +202,47 @@ inline CellWork cell_work_layout(const mipme_mesh_t* m, int64_t N, void* base) {
   return w;
 }
 
+// ---- the cell gradient of a frame batch (mipme_frames_table_contract / mipme_frames_step) ---------------------------------------
+// What the batch's cell riders and its finalize launch read of one frame: a record per frame behind the FrameDev array of the
+// frames table (host and device copy alike).  n_riders == 0: the frame's batch carries no cell gradient.
+struct FrameCellRec {
+  mipme_mesh_t mesh;
+  double bg, pair_scale;   // background term; 0.5 x the force scale of the pair list
+  const void* wbuf;        // (nx, ny, nzh) reals: the x stage's w = mu |rho^|^2 of this frame
+  const void* dG4;         // (nx, ny, nzh, 4) reals: the frame's derivative table
+  const double* cwave;     // [9 * n_waves]
+  double* rows;            // [n_riders][25]
+  const double* rpart;     // [9 * n_bricks]
+  const void* dc;          // 1 real
+  const void* seed;        // device scalar, nullable (= 1)
+  void* out;               // 27 reals: mesh part, pair part, sum
+  int n_waves, n_riders, n_bricks, _pad;
+};
+template <typename T> int frames_cell_riders(hipStream_t st, const FrameCellRec* recs, int n_frames, int n_riders, int nx, int ny,
+                                             int nzh, const double* epart_k, int n_k);
+template <typename T> int frames_cell_finalize(hipStream_t st, const FrameCellRec* recs, int n_frames);
+
+// cell_work of a frame batch, in doubles: `stride` per frame (frames_cell_stride of the largest frame, or more), laid out as
+// [wbuf: n_frames x Mh reals, contiguous -- the batched x stage writes entry c at c * Mh -- in the first n_frames * Mh doubles]
+// [per frame, stride - Mh doubles apart: rows 25 per rider | rpart 9 per brick | cwave 9 per wavefront of the row blocks]
+// The row blocks of the co-scheduled launch write a slot for EVERY wavefront they hold (kRowsPerSpreadBlock rows, a wavefront per
+// four of them), so cwave is sized by whole blocks; the riders read the (N + 3) / 4 wavefronts that hold a row.
+inline int64_t frames_cell_stride(const mipme_mesh_t* m, int64_t N) {
+  const CellWork w = cell_work_layout(m, N, nullptr);
+  const int64_t rows_per_block = 32, waves_per_block = 8;  // (frames.hip: static_assert against SPREAD_THREADS / kRowLanes)
+  const int64_t waves = (N + rows_per_block - 1) / rows_per_block * waves_per_block;
+  return 25 * w.n_riders + 9 * w.n_bricks + 9 * waves + int64_t(m->nx) * m->ny * (m->nz / 2 + 1);
+}
+inline CellWork frames_cell_layout(const mipme_mesh_t* m, int64_t N, int n_frames, int frame, void* base, int64_t stride,
+                                   size_t real_bytes) {
+  CellWork w = cell_work_layout(m, N, nullptr);
+  const int64_t Mh = int64_t(m->nx) * m->ny * (m->nz / 2 + 1);
+  w.wbuf = (char*)base + size_t(frame) * size_t(Mh) * real_bytes;
+  w.rows = (double*)base + int64_t(n_frames) * Mh + int64_t(frame) * (stride - Mh);
+  w.rpart = w.rows + 25 * w.n_riders;
+  w.cwave = w.rpart + 9 * w.n_bricks;
+  w.total = stride;
+  return w;
+}
+
 }  // namespace mipme

@@ -1584,12 +1584,11 @@ struct SlabCell {
   double c0, L;
   int axis;
 };
-template <typename T, bool SLAB = false>
-__global__ __launch_bounds__(1024) void cell_tail_finalize_kernel(mipme_mesh_t m, double bg, double pair_scale, int n_rows,
-                                                                 int n_bricks, const double* __restrict__ rows,
-                                                                 const double* __restrict__ rpart, const T* __restrict__ dc,
-                                                                 const T* __restrict__ seed, T* __restrict__ out,
-                                                                 SlabCell sc) {
+template <typename T, bool SLAB>
+__device__ __forceinline__ void cell_tail_finalize_body(mipme_mesh_t m, double bg, double pair_scale, int n_rows,
+                                                        int n_bricks, const double* __restrict__ rows,
+                                                        const double* __restrict__ rpart, const T* __restrict__ dc,
+                                                        const T* __restrict__ seed, T* __restrict__ out, SlabCell sc) {
   __shared__ double gs[34], geo[18], s[31], res[18];
   {
     const int t = threadIdx.x;
@@ -1701,6 +1700,51 @@ __global__ __launch_bounds__(1024) void cell_tail_finalize_kernel(mipme_mesh_t m
   if (threadIdx.x < 9) out[18 + threadIdx.x] = T(res[threadIdx.x] + res[9 + threadIdx.x]);  // the sum, for callers with ONE cell tensor
 }
 
+template <typename T, bool SLAB = false>
+__global__ __launch_bounds__(1024) void cell_tail_finalize_kernel(mipme_mesh_t m, double bg, double pair_scale, int n_rows,
+                                                                 int n_bricks, const double* __restrict__ rows,
+                                                                 const double* __restrict__ rpart, const T* __restrict__ dc,
+                                                                 const T* __restrict__ seed, T* __restrict__ out,
+                                                                 SlabCell sc) {
+  cell_tail_finalize_body<T, SLAB>(m, bg, pair_scale, n_rows, n_bricks, rows, rpart, dc, seed, out, sc);
+}
+
+// ---- the same for a frame batch: blockIdx.y = frame of the riders, blockIdx.x = frame of the finalize launch; everything a
+// frame's workgroups need is in its FrameCellRec (host.h).  The riders' moments use integer frequencies, so that they need
+// nothing of the frame's geometry; epart_k: the x stage's energy sums, n_k per batch entry.
+template <typename T>
+__global__ __launch_bounds__(1024) void frames_cell_rider_kernel(const FrameCellRec* __restrict__ recs, int nx, int ny, int nzh,
+                                                                const double* __restrict__ epart_k, int n_k) {
+  __shared__ double red[16 * kCellRow];
+  const FrameCellRec& f = recs[blockIdx.y];
+  const CellRider r{int(gridDim.x), nx, ny, nzh, f.wbuf, f.dG4, f.cwave, f.n_waves, epart_k + int64_t(blockIdx.y) * n_k, n_k, f.rows,
+                    nullptr, nullptr, {}, {}};
+  cell_rider_body<T>(r, blockIdx.x, int(blockDim.x), red);
+}
+
+template <typename T>
+__global__ __launch_bounds__(1024) void frames_cell_finalize_kernel(const FrameCellRec* __restrict__ recs) {
+  const FrameCellRec& f = recs[blockIdx.x];
+  cell_tail_finalize_body<T, false>(f.mesh, f.bg, f.pair_scale, f.n_riders, f.n_bricks, f.rows, f.rpart, (const T*)f.dc,
+                                    (const T*)f.seed, (T*)f.out, SlabCell{});
+}
+
+template <typename T>
+int frames_cell_riders(hipStream_t st, const FrameCellRec* recs, int n_frames, int n_riders, int nx, int ny, int nzh,
+                       const double* epart_k, int n_k) {
+  MIPME_REQUIRE(int64_t(nx) * ny * nzh < (int64_t(1) << 31), "mesh too large for the cell riders' 32-bit indices");
+  frames_cell_rider_kernel<T><<<dim3(unsigned(n_riders), unsigned(n_frames)), 1024, 0, st>>>(recs, nx, ny, nzh, epart_k, n_k);
+  MIPME_LAUNCH_CHECK();
+  return MIPME_OK;
+}
+
+template <typename T>
+int frames_cell_finalize(hipStream_t st, const FrameCellRec* recs, int n_frames) {
+  frames_cell_finalize_kernel<T><<<unsigned(n_frames), 1024, 0, st>>>(recs);
+  MIPME_LAUNCH_CHECK();
+  return MIPME_OK;
+}
+
 template <typename T>
 int cell_tail_finalize_impl(hipStream_t st, const mipme_mesh_t* m, double bg, double pair_scale, int64_t n_rows,
                             int64_t n_bricks, const void* rows, const void* rpart, const void* dc, const void* seed, void* out,
@@ -1722,6 +1766,10 @@ template int cell_tail_finalize_impl<float>(hipStream_t, const mipme_mesh_t*, do
                                             const void*, const void*, const void*, void*, const GatherTailHost*);
 template int cell_tail_finalize_impl<double>(hipStream_t, const mipme_mesh_t*, double, double, int64_t, int64_t, const void*,
                                              const void*, const void*, const void*, void*, const GatherTailHost*);
+template int frames_cell_riders<float>(hipStream_t, const FrameCellRec*, int, int, int, int, int, const double*, int);
+template int frames_cell_riders<double>(hipStream_t, const FrameCellRec*, int, int, int, int, int, const double*, int);
+template int frames_cell_finalize<float>(hipStream_t, const FrameCellRec*, int);
+template int frames_cell_finalize<double>(hipStream_t, const FrameCellRec*, int);
 template int kfilter_build_impl<float>(hipStream_t, const mipme_mesh_t*, const mipme_potential_t*, void*);
 template int kfilter_build_impl<double>(hipStream_t, const mipme_mesh_t*, const mipme_potential_t*, void*);
 template int apply_filter_impl<float>(hipStream_t, int64_t, int, const void*, const void*, void*, void*);

@@ -544,6 +544,8 @@ class GraphedFrameBatch:
     The frames may differ in atoms, cell and neighbour list; they must give the same mesh dimensions and share the
     calculator (P3M / PME with 1/r or 1/r^6), dtype and device.  ``energies, forces = batch(positions_list=None)``:
     ``energies`` (F,), ``forces`` a list of (N_f, 3) tensors (static buffers of the graph: read them before the next call).
+    ``charge_gradient`` / ``cell_gradient`` add ``dE/dcharges`` and ``dE/dcell`` of every frame to what a call returns, from the
+    same replay -- the first-order contract of :class:`GraphedEnergyForces` for a whole batch.
 
     :param calculator: a :class:`PMECalculator` / :class:`P3MCalculator`
     :param frames: sequence of ``(charges, cell, positions, neighbor_indices, neighbor_shifts)``
@@ -551,13 +553,26 @@ class GraphedFrameBatch:
         list ordered by its first index); off by default, see :class:`GraphedEnergyForces`
     :param energy_log: an :class:`EnergyLog` (or a capacity) that every replay appends its F energies to, see there
     :param epilogue: ``epilogue(batch)``, called once inside the capture after everything else (see :class:`GraphedEnergyForces`)
+    :param charge_gradient: also return ``dE/dcharges`` of every frame -- a list of (N_f, 1) static buffers, ``= 2 V``, written
+        by the gather launch (``self.charge_grads``)
+    :param cell_gradient: also return ``dE/dcell`` at fixed Cartesian positions of every frame as ONE (F, 3, 3) tensor
+        (``self.cell_grads``; the virial of frame f is ``-cell_f.T @ cell_grads[f]``): the pair sum, the x stage and the gather of
+        the batch leave partial sums behind, one launch of cell riders (riders x frames) and one single-workgroup-per-frame launch
+        assemble them (``mipme_frames_table_contract`` / ``mipme_frames_step``).  Needs cell shifts that fit the 4-byte entries
+        in every frame and excludes ``store_distances``: both are refused here, by ``ValueError``.  With both flags a call
+        returns ``energies, forces, charge_grads, cell_grads`` -- the order of :class:`GraphedEnergyForces`
     """
 
-    def __init__(self, calculator, frames, warmup: int = 2, store_distances: bool = False, energy_log=None, epilogue=None):
+    def __init__(self, calculator, frames, warmup: int = 2, store_distances: bool = False, energy_log=None, epilogue=None,
+                 charge_gradient: bool = False, cell_gradient: bool = False):
         _refuse_spline(calculator, "GraphedFrameBatch")
         lib = _lib.load()
         self.calc = calculator
         self.store_distances = bool(store_distances)
+        self.charge_gradient, self.cell_gradient = bool(charge_gradient), bool(cell_gradient)
+        if self.cell_gradient and self.store_distances:
+            raise ValueError("GraphedFrameBatch: `cell_gradient` and `store_distances` exclude each other (the pair kernels "
+                             "that form the cell sums keep the distances in registers)")
         frames = list(frames)
         F = self.n_frames = len(frames)
         if F == 0:
@@ -644,9 +659,34 @@ class GraphedFrameBatch:
         if compact_ok:  # the same (compact) entry format for every frame
             for k, (_, ent32) in enumerate(ent_streams):
                 self._frames[k].entries_shift, self._frames[k].shift_format = ent32.data_ptr(), 2
+        elif self.cell_gradient:
+            bad = [k for k, (_, ent32) in enumerate(ent_streams) if ent32 is None]
+            raise ValueError(f"GraphedFrameBatch: `cell_gradient` needs 4-byte pair entries in every frame; the cell shifts or "
+                             f"the atom count of frame(s) {bad} do not fit them")
         nbytes = lib.mipme_frames_table_bytes(dt, F)
         host = np.zeros((nbytes,), dtype=np.uint8)
         _lib.check(lib.mipme_frames_table_build(dt, F, self._frames, C.byref(self._pot), host.ctypes.data, nbytes))
+        self.charge_grads = self.cell_grads = self._cell_work = None
+        if self.charge_gradient or self.cell_gradient:
+            # the rest of the first-order contract from the same launches: seeded with +1 while the positions' seed is -1
+            self._one = torch.ones((1,), dtype=dtype, device=device)
+            ptrs = lambda tensors: (C.c_void_p * F)(*(t.data_ptr() for t in tensors))  # noqa: E731
+            gq = gc = None
+            G_deriv, G_deriv_stride, work_stride = None, 0, 0
+            if self.charge_gradient:
+                self.charge_grads = [torch.empty((f.n_atoms, 1), dtype=dtype, device=device) for f in self._frames]
+                gq = ptrs(self.charge_grads)
+            if self.cell_gradient:
+                self._grad_cell = torch.empty((F, 27), dtype=dtype, device=device)  # mesh part, pair part, sum per frame
+                self.cell_grads = self._grad_cell[:, 18:27].view(F, 3, 3)
+                self._G_deriv = torch.stack([ops.filter_derivative(g, self._pot, dtype, device).reshape(-1) for g in geoms]).contiguous()
+                G_deriv, G_deriv_stride = self._G_deriv.data_ptr(), self._G_deriv.shape[1]
+                work_stride = max(int(lib.mipme_frames_cell_work(C.byref(f.mesh), f.n_atoms)) for f in self._frames)
+                self._cell_work = torch.empty((F * work_stride,), dtype=torch.float64, device=device)
+                gc = ptrs(self._grad_cell)
+            _lib.check(lib.mipme_frames_table_contract(
+                dt, F, self._frames, C.byref(self._pot), host.ctypes.data, nbytes, gq, gc, G_deriv, G_deriv_stride,
+                _lib.ptr(self._cell_work), work_stride, self._one.data_ptr()))
         self.energy_log = _as_energy_log(energy_log, F, device)
         if self.energy_log is not None:  # every frame's gather tail also writes its slot of the log (no extra launch)
             _lib.check(lib.mipme_frames_table_energy_log(dt, F, host.ctypes.data, nbytes, self.energy_log.values.data_ptr(),
@@ -670,6 +710,16 @@ class GraphedFrameBatch:
         self.forces = [p.grad for p in self.pos]
 
     def _launch_forward(self):
+        if self.charge_gradient or self.cell_gradient:  # (without flags: the call, and so the kernels, of before)
+            with _lib.on_device(self.device):
+                a = _lib.FramesStepArgs(
+                    plan=self._plan.handle, stream=_lib.current_stream(self.device), dtype=self._dt, n_frames=self.n_frames,
+                    frames=self._frames, pot=C.pointer(self._pot), device_table=self._table.data_ptr(), G=self._G.data_ptr(),
+                    G_stride=self._G.shape[1], rho_mesh_all=self._rho.data_ptr(), hat_work_all=self._hat.data_ptr(),
+                    phi_mesh_all=self._phi.data_ptr(), dc_all=self._dc.data_ptr(), cell_work=_lib.ptr(self._cell_work),
+                    cell_gradient=int(self.cell_gradient))
+                _lib.check(_lib.load().mipme_frames_step(C.byref(a)))
+            return
         with _lib.on_device(self.device):
             _lib.check(_lib.load().mipme_frames_forward(
                 self._plan.handle, _lib.current_stream(self.device), self._dt, self.n_frames, self._frames,
@@ -696,4 +746,9 @@ class GraphedFrameBatch:
                     buf.copy_(new)
         self.calc.check()  # a NaN a previous replay met (pinned word, no synchronisation)
         self.graph.replay()
-        return self.energies, self.forces
+        out = (self.energies, self.forces)
+        if self.charge_gradient:
+            out += (self.charge_grads,)
+        if self.cell_gradient:
+            out += (self.cell_grads,)
+        return out
