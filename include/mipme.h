@@ -401,6 +401,35 @@ typedef struct {
 } mipme_frames_step_args_t;
 int mipme_frames_step(const mipme_frames_step_args_t* args);
 
+/* 2-D periodic (slab) frames in a batch: the term of mipme_kspace_forward_args_t.slab (potentials/coulomb.py:6-40) for every
+ * frame that is periodic along two cell vectors only, each with its own axis, next to fully periodic frames.  Potentials,
+ * energy, grad_positions, the stored field, grad_charges, grad_cell and the energy log of such a frame contain the term; its
+ * cell dependence goes through the volume and L = |cell[axis]| (z is the Cartesian coordinate along the axis).
+ * mipme_frames_table_slab patches a HOST table built by mipme_frames_table_build (before the upload; before or after
+ * mipme_frames_table_contract / mipme_frames_table_energy_log).  slab: int32[n_frames], 0 = the frame is fully periodic (no term),
+ * else its non-periodic axis + 1; NULL takes the term off the whole table again.  slab_work = float64[n_frames *
+ * slab_work_stride] on the device with slab_work_stride >= mipme_frames_slab_work(), owned by the caller, ZERO before the first
+ * use (every step leaves its ticket words zero again, so a captured step can be replayed).
+ * mipme_frames_slab_step is mipme_frames_step for such a table: one launch ahead of the binning forms the moments {sum q,
+ * sum q z, sum q z^2} of every slab frame (grid: blocks x frames; fp64 block sums added in a fixed order), the gather and --
+ * with step.cell_gradient -- the finalize launch run compiled with the term.  slab / slab_work / slab_work_stride: as given to
+ * the table.  A table without the term goes to mipme_frames_step / mipme_frames_forward as before.
+ * Refused with MIPME_EINVAL before anything is launched (both entry points): NULL pieces, a slab code outside 0..3, a frame
+ * without use_tail, a potential that is not 1/r, a stride below mipme_frames_slab_work(); the step also refuses what
+ * mipme_frames_step refuses. */
+int64_t mipme_frames_slab_work(void);
+int mipme_frames_table_slab(int dtype, int n_frames, const mipme_frame_t* frames, const mipme_potential_t* pot, void* host_table,
+                            int64_t host_table_bytes, const int32_t* slab, void* slab_work, int64_t slab_work_stride);
+#define MIPME_FRAMES_SLAB_STEP_VERSION 1
+typedef struct {
+  uint32_t size, version;   /* sizeof(mipme_frames_slab_step_args_t), MIPME_FRAMES_SLAB_STEP_VERSION */
+  mipme_frames_step_args_t step;  /* as for mipme_frames_step, its own size and version set */
+  const int32_t* slab;      /* host array, n_frames codes */
+  void* slab_work;
+  int64_t slab_work_stride;
+} mipme_frames_slab_step_args_t;
+int mipme_frames_slab_step(const mipme_frames_slab_step_args_t* args);
+
 int mipme_fft_plan_xfused(const mipme_fft_plan* plan);
 
 /* Adjoint of mipme_kspace_forward for an upstream gradient g = dL/d(out_lr), shape (N,C).

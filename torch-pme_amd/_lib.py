@@ -35,6 +35,7 @@ EXPORTS = (
     "mipme_ewald_filter", "mipme_ewald_structure", "mipme_ewald_potential", "mipme_ewald_backward",
     "mipme_frames_table_bytes", "mipme_frames_table_build", "mipme_frames_forward", "mipme_frames_backward",
     "mipme_frames_cell_work", "mipme_frames_table_contract", "mipme_frames_step",
+    "mipme_frames_slab_work", "mipme_frames_table_slab", "mipme_frames_slab_step",
     "mipme_scaled_match", "mipme_scaled_match_work", "mipme_scaled_match_wide", "mipme_md_supported", "mipme_md_lists_ints", "mipme_md_rebin", "mipme_md_step", "mipme_set_skip_flag", "mipme_energy_select", "mipme_energy_select_sum", "mipme_energy_select_contract",
     "mipme_kfilter_build_deriv", "mipme_cell_tail_work", "mipme_values_equal", "mipme_checksum", "mipme_checksum_words",
     "mipme_spread_jet", "mipme_gather_jet", "mipme_gather_jet3", "mipme_pair_sum", "mipme_pair_sum_rows", "mipme_pair_dot", "mipme_pair_diff", "mipme_pair_scatter",
@@ -275,6 +276,25 @@ class FramesStepArgs(_VersionedArgs):
         C.Structure.__init__(self, size=C.sizeof(type(self)), version=FRAMES_STEP_VERSION, **fields)
 
 
+FRAMES_SLAB_STEP_VERSION = 1
+
+
+class FramesSlabStepArgs(_VersionedArgs):
+    """``mipme_frames_slab_step_args_t`` (version ``MIPME_FRAMES_SLAB_STEP_VERSION``): a ``mipme_frames_step_args_t`` plus the
+    per-frame slab codes (host ``int32`` array: 0 = off, else the non-periodic axis + 1) and the moments' work buffer"""
+
+    _fields_ = [
+        ("size", C.c_uint32), ("version", C.c_uint32),
+        ("step", FramesStepArgs), ("slab", C.POINTER(C.c_int32)), ("slab_work", C.c_void_p), ("slab_work_stride", C.c_int64),
+    ]
+
+    def __init__(self, **fields):
+        unknown = set(fields) - {name for name, _ in self._fields_}
+        if unknown:
+            raise TypeError(f"{type(self).__name__}: unknown field(s) {sorted(unknown)}")
+        C.Structure.__init__(self, size=C.sizeof(type(self)), version=FRAMES_SLAB_STEP_VERSION, **fields)
+
+
 #: OR-ed into a shift format: rows written by ``mipme_nl_stream`` (``row_ptr`` int32[3N+1], every neighbour once per row)
 ROWS_PADDED = 0x100
 FWD_RHO_MESH_UNUSED = 1  # mipme_kspace_forward_args_t.flags: the caller never reads rho_mesh after the call
@@ -353,6 +373,8 @@ def _declare(lib):
         "mipme_frames_table_energy_log": [ci, ci, vp, i64, vp, vp, ci],
         "mipme_frames_table_contract": [ci, ci, C.POINTER(Frame), PP, vp, i64, C.POINTER(vp), C.POINTER(vp), vp, i64, vp, i64, vp],
         "mipme_frames_step": [C.POINTER(FramesStepArgs)],
+        "mipme_frames_table_slab": [ci, ci, C.POINTER(Frame), PP, vp, i64, C.POINTER(C.c_int32), vp, i64],
+        "mipme_frames_slab_step": [C.POINTER(FramesSlabStepArgs)],
         "mipme_scaled_match": [vp, ci, i64, vp, vp, vp, vp],
         "mipme_scaled_match_work": [i64],
         "mipme_scaled_match_wide": [vp, ci, i64, vp, vp, vp, vp, vp],
@@ -414,6 +436,8 @@ def _declare(lib):
     lib.mipme_fft_plan_kgrid_blocks.argtypes = [vp]
     lib.mipme_frames_cell_work.restype = i64
     lib.mipme_frames_cell_work.argtypes = [MP, i64]
+    lib.mipme_frames_slab_work.restype = i64
+    lib.mipme_frames_slab_work.argtypes = []
     lib.mipme_frames_table_bytes.restype = i64
     lib.mipme_frames_table_bytes.argtypes = [ci, ci]
     lib.mipme_profile_enable.restype = ci

@@ -115,51 +115,13 @@ static int check_plan(const mipme_fft_plan* plan, int dtype, const mipme_mesh_t*
 
 // ---- moments of the slab term of a gather tail (GatherTail, bricks_device.h): Q, M, M2 = sums of q, q z, q z^2 --------------
 // One launch ahead of the spread -- the moments depend on the atoms alone.  Block sums in fp64, then the block that draws the last
-// ticket adds them up in index order and leaves the ticket at zero (as dot_kernel does): the same bits run after run.
+// ticket adds them up in index order and leaves the ticket at zero: common.h slab_moments_body, shared with the frame batches.
 // z = zp[a * zs], q = qp[a * qs]: positions + charges of a calculator call (strides 3, 1) or the (x, y, z, q) records of the live
 // step (4, 4).  work: kSlabWork doubles = {Q, M, M2}, 3 sums per block, the ticket; zero when first used.
 template <typename T>
 __global__ __launch_bounds__(256) void slab_moments_blocks_kernel(int64_t N, const T* __restrict__ zp, int zs,
                                                                  const T* __restrict__ qp, int qs, double* work) {
-  double acc[3] = {0.0, 0.0, 0.0};
-  for (int64_t a = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; a < N; a += int64_t(gridDim.x) * blockDim.x) {
-    const double z = double(zp[a * zs]), q = double(qp[a * qs]);
-    acc[0] += q;
-    acc[1] += q * z;
-    acc[2] += q * z * z;
-  }
-  __shared__ double red[4][3];
-  __shared__ bool last;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  double* part = work + 3;
-  int* counter = reinterpret_cast<int*>(work + 3 + 3 * kSlabBlocks);
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    double v = acc[k];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    if (lane == 0) red[wave][k] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int k = 0; k < 3; ++k)
-      __hip_atomic_store(&part[3 * blockIdx.x + k], (red[0][k] + red[1][k]) + (red[2][k] + red[3][k]), __ATOMIC_RELAXED,
-                         __HIP_MEMORY_SCOPE_AGENT);
-    const int ticket = __hip_atomic_fetch_add(counter, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-    last = ticket == int(gridDim.x) - 1;
-  }
-  __syncthreads();
-  if (!last || wave != 0) return;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    double tot = int(threadIdx.x) < int(gridDim.x)
-                     ? __hip_atomic_load(&part[3 * threadIdx.x + k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-                     : 0.0;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) tot += __shfl_xor(tot, off, 64);
-    if (threadIdx.x == 0) work[k] = tot;
-  }
-  if (threadIdx.x == 0) __hip_atomic_store(counter, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  slab_moments_body<T>(N, zp, zs, qp, qs, work, blockIdx.x, gridDim.x);
 }
 
 template <typename T>

@@ -289,6 +289,55 @@ struct GatherTailHost {
 static constexpr int kSlabBlocks = 64;
 static constexpr int kSlabWork = 3 + 3 * kSlabBlocks + 1;
 
+// The moments launch's body (api.hip slab_moments_blocks_kernel: one system; frames_slab.hip: blockIdx.y = frame).  Block `block`
+// of `nblocks` sums its share of the N atoms in fp64 -- z = zp[a * zs], q = qp[a * qs] --, leaves its three sums behind work[3]
+// and draws a ticket; the block that draws the last one adds the block sums up in index order into work[0..2] and leaves the
+// ticket at zero (as dot_kernel does): the same bits run after run, and a captured launch can be replayed.
+// work: kSlabWork doubles = {Q, M, M2}, 3 sums per block, the ticket; zero when first used.  256 threads.
+template <typename T>
+__device__ __forceinline__ void slab_moments_body(int64_t N, const T* __restrict__ zp, int zs, const T* __restrict__ qp, int qs,
+                                                  double* work, unsigned block, unsigned nblocks) {
+  double acc[3] = {0.0, 0.0, 0.0};
+  for (int64_t a = int64_t(block) * blockDim.x + threadIdx.x; a < N; a += int64_t(nblocks) * blockDim.x) {
+    const double z = double(zp[a * zs]), q = double(qp[a * qs]);
+    acc[0] += q;
+    acc[1] += q * z;
+    acc[2] += q * z * z;
+  }
+  __shared__ double red[4][3];
+  __shared__ bool last;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  double* part = work + 3;
+  int* counter = reinterpret_cast<int*>(work + 3 + 3 * kSlabBlocks);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    double v = acc[k];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    if (lane == 0) red[wave][k] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int k = 0; k < 3; ++k)
+      __hip_atomic_store(&part[3 * block + k], (red[0][k] + red[1][k]) + (red[2][k] + red[3][k]), __ATOMIC_RELAXED,
+                         __HIP_MEMORY_SCOPE_AGENT);
+    const int ticket = __hip_atomic_fetch_add(counter, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+    last = ticket == int(nblocks) - 1;
+  }
+  __syncthreads();
+  if (!last || wave != 0) return;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    double tot = int(threadIdx.x) < int(nblocks)
+                     ? __hip_atomic_load(&part[3 * threadIdx.x + k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+                     : 0.0;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) tot += __shfl_xor(tot, off, 64);
+    if (threadIdx.x == 0) work[k] = tot;
+  }
+  if (threadIdx.x == 0) __hip_atomic_store(counter, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // Deferred slot fill (bricks_device.h bin_atoms_body<LEAN>, slot_rider_body): what the rider workgroups of the inverse (y,z)
 // plane launch need to write the gather's slot data of every atom -- filled by bricks.hip bins_slot_rider, handed to the
 // convolution in ConvCell::slots.  Riders: ceil(n_atoms / per_rider).

@@ -2,6 +2,8 @@
 // Device bodies: bricks_device.h (the single-frame kernels' bodies, blockIdx.y = frame); the per-frame record: frames_device.h.
 // The instantiations of the pair sum that also form the cell sums live in frames_cell.hip, a translation unit of their own, so that
 // the kernels of this file -- all the flags-off step launches -- compile to what they were (tools/device_digest.py --kernels).
+// The launches of a batch with the 2-D periodic (slab) term live in frames_slab.hip for the same reason; their entry points --
+// host code -- are here (mipme_frames_table_slab, mipme_frames_slab_step).
 #include "frames_device.h"
 
 namespace mipme {
@@ -244,10 +246,12 @@ static FrameCellRec* frames_cell_recs(const void* table, int n_frames) {
 
 // cell_work (nullable): the batch's cell gradient -- the CELL instantiations of the pair sum, the x stage's store of w, and behind
 // the convolution the riders of every frame in one launch and the finalize launch (the contract is in the table already)
+// slab: the table carries the slab term (mipme_frames_table_slab) -- the moments of every frame in one launch ahead of everything
+// else, then the gather and the finalize launch compiled with the term (frames_slab.hip); every frame has its tail
 template <typename T>
 static int frames_forward_t(mipme_fft_plan* plan, hipStream_t st, int n_frames, const mipme_frame_t* fr, const void* table,
                             const void* G, int64_t G_stride, void* rho_all, void* hat_all, void* phi_all, void* dc_all,
-                            int pfast, void* cell_work = nullptr) {
+                            int pfast, void* cell_work = nullptr, bool slab = false) {
   const FrameDev<T>* tb = (const FrameDev<T>*)table;
   const mipme_mesh_t* m = &fr[0].mesh;
   const BrickGeom bg = make_brick_geom(m);
@@ -255,6 +259,10 @@ static int frames_forward_t(mipme_fft_plan* plan, hipStream_t st, int n_frames, 
   for (int k = 0; k < n_frames; ++k) max_atoms = std::max<int64_t>(max_atoms, fr[k].n_atoms);
   const unsigned atom_blocks = unsigned((max_atoms + 255) / 256);
   const unsigned F = unsigned(n_frames);
+  if (slab) {
+    const int rcs = frames_slab_moments<T>(st, tb, n_frames, max_atoms);
+    if (rcs) return rcs;
+  }
   MIPME_DISPATCH_STENCIL_B(m->scheme, m->order, (frames_bin_atoms_kernel<S, N, T><<<dim3(atom_blocks, F), 256, 0, st>>>(tb)));
   MIPME_LAUNCH_CHECK();
   const int stage_rows = spread_stage_rows(m->order, sizeof(T));
@@ -340,6 +348,11 @@ static int frames_forward_t(mipme_fft_plan* plan, hipStream_t st, int n_frames, 
     const int n_riders = int(cell_work_layout(m, 1, nullptr).n_riders);
     if ((rc = frames_cell_riders<T>(st, recs, n_frames, n_riders, m->nx, m->ny, m->nz / 2 + 1, (const double*)epart_k, int(n_k)))) return rc;
   }
+  if (slab) {  // the same two launches with the term
+    MIPME_REQUIRE(all_tail, "the slab term of a frame batch rides on the gather tail of every frame");
+    if ((rc = frames_slab_gather_tail<T>(st, m->scheme, m->order, dim3(unsigned(bg.nb), F), tb, (const double*)epart_k, int(n_k)))) return rc;
+    return cell_work ? frames_slab_cell_finalize<T>(st, recs, n_frames) : MIPME_OK;
+  }
   if (all_tail) {  // energy + forces of every frame in the gather launch
     MIPME_DISPATCH_STENCIL_B(m->scheme, m->order,
                              ((void)S, frames_gather_tail_kernel<N, T><<<dim3(unsigned(bg.nb), F), GATHER_THREADS, 0, st>>>(
@@ -405,9 +418,16 @@ static int frames_table_contract_t(int n_frames, const mipme_frame_t* fr, const 
     tail.grad_q = grad_charges ? (T*)grad_charges[k] : nullptr;
     tail.aux_seed = (const T*)aux_seed;
     tail.rpart = nullptr;
-    tail.rec4 = nullptr;
+    // (the slab term, attached before or after this call by mipme_frames_table_slab, keeps its own: the records for z, and
+    // its fields of the cell record)
+    tail.rec4 = tail.slab_mom ? (const AtomRecord<T>*)f.records : nullptr;
     d[k].rows.cpart = nullptr;
+    const FrameCellRec before = recs[k];
     recs[k] = FrameCellRec{};
+    recs[k].slab_mom = before.slab_mom;
+    recs[k].slab_c0 = before.slab_c0;
+    recs[k].slab_L = before.slab_L;
+    recs[k].slab_axis = before.slab_axis;
     if (!grad_cell) continue;
     const CellWork cw = frames_cell_layout(&f.mesh, f.n_atoms, n_frames, k, cell_work, cell_work_stride, sizeof(T));
     tail.rpart = cw.rpart;
@@ -432,7 +452,96 @@ static int frames_table_contract_t(int n_frames, const mipme_frame_t* fr, const 
   return MIPME_OK;
 }
 
+// ---- the 2-D periodic (slab) term of a frame batch ---------------------------------------------------------------------------
+// What both entry points refuse, before anything is launched.  slab[k]: 0 = frame k is fully periodic, else its non-periodic
+// axis + 1
+static int frames_slab_check(int n_frames, const mipme_frame_t* fr, const mipme_potential_t* pot, const int32_t* slab,
+                             const void* work, int64_t stride, const char* who) {
+  MIPME_REQUIRE(slab && work, "%s: NULL slab array or slab_work", who);
+  MIPME_REQUIRE(pot->kind == MIPME_COULOMB || pot->exponent == 1, "%s: the slab term exists for 1/r only", who);
+  MIPME_REQUIRE(stride >= kSlabWork, "%s: slab_work_stride = %lld is below mipme_frames_slab_work() = %d", who, (long long)stride,
+                kSlabWork);
+  for (int k = 0; k < n_frames; ++k) {
+    MIPME_REQUIRE(slab[k] >= 0 && slab[k] <= 3, "%s: frame %d: slab must be 0 (off) or the non-periodic axis + 1, got %d", who, k,
+                  int(slab[k]));
+    MIPME_REQUIRE(fr[k].use_tail, "%s: frame %d: the slab term rides on the gather tail (mipme_frame_t.use_tail)", who, k);
+  }
+  return MIPME_OK;
+}
+
+template <typename T>
+static int frames_table_slab_t(int n_frames, const mipme_frame_t* fr, const mipme_potential_t* pot, void* host_table,
+                               const int32_t* slab, void* work, int64_t stride) {
+  FrameDev<T>* d = (FrameDev<T>*)host_table;
+  FrameCellRec* recs = frames_cell_recs<T>(host_table, n_frames);
+  for (int k = 0; k < n_frames; ++k) {
+    GatherTail<T>& tail = d[k].tail;
+    GatherTailHost th{};
+    if (slab && slab[k]) tail_attach_slab(th, &fr[k].mesh, pot, slab[k]);
+    // every frame of a slab batch has its work slice: a fully periodic one keeps the zeros there and c0 = L = 0, so that the
+    // launches compiled with the term add exact zeros to it
+    tail.slab_mom = slab ? (const double*)work + int64_t(k) * stride : nullptr;
+    tail.slab_c0 = th.slab_c0;
+    tail.slab_L = th.slab_L;
+    tail.slab_axis = th.slab ? th.slab - 1 : 0;
+    // z of an atom comes from its record (x, y, z, q), written by the binning pass of the step; the cell sums read it too
+    tail.rec4 = (slab || tail.rpart) ? (const AtomRecord<T>*)fr[k].records : nullptr;
+    recs[k].slab_mom = tail.slab_mom;
+    recs[k].slab_c0 = tail.slab_c0;
+    recs[k].slab_L = tail.slab_L;
+    recs[k].slab_axis = tail.slab_axis;
+  }
+  return MIPME_OK;
+}
+
 extern "C" {
+
+int64_t mipme_frames_slab_work(void) { return kSlabWork; }
+
+int mipme_frames_table_slab(int dtype, int n_frames, const mipme_frame_t* frames, const mipme_potential_t* pot, void* host_table,
+                            int64_t host_table_bytes, const int32_t* slab, void* slab_work, int64_t slab_work_stride) {
+  int rc = frames_check(dtype, n_frames, frames);
+  if (rc) return rc;
+  MIPME_REQUIRE(pot && host_table && host_table_bytes >= mipme_frames_table_bytes(dtype, n_frames),
+                "invalid arguments to mipme_frames_table_slab");
+  if (slab && (rc = frames_slab_check(n_frames, frames, pot, slab, slab_work, slab_work_stride, "mipme_frames_table_slab"))) return rc;
+  DT_SWITCH(dtype, frames_table_slab_t<float>(n_frames, frames, pot, host_table, slab, slab_work, slab_work_stride),
+            frames_table_slab_t<double>(n_frames, frames, pot, host_table, slab, slab_work, slab_work_stride));
+}
+
+int mipme_frames_slab_step(const mipme_frames_slab_step_args_t* s) {
+  MIPME_REQUIRE(s, "NULL argument struct passed to mipme_frames_slab_step");
+  MIPME_REQUIRE(s->size == sizeof(mipme_frames_slab_step_args_t), "mipme_frames_slab_step_args_t: size %u, this library expects %zu",
+                s->size, sizeof(mipme_frames_slab_step_args_t));
+  MIPME_REQUIRE(s->version == MIPME_FRAMES_SLAB_STEP_VERSION, "mipme_frames_slab_step_args_t: version %u, this library expects %d",
+                s->version, MIPME_FRAMES_SLAB_STEP_VERSION);
+  const mipme_frames_step_args_t* a = &s->step;
+  MIPME_REQUIRE(a->size == sizeof(mipme_frames_step_args_t) && a->version == MIPME_FRAMES_STEP_VERSION,
+                "mipme_frames_slab_step_args_t.step: size %u / version %u, this library expects %zu / %d", a->size, a->version,
+                sizeof(mipme_frames_step_args_t), MIPME_FRAMES_STEP_VERSION);
+  int rc = frames_check(a->dtype, a->n_frames, a->frames);
+  if (rc) return rc;
+  MIPME_REQUIRE(a->plan && a->pot && a->device_table && a->G && a->rho_mesh_all && a->hat_work_all && a->phi_mesh_all && a->dc_all &&
+                    a->G_stride >= 0,
+                "NULL buffer passed to mipme_frames_slab_step");
+  MIPME_REQUIRE(!a->cell_gradient || a->cell_work, "mipme_frames_slab_step: the cell gradient needs cell_work");
+  if ((rc = frames_slab_check(a->n_frames, a->frames, a->pot, s->slab, s->slab_work, s->slab_work_stride, "mipme_frames_slab_step")))
+    return rc;
+  if ((rc = frames_contract_check(a->n_frames, a->frames, a->cell_gradient != 0))) return rc;
+  MIPME_REQUIRE(fft_plan_xfused(a->plan) && fft_plan_batch(a->plan) == a->n_frames,
+                "mipme_frames_slab_step needs a plan with batch = n_frames and a power-of-two nx");
+  SRPot sp;
+  if ((rc = make_srpot(a->pot, sp))) return rc;
+  const int pfast = fast_rs_exponent(sp);
+  MIPME_REQUIRE(pfast == 1, "mipme_frames_slab_step: the slab term exists for 1/r with a smearing");
+  hipStream_t st = (hipStream_t)a->stream;
+  void* cw = a->cell_gradient ? a->cell_work : nullptr;
+  DT_SWITCH(a->dtype,
+            frames_forward_t<float>(a->plan, st, a->n_frames, a->frames, a->device_table, a->G, a->G_stride, a->rho_mesh_all,
+                                    a->hat_work_all, a->phi_mesh_all, a->dc_all, pfast, cw, true),
+            frames_forward_t<double>(a->plan, st, a->n_frames, a->frames, a->device_table, a->G, a->G_stride, a->rho_mesh_all,
+                                     a->hat_work_all, a->phi_mesh_all, a->dc_all, pfast, cw, true));
+}
 
 int64_t mipme_frames_table_bytes(int dtype, int n_frames) {
   if (n_frames <= 0) return 0;

@@ -1,4 +1,4 @@
-// The per-frame record of the frame batches (frames.hip, frames_cell.hip): every kernel of a batch reads its frame's arguments from
+// The per-frame record of the frame batches (frames.hip, frames_cell.hip, frames_slab.hip): every kernel of a batch reads its frame's arguments from
 // a device-resident table of these, built once per batch (mipme_frames_table_build / mipme_frames_table_contract).
 #pragma once
 #include "bricks_device.h"
@@ -43,5 +43,12 @@ struct FrameDev {
 template <typename T> int frames_cell_plane_rows(hipStream_t st, int scheme, int order, int pfast, dim3 grid, size_t lds,
                                                  const FrameDev<T>* table, const PlaneArgs<T>& pa, int64_t frame_stride);
 template <typename T> int frames_cell_spread_rows(hipStream_t st, int scheme, int order, int pfast, dim3 grid, size_t lds, const FrameDev<T>* table);
+
+// frames_slab.hip: the launches of a batch with the 2-D periodic (slab) term (mipme_frames_table_slab / mipme_frames_slab_step) --
+// the moments {Q, sum q z, sum q z^2} of every frame in one launch, grid (blocks <= kSlabBlocks, frames), and the gather + tail
+// compiled with the term (gather_brick_body<SLAB>)
+template <typename T> int frames_slab_moments(hipStream_t st, const FrameDev<T>* table, int n_frames, int64_t max_atoms);
+template <typename T> int frames_slab_gather_tail(hipStream_t st, int scheme, int order, dim3 grid, const FrameDev<T>* table,
+                                                  const double* epart_k, int n_k);
 
 }  // namespace mipme

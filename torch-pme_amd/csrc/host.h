@@ -217,10 +217,17 @@ struct FrameCellRec {
   const void* seed;        // device scalar, nullable (= 1)
   void* out;               // 27 reals: mesh part, pair part, sum
   int n_waves, n_riders, n_bricks, _pad;
+  // the slab term of the frame (mipme_frames_table_slab; read by the SLAB finalize launch alone): as GatherTail's fields.
+  // A fully periodic frame of a slab batch has c0 = 0 and moments of zero: every term it adds is an exact zero
+  const double* slab_mom;
+  double slab_c0, slab_L;
+  int slab_axis, _pad_slab;
 };
 template <typename T> int frames_cell_riders(hipStream_t st, const FrameCellRec* recs, int n_frames, int n_riders, int nx, int ny,
                                              int nzh, const double* epart_k, int n_k);
 template <typename T> int frames_cell_finalize(hipStream_t st, const FrameCellRec* recs, int n_frames);
+// frames_slab.hip: the same launch with the slab term of every frame (FrameCellRec::slab_*)
+template <typename T> int frames_slab_cell_finalize(hipStream_t st, const FrameCellRec* recs, int n_frames);
 
 // cell_work of a frame batch, in doubles: `stride` per frame (frames_cell_stride of the largest frame, or more), laid out as
 // [wbuf: n_frames x Mh reals, contiguous -- the batched x stage writes entry c at c * Mh -- in the first n_frames * Mh doubles]

@@ -561,11 +561,24 @@ class GraphedFrameBatch:
         assemble them (``mipme_frames_table_contract`` / ``mipme_frames_step``).  Needs cell shifts that fit the 4-byte entries
         in every frame and excludes ``store_distances``: both are refused here, by ``ValueError``.  With both flags a call
         returns ``energies, forces, charge_grads, cell_grads`` -- the order of :class:`GraphedEnergyForces`
+    :param periodic: with ``slab_correction=True``: which cell vectors the frames repeat along -- one triple of booleans for
+        every frame, or a sequence of F triples, one per frame.  A triple has exactly two true entries (a 2-D periodic frame; the
+        third axis is its own, frames of one batch may differ in it) or three (a fully periodic frame, which gets no term)
+    :param slab_correction: add the 2-D periodic (slab) term of the reference (``potentials/coulomb.py:6-40``) to every frame that
+        ``periodic`` marks as a slab: its energy, forces, ``charge_grads``, ``cell_grads`` and ``energy_log`` entries then describe
+        a system that repeats in two directions only, as with :class:`GraphedEnergyForces`.  One launch ahead of the binning
+        forms the moments ``sum q``, ``sum q z``, ``sum q z^2`` of all frames (blocks x frames), and the gather and the cell
+        finalize launch run compiled with the term (``mipme_frames_table_slab`` / ``mipme_frames_slab_step``).  The potential
+        must be 1/r with a smearing.  The batch takes explicit pair lists, so ``periodic`` has no list to shape: it is refused
+        without ``slab_correction=True``.  A batch whose frames are all fully periodic is built and launched as without the
+        keywords
     """
 
     def __init__(self, calculator, frames, warmup: int = 2, store_distances: bool = False, energy_log=None, epilogue=None,
-                 charge_gradient: bool = False, cell_gradient: bool = False):
+                 charge_gradient: bool = False, cell_gradient: bool = False, periodic=None, slab_correction: bool = False):
         _refuse_spline(calculator, "GraphedFrameBatch")
+        frames = list(frames)
+        slab = self._slab_codes(calculator, len(frames), periodic, slab_correction)
         lib = _lib.load()
         self.calc = calculator
         self.store_distances = bool(store_distances)
@@ -573,7 +586,6 @@ class GraphedFrameBatch:
         if self.cell_gradient and self.store_distances:
             raise ValueError("GraphedFrameBatch: `cell_gradient` and `store_distances` exclude each other (the pair kernels "
                              "that form the cell sums keep the distances in registers)")
-        frames = list(frames)
         F = self.n_frames = len(frames)
         if F == 0:
             raise ValueError("no frames")
@@ -687,6 +699,15 @@ class GraphedFrameBatch:
             _lib.check(lib.mipme_frames_table_contract(
                 dt, F, self._frames, C.byref(self._pot), host.ctypes.data, nbytes, gq, gc, G_deriv, G_deriv_stride,
                 _lib.ptr(self._cell_work), work_stride, self._one.data_ptr()))
+        #: per frame: the non-periodic axis of a slab frame, ``None`` for a fully periodic one (``None`` as a whole: no slab term)
+        self.slab_axes = None if slab is None else [c - 1 if c else None for c in slab]
+        self._slab = self._slab_work = None
+        if slab is not None:
+            self._slab = (C.c_int32 * F)(*slab)
+            self._slab_stride = int(lib.mipme_frames_slab_work())
+            self._slab_work = torch.zeros((F * self._slab_stride,), dtype=torch.float64, device=device)
+            _lib.check(lib.mipme_frames_table_slab(dt, F, self._frames, C.byref(self._pot), host.ctypes.data, nbytes, self._slab,
+                                                   self._slab_work.data_ptr(), self._slab_stride))
         self.energy_log = _as_energy_log(energy_log, F, device)
         if self.energy_log is not None:  # every frame's gather tail also writes its slot of the log (no extra launch)
             _lib.check(lib.mipme_frames_table_energy_log(dt, F, host.ctypes.data, nbytes, self.energy_log.values.data_ptr(),
@@ -709,8 +730,40 @@ class GraphedFrameBatch:
                 epilogue(self)
         self.forces = [p.grad for p in self.pos]
 
+    @staticmethod
+    def _slab_codes(calculator, n_frames, periodic, slab_correction):
+        """``mipme_frames_table_slab``'s code per frame (0 = fully periodic, else the non-periodic axis + 1) from the two keywords;
+        ``None``: no slab term anywhere in the batch -- the calls and kernels of a batch without the keywords."""
+        if not slab_correction:
+            if periodic is not None:
+                raise ValueError("GraphedFrameBatch: `periodic` only selects the frames and axes of `slab_correction=True` (the batch "
+                                 "takes explicit pair lists, there is no neighbour list for it to shape)")
+            return None
+        if periodic is None:
+            raise ValueError("GraphedFrameBatch: `slab_correction` needs `periodic`: one triple of booleans for every frame, or one "
+                             "per frame")
+        per = list(periodic)
+        if len(per) == 3 and all(isinstance(p, (bool, int, np.bool_)) or (torch.is_tensor(p) and p.ndim == 0) for p in per):
+            per = [per] * n_frames
+        if len(per) != n_frames:
+            raise ValueError(f"GraphedFrameBatch: `periodic` must be one triple or one triple per frame ({n_frames}), got {len(per)}")
+        codes = []
+        for k, triple in enumerate(per):
+            flags = [bool(p) for p in triple]
+            if len(flags) != 3 or sum(flags) < 2:
+                raise ValueError(f"frame {k}: `slab_correction` needs exactly two periodic axes (or three: a fully periodic frame), "
+                                 f"got periodic={tuple(flags)}")
+            codes.append(0 if all(flags) else flags.index(False) + 1)
+        desc = calculator.potential._descriptor()
+        if not (desc.kind == _lib.COULOMB or desc.exponent == 1):
+            raise ValueError("`slab_correction`: the slab term exists for 1/r only (CoulombPotential, or "
+                             "InversePowerLawPotential(exponent=1))")
+        if calculator.potential.smearing is None:
+            raise ValueError("`slab_correction` belongs to the mesh part: the potential needs a smearing")
+        return codes if any(codes) else None
+
     def _launch_forward(self):
-        if self.charge_gradient or self.cell_gradient:  # (without flags: the call, and so the kernels, of before)
+        if self._slab is not None or self.charge_gradient or self.cell_gradient:  # (without flags: the call, and so the kernels, of before)
             with _lib.on_device(self.device):
                 a = _lib.FramesStepArgs(
                     plan=self._plan.handle, stream=_lib.current_stream(self.device), dtype=self._dt, n_frames=self.n_frames,
@@ -718,7 +771,12 @@ class GraphedFrameBatch:
                     G_stride=self._G.shape[1], rho_mesh_all=self._rho.data_ptr(), hat_work_all=self._hat.data_ptr(),
                     phi_mesh_all=self._phi.data_ptr(), dc_all=self._dc.data_ptr(), cell_work=_lib.ptr(self._cell_work),
                     cell_gradient=int(self.cell_gradient))
-                _lib.check(_lib.load().mipme_frames_step(C.byref(a)))
+                if self._slab is not None:
+                    s = _lib.FramesSlabStepArgs(step=a, slab=self._slab, slab_work=self._slab_work.data_ptr(),
+                                                slab_work_stride=self._slab_stride)
+                    _lib.check(_lib.load().mipme_frames_slab_step(C.byref(s)))
+                else:
+                    _lib.check(_lib.load().mipme_frames_step(C.byref(a)))
             return
         with _lib.on_device(self.device):
             _lib.check(_lib.load().mipme_frames_forward(
