@@ -7,7 +7,7 @@
 //   direct        B = 1/r^3,                              C = 3/r^5
 //   short range   B = erfc(y)/r^3 + kap e/r^2,            C = 3 erfc(y)/r^5 + kap (2 alpha + 3/r^2) e/r^2
 //   long range    B = erf(y)/r^3 - kap e/r^2,             C = 3 erf(y)/r^5 - kap (2 alpha + 3/r^2) e/r^2
-//   exclusion     -f_c(r) T_lr(r)
+//   exclusion     -f_c(r) T_lr(r)                         (T_lr from a power series for alpha r^2 < 4: dipole_lr_series)
 // with alpha = 1/(2 sigma^2), y = sqrt(alpha) r, e = exp(-alpha r^2), kap = 2 sqrt(alpha/pi).  The short-range form is
 // evaluated directly (the reference's from_dist - lr_from_dist cancels in fp32).  B' = -r C for every radial form.
 //   dL/dr_p = prefactor/2 [ (B'/r)(a.b) r - (C'/r)(a.r)(b.r) r - C ((b.r) a + (a.r) b) ]  for a = g_i, b = mu_j (+ g_j, mu_i)
@@ -30,6 +30,29 @@ namespace mipme {
 
 __device__ __forceinline__ void dipole_phase(float a, float& s, float& c) { sincosf(a, &s, &c); }
 __device__ __forceinline__ void dipole_phase(double a, double& s, double& c) { sincos(a, &s, &c); }
+// sin and cos of the phase k.r.  double: the phase in working precision.  float: the phase is formed and reduced in double --
+// phi = k.r, n = rint(phi 2/pi) (by adding 1.5 2^52, whose low word then holds n), rho = phi - n pi/2 in [-pi/4, pi/4] -- and
+// only rho is rounded to float; then sin(rho), cos(rho) from their degree-7 / degree-8 polynomials (the Cephes sinf / cosf
+// coefficients: 1.3e-7 relative on that interval) and the quadrant swap.  A float phase carries an absolute error of
+// |k.r| 2^-24 (4e-6 at |k.r| = 70): that was the accuracy limit of every float sum over k here, and next to a zero of cos or
+// sin it left them no relative accuracy at all; this way both are good to 1.3e-7 of themselves.  (pi/2 as one double: n times
+// its 6e-17 is below 2^-24 |rho| unless |rho| < 4e-9 n.)
+__device__ __forceinline__ void dipole_phase3(double kx, double ky, double kz, double x, double y, double z, double& s,
+                                              double& c) {
+  sincos(kx * x + ky * y + kz * z, &s, &c);
+}
+__device__ __forceinline__ void dipole_phase3(float kx, float ky, float kz, float x, float y, float z, float& s, float& c) {
+  constexpr double magic = 6755399441055744.0;  // 1.5 * 2^52
+  const double phi = __builtin_fma(double(kx), double(x), __builtin_fma(double(ky), double(y), double(kz) * double(z)));
+  const double t = __builtin_fma(phi, 0.63661977236758134308, magic);
+  const int q = __double2loint(t);
+  const float r = float(__builtin_fma(t - magic, -1.5707963267948966, phi)), z2 = r * r;
+  const float sn = r + r * z2 * ((-1.9515295891e-4f * z2 + 8.3321608736e-3f) * z2 - 1.6666654611e-1f);
+  const float cs = 1.0f - 0.5f * z2 + z2 * z2 * ((2.443315711809948e-5f * z2 - 1.388731625493765e-3f) * z2 + 4.166664568298827e-2f);
+  const float a = (q & 1) ? cs : sn, b = (q & 1) ? sn : cs;  // sin, cos up to sign
+  s = __uint_as_float(__float_as_uint(a) ^ ((unsigned(q) & 2u) << 30));
+  c = __uint_as_float(__float_as_uint(b) ^ ((unsigned(q + 1) & 2u) << 30));
+}
 __device__ __forceinline__ float dipole_erf(float y) { return erff(y); }
 __device__ __forceinline__ double dipole_erf(double y) { return erf(y); }
 __device__ __forceinline__ float dipole_exp(float x) { return expf(x); }
@@ -60,11 +83,39 @@ static int make_dippot(const mipme_dipole_t* pot, DipPot<T>& d) {
   return MIPME_OK;
 }
 
-// B, C of the pair tensor at distance r (r2 = r^2, ri = 1/r); with GRAD also dB = B'/r and dC = C'/r
-template <typename T, bool GRAD>
+// The long-range functions for x = alpha r^2 < 4 from the power series of the regularised lower incomplete gamma function,
+//   P(a, x) = x^a e^-x S(a),  S(a) = sum_{k>=0} x^k / Gamma(a + k + 1),  S(a) = 1 / Gamma(a + 1) + x S(a + 1):
+//   B_lr = P(3/2, x)/r^3 = alpha^(3/2) e^-x S(3/2),  C_lr = 3 P(5/2, x)/r^5 = 3 alpha^(5/2) e^-x S(5/2),
+//   C_lr'/r = -15 P(7/2, x)/r^7 = -15 alpha^(7/2) e^-x S(7/2)
+// (x^a / r^(2a) = alpha^a: no negative power of r, every term positive).  The erf forms below are differences whose leading
+// terms cancel to order y^2, y^4, y^6: at y = 0.1 they left C with 5e-3 and C' with no correct digit in fp32, 4e-12 and 9e-10 in
+// fp64.  One series, S(7/2), with the two others from the recurrence; term ratio x / (7/2 + k) < 8/9: 18 (float) / 32 (double)
+// terms reach the rounding level at x = 4.  Below y = 2 the erf forms are also the less accurate ones for C' in fp32 (5e-6 on
+// 1 <= y < 2), which is why the switch is not at x = 1 as in lower_gamma_series.
+template <typename T>
+__device__ __forceinline__ void dipole_lr_series(const DipPot<T>& P, T x, T e, T& B, T& C, T& dC) {
+  constexpr int K = sizeof(T) == 4 ? 18 : 32;
+  constexpr double ig52 = 0.75225277806367505, ig72 = 0.30090111122547002, ig92 = 0.085971746064420005;  // 1 / Gamma(a)
+  T term = T(1), sum = T(1);
+#pragma unroll
+  for (int k = 1; k <= K; ++k) {
+    term *= x * T(1.0 / (3.5 + k));
+    sum += term;
+  }
+  const T s72 = T(ig92) * sum, s52 = T(ig72) + x * s72, s32 = T(ig52) + x * s52;
+  const T a = P.alpha, a32e = a * P.sqrt_alpha * e;
+  B = a32e * s32;
+  C = T(3) * a * a32e * s52;
+  dC = T(-15) * a * a * a32e * s72;
+}
+
+// B, C of the pair tensor at distance r (r2 = r^2, ri = 1/r); with GRAD also dB = B'/r and dC = C'/r.  EXCL: the exclusion
+// variant (mode 2) -- an instantiation of its own, so that the series and the switch stay out of the instruction stream of
+// the direct and the short-range form.
+template <typename T, bool GRAD, bool EXCL>
 __device__ __forceinline__ void dipole_bc(const DipPot<T>& P, T r2, T ri, T& B, T& C, T& dB, T& dC) {
   const T ri2 = ri * ri, ri3 = ri2 * ri, ri5 = ri3 * ri2;
-  if (P.mode == 0) {
+  if (!EXCL && P.mode == 0) {
     B = ri3;
     C = T(3) * ri5;
     if (GRAD) {
@@ -73,25 +124,30 @@ __device__ __forceinline__ void dipole_bc(const DipPot<T>& P, T r2, T ri, T& B, 
     }
     return;
   }
-  const T r = r2 * ri, y = P.sqrt_alpha * r, e = dipole_exp(-P.alpha * r2);
-  // w = erfc(y) with kap as it is (short range), or w = erf(y) with kap negated (long range, exclusion variant)
-  T w, kap;
-  if (P.mode == 1) {
-    w = erfc_from_exp(y, e);
-    kap = P.kap;
-  } else {
-    w = dipole_erf(y);
-    kap = -P.kap;
-  }
-  const T ke = kap * e, a = P.alpha;
-  B = w * ri3 + ke * ri2;
-  C = T(3) * w * ri5 + ke * (T(2) * a * ri2 + T(3) * ri2 * ri2);
-  if (GRAD) {
-    // B' = -r C;  C' = -15 w/r^6 - kap e (15/r^5 + 10 alpha/r^3 + 4 alpha^2/r)
+  const T r = r2 * ri, x = P.alpha * r2, y = P.sqrt_alpha * r, e = dipole_exp(-x);
+  if (EXCL && x < T(4)) {
+    dipole_lr_series<T>(P, x, e, B, C, dC);
     dB = -C;
-    dC = T(-15) * w * ri5 * ri2 - ke * ri2 * (T(15) * ri2 * ri2 + T(10) * a * ri2 + T(4) * a * a);
+  } else {
+    // w = erfc(y) with kap as it is (short range), or w = erf(y) with kap negated (long range, exclusion variant)
+    T w, kap;
+    if (!EXCL) {
+      w = erfc_from_exp(y, e);
+      kap = P.kap;
+    } else {
+      w = dipole_erf(y);
+      kap = -P.kap;
+    }
+    const T ke = kap * e, a = P.alpha;
+    B = w * ri3 + ke * ri2;
+    C = T(3) * w * ri5 + ke * (T(2) * a * ri2 + T(3) * ri2 * ri2);
+    if (GRAD) {
+      // B' = -r C;  C' = -15 w/r^6 - kap e (15/r^5 + 10 alpha/r^3 + 4 alpha^2/r)
+      dB = -C;
+      dC = T(-15) * w * ri5 * ri2 - ke * ri2 * (T(15) * ri2 * ri2 + T(10) * a * ri2 + T(4) * a * a);
+    }
   }
-  if (P.mode == 2) {
+  if (EXCL) {
     T fc = T(0), dfc = T(0);  // f_c and f_c'/r
     if (r < P.rx) {
       const T arg = T(kDipPi) * r / P.rx;
@@ -119,7 +175,7 @@ __device__ __forceinline__ void dipole_pair(const I* __restrict__ pairs, int64_t
 }
 
 // V_i += T mu_j / 2 (and V_j += T mu_i / 2 for a half list).  Also the dipole gradient: the same sum applied to g.
-template <typename T, typename I>
+template <typename T, typename I, bool EXCL>
 __global__ __launch_bounds__(256) void dipole_rspace_kernel(DipPot<T> P, int64_t n_pairs, bool full,
                                                            const I* __restrict__ pairs, const T* __restrict__ vec,
                                                            const T* __restrict__ mu, T* __restrict__ out) {
@@ -130,7 +186,7 @@ __global__ __launch_bounds__(256) void dipole_rspace_kernel(DipPot<T> P, int64_t
     const T r2 = rx * rx + ry * ry + rz * rz;
     const T ri = T(1) / fsqrt(r2);
     T B, C, dB, dC;
-    dipole_bc<T, false>(P, r2, ri, B, C, dB, dC);
+    dipole_bc<T, false, EXCL>(P, r2, ri, B, C, dB, dC);
     const T hb = T(0.5) * P.pref * B, hc = T(0.5) * P.pref * C;
     {
       const T mx = mu[3 * j], my = mu[3 * j + 1], mz = mu[3 * j + 2];
@@ -161,7 +217,7 @@ __device__ __forceinline__ void dipole_pair_grad(T rx, T ry, T rz, T C, T dB, T 
 }
 
 // dL/d neighbor_vectors for L = sum_i g_i . V_i
-template <typename T, typename I>
+template <typename T, typename I, bool EXCL>
 __global__ __launch_bounds__(256) void dipole_rspace_grad_vectors_kernel(DipPot<T> P, int64_t n_pairs, bool full,
                                                                         const I* __restrict__ pairs,
                                                                         const T* __restrict__ vec,
@@ -175,7 +231,7 @@ __global__ __launch_bounds__(256) void dipole_rspace_grad_vectors_kernel(DipPot<
     const T r2 = rx * rx + ry * ry + rz * rz;
     const T ri = T(1) / fsqrt(r2);
     T B, C, dB, dC;
-    dipole_bc<T, true>(P, r2, ri, B, C, dB, dC);
+    dipole_bc<T, true, EXCL>(P, r2, ri, B, C, dB, dC);
     T gx = T(0), gy = T(0), gz = T(0);
     dipole_pair_grad<T>(rx, ry, rz, C, dB, dC, g[3 * i], g[3 * i + 1], g[3 * i + 2], mu[3 * j], mu[3 * j + 1],
                         mu[3 * j + 2], gx, gy, gz);
@@ -237,7 +293,7 @@ __global__ __launch_bounds__(256) void dipole_structure_kernel(int64_t N, int64_
     if (live)
       for (int i = al; i < n; i += kDipLanes) {
         T s, c;
-        dipole_phase(kx * sp[3 * i] + ky * sp[3 * i + 1] + kz * sp[3 * i + 2], s, c);
+        dipole_phase3(kx, ky, kz, sp[3 * i], sp[3 * i + 1], sp[3 * i + 2], s, c);
         const T q = kx * sw[3 * i] + ky * sw[3 * i + 1] + kz * sw[3 * i + 2];
         ac += q * c;
         as += q * s;
@@ -297,7 +353,7 @@ __global__ __launch_bounds__(256) void dipole_atom_kernel(int64_t K, int64_t chu
     if (gk == T(0)) continue;  // exact: the term is G(k) times a finite sum
     const T kx = kvec[3 * k], ky = kvec[3 * k + 1], kz = kvec[3 * k + 2];
     T s, c;
-    dipole_phase(kx * x + ky * y + kz * z, s, c);
+    dipole_phase3(kx, ky, kz, x, y, z, s, c);
     T b;
     if (GRAD)
       b = gk * ((gx * kx + gy * ky + gz * kz) * (c * Ss[k] - s * Sc[k]) +
@@ -365,7 +421,7 @@ __global__ __launch_bounds__(256) void dipole_grad_kvectors_kernel(int64_t N, in
         const T mx = sm[3 * i], my = sm[3 * i + 1], mz = sm[3 * i + 2];
         const T gx = sg[3 * i], gy = sg[3 * i + 1], gz = sg[3 * i + 2];
         T s, c;
-        dipole_phase(kx * x + ky * y + kz * z, s, c);
+        dipole_phase3(kx, ky, kz, x, y, z, s, c);
         const T a1 = c * lSc + s * lSs, a2 = c * lTc + s * lTs;
         const T b = (gx * kx + gy * ky + gz * kz) * (c * lSs - s * lSc) + (mx * kx + my * ky + mz * kz) * (c * lTs - s * lTc);
         ax += gx * a1 + mx * a2 + b * x;
@@ -404,6 +460,18 @@ static inline unsigned dipole_pair_grid(int64_t P) {
   return unsigned(std::max<int64_t>(1, std::min<int64_t>(b, 256 * 16)));
 }
 
+// the pair sum with the instantiation of the descriptor's mode (see dipole_bc)
+template <typename T, typename I>
+static void dipole_rspace_launch(hipStream_t st, const DipPot<T>& dp, int64_t P, bool full, const void* pairs,
+                                 const void* vec, const void* mu, void* out) {
+  if (dp.mode == 2)
+    dipole_rspace_kernel<T, I, true><<<dipole_pair_grid(P), 256, 0, st>>>(dp, P, full, (const I*)pairs, (const T*)vec,
+                                                                          (const T*)mu, (T*)out);
+  else
+    dipole_rspace_kernel<T, I, false><<<dipole_pair_grid(P), 256, 0, st>>>(dp, P, full, (const I*)pairs, (const T*)vec,
+                                                                           (const T*)mu, (T*)out);
+}
+
 template <typename T, typename I>
 static int dipole_rspace_forward_t(hipStream_t st, int64_t N, int64_t P, int full, const void* pairs, const void* vec,
                                    const void* mu, const mipme_dipole_t* pot, void* out) {
@@ -412,8 +480,7 @@ static int dipole_rspace_forward_t(hipStream_t st, int64_t N, int64_t P, int ful
   if (rc) return rc;
   MIPME_CHECK_HIP(zero_async(out, sizeof(T) * size_t(N) * 3, st));
   if (P == 0) return MIPME_OK;
-  dipole_rspace_kernel<T, I><<<dipole_pair_grid(P), 256, 0, st>>>(dp, P, full != 0, (const I*)pairs, (const T*)vec,
-                                                                  (const T*)mu, (T*)out);
+  dipole_rspace_launch<T, I>(st, dp, P, full != 0, pairs, vec, mu, out);
   MIPME_LAUNCH_CHECK();
   return MIPME_OK;
 }
@@ -428,14 +495,17 @@ static int dipole_rspace_backward_t(hipStream_t st, int64_t N, int64_t P, int fu
   if (grad_mu) {  // T is symmetric and even in r: the dipole gradient is the forward sum applied to g
     MIPME_CHECK_HIP(zero_async(grad_mu, sizeof(T) * size_t(N) * 3, st));
     if (P > 0) {
-      dipole_rspace_kernel<T, I><<<dipole_pair_grid(P), 256, 0, st>>>(dp, P, full != 0, (const I*)pairs, (const T*)vec,
-                                                                      (const T*)g, (T*)grad_mu);
+      dipole_rspace_launch<T, I>(st, dp, P, full != 0, pairs, vec, g, grad_mu);
       MIPME_LAUNCH_CHECK();
     }
   }
   if (grad_vec && P > 0) {
-    dipole_rspace_grad_vectors_kernel<T, I><<<dipole_pair_grid(P), 256, 0, st>>>(
-        dp, P, full != 0, (const I*)pairs, (const T*)vec, (const T*)mu, (const T*)g, (T*)grad_vec);
+    if (dp.mode == 2)
+      dipole_rspace_grad_vectors_kernel<T, I, true><<<dipole_pair_grid(P), 256, 0, st>>>(
+          dp, P, full != 0, (const I*)pairs, (const T*)vec, (const T*)mu, (const T*)g, (T*)grad_vec);
+    else
+      dipole_rspace_grad_vectors_kernel<T, I, false><<<dipole_pair_grid(P), 256, 0, st>>>(
+          dp, P, full != 0, (const I*)pairs, (const T*)vec, (const T*)mu, (const T*)g, (T*)grad_vec);
     MIPME_LAUNCH_CHECK();
   }
   return MIPME_OK;
