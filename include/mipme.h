@@ -884,6 +884,80 @@ int mipme_combined_sr_eval(void* stream, int dtype, const mipme_combined_t* comb
                            const void* d, const void* weights, void* out);
 int mipme_combined_kfilter_build(void* stream, int dtype, const mipme_mesh_t* mesh, const mipme_combined_t* comb, void* out);
 
+/* Energy + forces step of a RANGE-SEPARATED combination (every term smearing > 0), the MD form: everything is linear in the
+ * potential, so the mesh part is ONE pass with the contracted table G = sum_t w_t G_t, the pair part ONE walk over the row
+ * stream with sum_t w_t v_t(d), and dE/dw_t is the energy of term t alone.  With V the potentials the eager calculator returns,
+ * c = 1/2, c' = 1/2 for a full list and 1 otherwise, s = grad_seed[0] (NULL = 1), Q = sum_a q_a, and self_t / bg_t the self and
+ * background constants of term t (potentials/coulomb.py:144-158, potentials/inversepowerlaw.py:143-166):
+ *   V_sr[a]            = c sum_e q_o sum_t w_t v_t(d_e)                    (roles of the entries: as mipme_sr_rows_fused in its
+ *   pair_force[a]      = -sum_e q_o (sum_t w_t v_t'(d_e) / d_e) vec_e       potential + force-sum mode)
+ *   u_t[a]             = c sum_e q_o v_t(d_e)
+ *   potentials[a]      = V_a = V_sr[a] + 1/2 (phi_a - q_a sum_t w_t self_t - 2 (sum_t w_t bg_t) Q / V)
+ *   energy             = sum_a q_a V_a
+ *   grad_positions[a]  = s q_a (c' pair_force[a] + field[a])
+ *   grad_charges[a]    = 2 V_a      (half lists: a full list need not be symmetric, hence refused as for out_grad_charges)
+ *   grad_weights[t]    = sum_a q_a u_t[a] + (1/2V) sum_k mu_k G_t(k) |rho^(k)|^2 - 1/2 self_t sum_a q_a^2 - bg_t Q^2 / V
+ * (phi_a: the raw gather / V of the mesh pass; mu_k: 2, except 1 on the kz = 0 and kz = nz/2 planes of the half grid, as in the
+ * energy partials described at out_energy above).
+ * Launches, one after the other on `stream` (capturable; nothing runs beside anything else): the contraction of the tables and
+ * of the constants; the mesh part exactly as mipme_kspace_forward runs it (binning, spread, fused convolution, gather with the
+ * field) with G; the combined pair rows (16 lanes per row, the 7^3 shift table in LDS, one record gather per entry, a uniform
+ * loop over the terms); with grad_weights one pass over rho^ for all terms; one finish launch.  Sums are float64 block partials
+ * added up in a fixed order; no atomics in these kernels.  The weights are read from device memory by every kernel and never
+ * by the host.
+ * Buffers: weights (n_terms values of `dtype`); G_terms (n_terms, nx, ny, nz/2+1) from mipme_combined_kfilter_build; G (one
+ * half grid, written); rho_mesh / hat_work / phi_mesh / dc / atom_bins as for mipme_kspace_forward (atom_bins: required where
+ * mipme_atom_bins_bytes is > 0; a mesh too small for bricks takes the kernels without bins, and `field` is then scratch that
+ * holds q_a field[a]); records (4N reals, 16-byte aligned, written); rho_hat (complex half grid, written; needed with
+ * grad_weights only); row_ptr int32[2N+1] and entries int32[2P+1] = other | code << 22 (shift_format 2, the only one served);
+ * cell (3,3) device copy in `dtype`; work: float64[the value of mipme_combined_step_work] of scratch; nan_flag as for
+ * mipme_kspace_forward.
+ * MIPME_EINVAL before anything is launched: a NULL required buffer, n_terms outside 1..8, a direct term, another shift format,
+ * more than one channel, a mesh whose nx is no power of two (or a plan that does not match the mesh), grad_charges with a full
+ * list, grad_weights without rho_hat.  The struct is versioned like the arguments of mipme_kspace_forward: size and version
+ * first, fields only ever appended. */
+#define MIPME_COMBINED_STEP_VERSION 1
+typedef struct mipme_combined_step_args {
+  uint32_t size;
+  uint32_t version;
+  mipme_fft_plan* plan;
+  void* stream;
+  int32_t dtype;
+  int32_t full_list;
+  const mipme_mesh_t* mesh;
+  const mipme_combined_t* comb;
+  int64_t n_atoms;
+  const void* positions;
+  const void* charges;
+  const void* cell;
+  const void* weights;
+  const void* G_terms;
+  void* G;
+  void* rho_mesh;
+  void* hat_work;
+  void* phi_mesh;
+  void* dc;
+  void* atom_bins;
+  void* records;
+  void* rho_hat;
+  const void* row_ptr;
+  const void* entries;
+  int32_t shift_format;
+  int32_t _pad;
+  void* potentials;
+  void* pair_force;
+  void* field;
+  void* energy;
+  void* grad_positions;
+  const void* grad_seed;
+  void* grad_weights;
+  void* grad_charges;
+  void* work;
+  void* nan_flag;
+} mipme_combined_step_args_t;
+int mipme_combined_step(const mipme_combined_step_args_t* args);
+int64_t mipme_combined_step_work(const mipme_fft_plan* plan, const mipme_mesh_t* mesh, int64_t n_atoms, int n_terms);
+
 /* ---- device neighbour list (the reference uses third-party vesin on the host,
  * tests/helpers.py:240-275, and hands a fresh list to every call, examples/02-neighbor-lists-usage.py:97-164) -------------
  * One cell-list traversal, two products:

@@ -43,6 +43,7 @@ EXPORTS = (
     "mipme_dipole_field", "mipme_dipole_backward",
     "mipme_spline_eval", "mipme_spline_eval_reciprocal", "mipme_spline_kfilter_build",
     "mipme_combined_sr_eval", "mipme_combined_kfilter_build",
+    "mipme_combined_step", "mipme_combined_step_work",
 )
 
 
@@ -295,6 +296,33 @@ class FramesSlabStepArgs(_VersionedArgs):
         C.Structure.__init__(self, size=C.sizeof(type(self)), version=FRAMES_SLAB_STEP_VERSION, **fields)
 
 
+COMBINED_STEP_VERSION = 1
+
+
+class CombinedStepArgs(_VersionedArgs):
+    """``mipme_combined_step_args_t`` (version ``MIPME_COMBINED_STEP_VERSION``)"""
+
+    _fields_ = [
+        ("size", C.c_uint32), ("version", C.c_uint32),
+        ("plan", C.c_void_p), ("stream", C.c_void_p), ("dtype", C.c_int32), ("full_list", C.c_int32),
+        ("mesh", C.POINTER(MeshDesc)), ("comb", C.POINTER(CombinedDesc)), ("n_atoms", C.c_int64),
+        ("positions", C.c_void_p), ("charges", C.c_void_p), ("cell", C.c_void_p), ("weights", C.c_void_p),
+        ("G_terms", C.c_void_p), ("G", C.c_void_p),
+        ("rho_mesh", C.c_void_p), ("hat_work", C.c_void_p), ("phi_mesh", C.c_void_p), ("dc", C.c_void_p),
+        ("atom_bins", C.c_void_p), ("records", C.c_void_p), ("rho_hat", C.c_void_p),
+        ("row_ptr", C.c_void_p), ("entries", C.c_void_p), ("shift_format", C.c_int32), ("_pad", C.c_int32),
+        ("potentials", C.c_void_p), ("pair_force", C.c_void_p), ("field", C.c_void_p), ("energy", C.c_void_p),
+        ("grad_positions", C.c_void_p), ("grad_seed", C.c_void_p), ("grad_weights", C.c_void_p), ("grad_charges", C.c_void_p),
+        ("work", C.c_void_p), ("nan_flag", C.c_void_p),
+    ]
+
+    def __init__(self, **fields):
+        unknown = set(fields) - {name for name, _ in self._fields_}
+        if unknown:
+            raise TypeError(f"{type(self).__name__}: unknown field(s) {sorted(unknown)}")
+        C.Structure.__init__(self, size=C.sizeof(type(self)), version=COMBINED_STEP_VERSION, **fields)
+
+
 #: OR-ed into a shift format: rows written by ``mipme_nl_stream`` (``row_ptr`` int32[3N+1], every neighbour once per row)
 ROWS_PADDED = 0x100
 FWD_RHO_MESH_UNUSED = 1  # mipme_kspace_forward_args_t.flags: the caller never reads rho_mesh after the call
@@ -367,6 +395,7 @@ def _declare(lib):
         "mipme_spline_kfilter_build": [vp, ci, MP, C.POINTER(SplineDesc), vp],
         "mipme_combined_sr_eval": [vp, ci, C.POINTER(CombinedDesc), ci, C.POINTER(dbl), i64, vp, vp, vp],
         "mipme_combined_kfilter_build": [vp, ci, MP, C.POINTER(CombinedDesc), vp],
+        "mipme_combined_step": [C.POINTER(CombinedStepArgs)],
         "mipme_dot_forward": [vp, ci, i64, vp, vp, vp, vp],
         "mipme_dot_backward": [vp, ci, i64, vp, vp, vp, vp, vp],
         "mipme_energy_log_push": [vp, ci, ci, vp, vp, vp, ci],
@@ -436,6 +465,8 @@ def _declare(lib):
     lib.mipme_fft_plan_kgrid_blocks.argtypes = [vp]
     lib.mipme_frames_cell_work.restype = i64
     lib.mipme_frames_cell_work.argtypes = [MP, i64]
+    lib.mipme_combined_step_work.restype = i64
+    lib.mipme_combined_step_work.argtypes = [vp, MP, i64, ci]
     lib.mipme_frames_slab_work.restype = i64
     lib.mipme_frames_slab_work.argtypes = []
     lib.mipme_frames_table_bytes.restype = i64

@@ -810,3 +810,179 @@ class GraphedFrameBatch:
         if self.cell_gradient:
             out += (self.cell_grads,)
         return out
+
+
+def _combined_refusal(pot) -> str | None:
+    """Why ``combined.plan`` does not serve this combination in the graphed step (``None``: it does)."""
+    from .potentials import CombinedPotential, CoulombPotential, InversePowerLawPotential, SplinePotential
+
+    members = list(pot.potentials)
+    if len(members) > _lib.COMBINED_MAX_TERMS:
+        return f"it has {len(members)} members, the kernels take at most {_lib.COMBINED_MAX_TERMS}"
+    for k, m in enumerate(members):
+        if isinstance(m, CombinedPotential):
+            return f"member {k} is itself a CombinedPotential (nested combinations are not served)"
+        if isinstance(m, SplinePotential):
+            return f"member {k} is a SplinePotential; the kernels know CoulombPotential and InversePowerLawPotential members"
+        if type(m) not in (CoulombPotential, InversePowerLawPotential):
+            return (f"member {k} is a {type(m).__name__}; the kernels know exactly CoulombPotential and "
+                    "InversePowerLawPotential members")
+        if m.exclusion_radius is not None:
+            return f"member {k} has an exclusion radius"
+    if any(m.smearing is None for m in members):
+        return "its members are direct potentials (`smearing=None`): the step is the range-separated mesh calculation"
+    return None
+
+
+class GraphedCombinedStep:
+    """``E, F, dE_dw = step(positions)`` for a calculator with a :class:`~torchpme_amd.CombinedPotential` -- Coulomb +
+    dispersion, or any weighted sum of range-separated 1/r^p terms -- replayed from one HIP graph: the MD form of the eager call.
+
+    With ``V`` the potentials the eager calculator returns for the same arguments and ``w`` the potential's ``weights``:
+    ``E = sum_a q_a V_a`` (0-dim), ``F = -dE/dpositions`` (N, 3), ``dE_dw = dE/dweights`` (n_terms,) with ``weight_gradient``, and
+    behind it ``dE_dq = 2 V`` (N, 1) with ``charge_gradient`` (half lists only).  All of them are buffers of the object,
+    overwritten by every call.  Everything is linear in the potential: the mesh part is one pass with the contracted table
+    ``sum_t w_t G_t``, the pair part one walk over the rows with ``sum_t w_t v_t(d)``, and ``dE/dw_t`` is the energy of member t
+    alone (``mipme_combined_step``, csrc/combined_step.hip).
+
+    The weights are followed without a new capture: every call copies ``calculator.potential.weights`` into a device buffer of the
+    object on the current stream just before the replay -- one small device copy, no host read -- so a step of an optimizer on
+    the weights is seen by the next call.
+
+    :param calculator: a :class:`PMECalculator` / :class:`P3MCalculator` whose potential is a combination ``combined.plan``
+        serves with range-separated members: exactly ``CoulombPotential`` / ``InversePowerLawPotential`` members without an
+        exclusion radius, at most 8 of them
+    :param charges: (N, 1); the step reads this tensor in every call
+    :param neighbor_indices, neighbor_shifts: an explicit half or full list (``calculator.full_neighbor_list``) whose cell shifts
+        are integers in [-3, 3]
+    :param weight_gradient: also return ``dE/dweights`` (one pass over the transformed charge mesh more per call)
+    :param charge_gradient: also return ``dE/dcharges``; refused for a full list, which need not be symmetric
+    """
+
+    def __init__(self, calculator, charges, cell, positions, neighbor_indices, neighbor_shifts, weight_gradient: bool = True,
+                 charge_gradient: bool = False, warmup: int = 3):
+        from . import analytic, combined
+        from .potentials import CombinedPotential
+
+        pot = getattr(calculator, "potential", None)
+        if not isinstance(pot, CombinedPotential):
+            raise TypeError(f"GraphedCombinedStep serves a calculator with a CombinedPotential, got a {type(pot).__name__}: "
+                            "use GraphedEnergyForces for a single potential")
+        why = _combined_refusal(pot)
+        self._plan_c = combined.plan(pot) if why is None else None
+        if why is None and self._plan_c is None:
+            why = "its members are not all range separated or all direct"
+        if why is not None:
+            raise TypeError(f"GraphedCombinedStep does not serve this CombinedPotential: {why}; call the calculator eagerly")
+        if not hasattr(calculator, "mesh_spacing"):
+            raise TypeError(f"GraphedCombinedStep needs a PMECalculator or a P3MCalculator, got a {type(calculator).__name__}")
+        if charges.dim() != 2 or charges.shape[1] != 1:
+            raise ValueError(f"GraphedCombinedStep handles a single charge channel, got charges of shape {tuple(charges.shape)}")
+        for t, name in ((positions, "positions"), (charges, "charges"), (cell, "cell"), (neighbor_indices, "neighbor_indices"),
+                        (neighbor_shifts, "neighbor_shifts")):
+            _lib.require_device(t, name)
+        self.calc = calculator
+        self.weight_gradient, self.charge_gradient = bool(weight_gradient), bool(charge_gradient)
+        self.full = bool(calculator.full_neighbor_list)
+        if self.charge_gradient and self.full:
+            raise ValueError("GraphedCombinedStep: `charge_gradient` (dE/dq = 2 V) needs a half list: a full list need not be "
+                             "symmetric")
+        lib = self._lib = _lib.load()
+        device, dtype = positions.device, positions.dtype
+        self.device, self.dtype, self._dt = device, dtype, _lib.dtype_code(dtype)
+        N = self.n_atoms = positions.shape[0]
+        T = self.n_terms = self._plan_c.n_terms
+        geom = self._geom = analytic._geometry(calculator, cell)
+        geom.plan_store = calculator._plan_store
+        self._tables = analytic._combined_tables(calculator, self._plan_c, cell, geom, dtype)
+        self._md = geom.desc(1)
+        self._plan = _lib.get_plan(device, dtype, geom.ns, 1, geom.plan_store)
+        if not self._plan.xfused:
+            raise ValueError(f"GraphedCombinedStep needs a power-of-two mesh along x, the cell gives {geom.ns}")
+        new = lambda *shape, dt=dtype: torch.empty(shape, dtype=dt, device=device)  # noqa: E731
+        cdtype = torch.complex64 if dtype == torch.float32 else torch.complex128
+        self.q = charges.detach().contiguous()
+        self.cell = cell.detach().to(dtype).contiguous()
+        self.pos = positions.detach().clone().contiguous()
+        self._w = new(T)
+        self._G = new(*self._tables.shape[1:])
+        self._rho, self._phi = new(*geom.ns), new(*geom.ns)
+        self._hat = new(geom.n_half, dt=cdtype)
+        self._rho_hat = new(geom.n_half, dt=cdtype) if self.weight_gradient else None
+        self._dc = new(1)
+        nbytes = int(lib.mipme_atom_bins_bytes(C.byref(self._md), N, self._dt))
+        self._bins = new(nbytes, dt=torch.uint8) if nbytes > 0 else None  # (None: a mesh too small for bricks)
+        self._rec = new(N, 4)
+        self.potentials, self._pair_force, self._field = new(N), new(N, 3), new(N, 3)
+        self.energy, self.forces = new(), new(N, 3)
+        self.weight_grad = new(T) if self.weight_gradient else None
+        self.charge_grad = new(N, 1) if self.charge_gradient else None
+        self._minus_one = torch.tensor(-1.0, dtype=dtype, device=device)
+        self._work = new(int(lib.mipme_combined_step_work(self._plan.handle, C.byref(self._md), N, T)), dt=torch.float64)
+        self._nan_flag = calculator._nan_flag_ptr()
+        calculator._nan_shape = [1, *geom.ns]
+        self._warmup = max(1, int(warmup))
+        self._capture(neighbor_indices, neighbor_shifts)
+
+    def _capture(self, neighbor_indices, neighbor_shifts):
+        device, N = self.device, self.n_atoms
+        self.pairs = neighbor_indices
+        sh = neighbor_shifts.to(self.dtype).contiguous()
+        topo = ops.get_topology(neighbor_indices, N)
+        ent32 = topo.compact_entries(sh, neighbor_shifts)
+        if ent32 is None:
+            raise ValueError("GraphedCombinedStep: the cell shifts must be integers in [-3, 3] (the 4-byte pair entries of the "
+                             "row kernel) and the system at most 2^22 atoms")
+        self._row_ptr, self._ent32 = topo.row_ptr, ent32
+        # the captured graph holds raw pointers into cached buffers (transposed list, entry stream, the members' tables, the plan)
+        self._keepalive = [topo, topo.row_ptr, ent32, sh, self._tables, self._plan, self._geom, getattr(self.calc, "_plan_store", None)]
+        side = torch.cuda.Stream(device)
+        side.wait_stream(torch.cuda.current_stream(device))
+        with torch.cuda.stream(side):  # warm-up off the default stream: the plan allocates its scratch on first use
+            self._w.copy_(self.calc.potential.weights.detach())
+            for _ in range(self._warmup):
+                self._launch()
+        torch.cuda.current_stream(device).wait_stream(side)
+        torch.cuda.synchronize(device)
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph):
+            self._launch()
+
+    def _launch(self):
+        with _lib.on_device(self.device):
+            a = _lib.CombinedStepArgs(
+                plan=self._plan.handle, stream=_lib.current_stream(self.device), dtype=self._dt, full_list=int(self.full),
+                mesh=C.pointer(self._md), comb=C.pointer(self._plan_c.desc), n_atoms=self.n_atoms, positions=self.pos.data_ptr(),
+                charges=self.q.data_ptr(), cell=self.cell.data_ptr(), weights=self._w.data_ptr(),
+                G_terms=self._tables.data_ptr(), G=self._G.data_ptr(), rho_mesh=self._rho.data_ptr(),
+                hat_work=self._hat.data_ptr(), phi_mesh=self._phi.data_ptr(), dc=self._dc.data_ptr(),
+                atom_bins=_lib.ptr(self._bins), records=self._rec.data_ptr(), rho_hat=_lib.ptr(self._rho_hat),
+                row_ptr=self._row_ptr.data_ptr(), entries=self._ent32.data_ptr(), shift_format=2,
+                potentials=self.potentials.data_ptr(), pair_force=self._pair_force.data_ptr(), field=self._field.data_ptr(),
+                energy=self.energy.data_ptr(), grad_positions=self.forces.data_ptr(), grad_seed=self._minus_one.data_ptr(),
+                grad_weights=_lib.ptr(self.weight_grad), grad_charges=_lib.ptr(self.charge_grad), work=self._work.data_ptr(),
+                nan_flag=self._nan_flag)
+            _lib.check(self._lib.mipme_combined_step(C.byref(a)))
+
+    def recapture(self, neighbor_indices, neighbor_shifts, positions: torch.Tensor | None = None) -> None:
+        """New neighbour list: rebuild the pair topology and capture the step again; every other buffer is kept."""
+        if positions is not None:
+            with torch.no_grad():
+                self.pos.copy_(positions)
+        self._capture(neighbor_indices, neighbor_shifts)
+
+    def __call__(self, positions: torch.Tensor | None = None):
+        """``E, F`` (+ ``dE/dweights`` with ``weight_gradient``, + ``dE/dcharges`` with ``charge_gradient``, in that order) of the
+        current -- or the given -- positions with the weights as they are now: one small copy and one graph replay."""
+        self.calc.check()  # a NaN a previous replay met (pinned word, no synchronisation)
+        with torch.no_grad():
+            if positions is not None:
+                self.pos.copy_(positions)
+            self._w.copy_(self.calc.potential.weights.detach())
+        self.graph.replay()
+        out = (self.energy, self.forces)
+        if self.weight_gradient:
+            out += (self.weight_grad,)
+        if self.charge_gradient:
+            out += (self.charge_grad,)
+        return out
