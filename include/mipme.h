@@ -958,6 +958,72 @@ typedef struct mipme_combined_step_args {
 int mipme_combined_step(const mipme_combined_step_args_t* args);
 int64_t mipme_combined_step_work(const mipme_fft_plan* plan, const mipme_mesh_t* mesh, int64_t n_atoms, int n_terms);
 
+/* Energy, forces and dE/dmu of point dipoles in ONE step, the MD form of CalculatorDipole: GraphedDipoleStep, graphed.py.
+ * With V what the eager calculator returns for vectors r_j - r_i + S cell (the step forms them itself from the rows):
+ *   energy        = E = sum_i mu_i . V_i                        (one value of `dtype`)
+ *   forces        = -dE/dpositions    (N,3)                     (total: pair vectors and reciprocal part)
+ *   grad_dipoles  = dE/ddipoles       (N,3)                     (total: 2 V for a half list; V plus the transposed half for a full one)
+ *   grad_cell     = dE/dcell          (3,3) at fixed Cartesian positions, with cell_gradient
+ * The caller supplies what depends on the cell alone: the COMPACTED k-vectors (n_k, 3) -- k = 0 dropped, one of every +-k pair --
+ * with their multiplicity (2, or 1 where the mirror is not in the grid) folded into G and dG (n_k each; dG = dG/dk^2, read with
+ * cell_gradient only), inv_volume = 1/|det cell|, self_term = prefactor 4 pi/3 (alpha/pi)^(3/2), background = prefactor 4 pi /
+ * (2 epsilon + 1) (0: none), cell (3,3) and inv_cell = cell^-1 (3,3) as device copies in `dtype`.  n_k = 0 with a potential
+ * without smearing: pair rows only.
+ * Launches, one after the other on `stream` (capturable; nothing runs beside anything else):
+ *   records     (x, y, z, -) and (mu_x, mu_y, mu_z, -) of every atom, float64 block partials of sum_j mu_j
+ *   structure   S_c, S_s over the compacted list (mipme_dipole_structure as it is, once)                       [n_k > 0]
+ *   atoms       block per (atom, k slice), one phase per (atom, k): the field G k (c S_c + s S_s) and the position bracket
+ *               G (mu_i.k)(c S_s - s S_c) k, six sums per thread, written as slice partials                    [n_k > 0]
+ *   rows        16 lanes per atom row over row_ptr int32[2N+1] / entries int32[2P+1] = other | code << 22 (shift_format 2,
+ *               the only one served), the 7^3 shift table in LDS, two record gathers per entry: per atom
+ *               c sum_e T(vec_e) mu_o and c sum_e grad_vec (mu_a.T(vec_e).mu_o) over both roles (c = 1, or 1/2 for a full list);
+ *               with cell_gradient float64 block partials of sum_p S_p (x) dE/dvec_p over the role-i entries
+ *   cell k      per-k gradient with g = mu, T = S contracted with k to 3 x 3 float64 block partials          [cell_gradient, n_k > 0]
+ *   finish      per atom: slice partials in slice order, 1/V, self and background terms, + the row results; float64 block
+ *               partials of 1/2 mu_i . dE/dmu_i (E is quadratic in mu)
+ *   final       one block: E and grad_cell from the partials, in index order
+ * No atomics anywhere: every sum has a fixed order.  records: 8 N reals, 16-byte aligned, written; s_cos / s_sin: n_k reals each,
+ * written; work: float64[mipme_dipole_step_work(n_atoms, n_k, cell_gradient)] of scratch (0 for invalid sizes).
+ * MIPME_EINVAL before anything is launched: a NULL struct or required buffer, another struct version, an implausible size, a bad
+ * dtype, a NULL descriptor, n_k > 0 with a potential without smearing, another shift format, n_atoms outside 1..2^22, n_k < 0,
+ * cell_gradient without grad_cell (or without dG when n_k > 0).  Versioned like mipme_combined_step_args_t: size and version
+ * first, fields only ever appended. */
+#define MIPME_DIPOLE_STEP_VERSION 1
+typedef struct mipme_dipole_step_args {
+  uint32_t size;
+  uint32_t version;
+  void* stream;
+  int32_t dtype;
+  int32_t full_list;
+  const mipme_dipole_t* pot;
+  int64_t n_atoms;
+  int64_t n_k;
+  double inv_volume;
+  double self_term;
+  double background;
+  const void* positions;
+  const void* dipoles;
+  const void* cell;
+  const void* inv_cell;
+  const void* kvectors;
+  const void* G;
+  const void* dG;
+  const void* row_ptr;
+  const void* entries;
+  int32_t shift_format;
+  int32_t cell_gradient;
+  void* records;
+  void* s_cos;
+  void* s_sin;
+  void* energy;
+  void* forces;
+  void* grad_dipoles;
+  void* grad_cell;
+  void* work;
+} mipme_dipole_step_args_t;
+int mipme_dipole_step(const mipme_dipole_step_args_t* args);
+int64_t mipme_dipole_step_work(int64_t n_atoms, int64_t n_k, int cell_gradient);
+
 /* ---- device neighbour list (the reference uses third-party vesin on the host,
  * tests/helpers.py:240-275, and hands a fresh list to every call, examples/02-neighbor-lists-usage.py:97-164) -------------
  * One cell-list traversal, two products:

@@ -1,0 +1,528 @@
+// Energy, forces and dE/dmu (+ dE/dcell) of point dipoles in ONE step (mipme_dipole_step, include/mipme.h): the MD form of
+// CalculatorDipole, every launch on one stream so that the whole step is one captured graph.
+//
+// E = sum_i mu_i . V_i is quadratic in the dipoles, so with the upstream gradient g = mu the structure factors of g are those of
+// mu (T = S) and everything the eager forward + backward computes in five passes over the (k, atom) phases comes from two:
+//
+//   records    (x, y, z, -) / (mu_x, mu_y, mu_z, -) per atom, float64 block partials of sum_j mu_j        dipole_step_records_kernel
+//   structure  S_c(k) = sum_j (mu_j.k) cos(k r_j), S_s likewise, over the COMPACTED k list                dipole_structure_kernel (dipole.hip)
+//   atoms      per (atom, k) one phase: field_i += G k (c S_c + s S_s), bracket_i += G (mu_i.k)(c S_s - s S_c) k
+//                                                                                                          dipole_step_atom_kernel
+//   rows       per atom a over both roles of its row: c sum_e T(vec_e) mu_o and c sum_e grad_vec (mu_a.T(vec_e).mu_o),
+//              vec_e = r_o - r_a + S'_e cell (role-adjusted shift); with CELL sum_p S_p (x) dE/dvec_p over role i
+//                                                                                                          dipole_step_rows_kernel
+//   cell k     per k: d/dk of 1/2 G |S|^2, contracted with k to 3 x 3, and 1/2 G |S|^2 itself              dipole_step_cellk_kernel
+//   finish     16 lanes per atom over the slices: dE/dmu_i = field_i / V - self mu_i + bg/V sum_j mu_j + rows;
+//              F_i = -bracket_i / V + rows; float64 block partials of 1/2 mu_i . dE/dmu_i                  dipole_step_finish_kernel
+//   final      one block: E, and dE/dcell = rows - A^-T W / V - (E_k + E_bg) A^-T  with W = sum_k (dE_raw/dk) (x) k
+//              (k = 2 pi f A^-T, so sum_k dE/dk . dk/dA = -A^-T W; 1/V gives the second term)              dipole_step_final_kernel
+//
+// The compacted list holds one of every +-k pair (the two terms of every sum above are equal) with the multiplicity folded into
+// G and dG by the caller.  No atomics: every sum has a fixed order, results are the same bits run after run.
+#include <cmath>
+#include <cstring>
+
+#include "dipole_device.h"
+#include "host.h"
+#include "rows_body.h"
+
+namespace mipme {
+
+constexpr int kDsBlock = 256;
+constexpr int kDsWaves = kDsBlock / 64;
+constexpr int kDsRowsPerBlock = kDsBlock / 16;  // 16 lanes per atom row
+static_assert(kRowLanes == 16, "row_sum of rows_body.h adds up the 16 lanes of a row");
+constexpr int kDsKPerBlock = 8;                 // k-vectors per block of the cell kernel, 32 lanes each
+constexpr int kDsKLanes = kDsBlock / kDsKPerBlock;
+constexpr int kDsTile = 256;                    // atoms staged per LDS tile of the cell kernel
+constexpr int kDsCellK = 10;                    // per k block: W (9), 1/2 sum G |S|^2
+constexpr int64_t kDsTargetBlocks = 2048;       // 256 CUs x 8 workgroups
+constexpr int64_t kDsMinSlice = 1024;           // k-vectors per slice at least (4 per thread)
+
+static int64_t ds_slices(int64_t N, int64_t K) {
+  if (N <= 0 || K <= 0) return 0;
+  int64_t s = (kDsTargetBlocks + N - 1) / N;
+  s = std::min<int64_t>(s, std::max<int64_t>(1, K / kDsMinSlice));
+  return std::max<int64_t>(1, std::min<int64_t>(s, 65535));
+}
+
+// work (float64 slots): [mu partials 3 per atom block][energy partials 1 per finish block][row cell partials 9 per row block]
+//                       [k cell partials 10 per k block][row results 6 N (values of T)][slice partials 6 N S (values of T)]
+struct DsWork {
+  int64_t n_atom_blocks, n_fin_blocks, n_row_blocks, n_k_blocks, n_slices;
+  double *mu_part, *e_part, *row_cell, *k_cell;
+  void *row_out, *slice_part;
+  int64_t total;
+};
+static DsWork ds_work_layout(int64_t N, int64_t K, bool cell, void* base) {
+  DsWork w;
+  w.n_atom_blocks = (N + kDsBlock - 1) / kDsBlock;
+  w.n_fin_blocks = (N + kDsRowsPerBlock - 1) / kDsRowsPerBlock;
+  w.n_row_blocks = cell ? w.n_fin_blocks : 0;
+  w.n_k_blocks = cell ? (K + kDsKPerBlock - 1) / kDsKPerBlock : 0;
+  w.n_slices = ds_slices(N, K);
+  double* b = (double*)base;
+  w.mu_part = b;
+  w.e_part = w.mu_part + 3 * w.n_atom_blocks;
+  w.row_cell = w.e_part + w.n_fin_blocks;
+  w.k_cell = w.row_cell + 9 * w.n_row_blocks;
+  double* row_out = w.k_cell + kDsCellK * w.n_k_blocks;
+  double* slice_part = row_out + 6 * N;
+  w.row_out = row_out;
+  w.slice_part = slice_part;
+  w.total = 3 * w.n_atom_blocks + w.n_fin_blocks + 9 * w.n_row_blocks + kDsCellK * w.n_k_blocks + 6 * N + 6 * N * w.n_slices;
+  return w;
+}
+
+// sum over the workgroup, the waves in index order (every thread calls it)
+__device__ __forceinline__ double ds_block_sum(double v, double* red) {
+  v = wave_sum(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double s = 0.0;
+#pragma unroll
+  for (int w = 0; w < kDsWaves; ++w) s += red[w];
+  return s;
+}
+
+// sum_b p[b * stride + off], b < n: thread t adds b = t, t + 256, ... in that order, then the threads in a fixed order
+__device__ __forceinline__ double ds_strided_sum(const double* __restrict__ p, int64_t n, int stride, int off, double* red) {
+  double s = 0.0;
+  for (int64_t b = threadIdx.x; b < n; b += kDsBlock) s += p[b * stride + off];
+  return ds_block_sum(s, red);
+}
+
+// ---- 1. records ------------------------------------------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(kDsBlock) void dipole_step_records_kernel(int64_t N, const T* __restrict__ pos, const T* __restrict__ mu,
+                                                                      AtomRecord<T>* __restrict__ recp,
+                                                                      AtomRecord<T>* __restrict__ recm, double* __restrict__ mu_part) {
+  __shared__ double red[kDsWaves];
+  const int64_t a = int64_t(blockIdx.x) * kDsBlock + threadIdx.x;
+  double m[3] = {0.0, 0.0, 0.0};
+  if (a < N) {
+    const T mx = mu[3 * a], my = mu[3 * a + 1], mz = mu[3 * a + 2];
+    recp[a] = AtomRecord<T>{pos[3 * a], pos[3 * a + 1], pos[3 * a + 2], T(0)};
+    recm[a] = AtomRecord<T>{mx, my, mz, T(0)};
+    m[0] = double(mx), m[1] = double(my), m[2] = double(mz);
+  }
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const double s = ds_block_sum(m[c], red);
+    if (threadIdx.x == 0) mu_part[3 * int64_t(blockIdx.x) + c] = s;
+  }
+}
+
+// ---- 2. fused atom kernel: block (i, slice), atom i against the k-vectors [slice * chunk, (slice + 1) * chunk) ---------------
+// part[(slice N + i) 6 + c]: c < 3 the field sum_k G k (c S_c + s S_s), c >= 3 the bracket sum_k G (mu_i.k)(c S_s - s S_c) k
+template <typename T>
+__global__ __launch_bounds__(kDsBlock) void dipole_step_atom_kernel(int64_t K, int64_t chunk, const AtomRecord<T>* __restrict__ recp,
+                                                                   const AtomRecord<T>* __restrict__ recm,
+                                                                   const T* __restrict__ kvec, const T* __restrict__ G,
+                                                                   const T* __restrict__ Sc, const T* __restrict__ Ss,
+                                                                   T* __restrict__ part) {
+  __shared__ T red[kDsWaves][6];
+  const int64_t i = blockIdx.x, N = gridDim.x;
+  const int64_t k0 = int64_t(blockIdx.y) * chunk, k1 = min<int64_t>(K, k0 + chunk);
+  const AtomRecord<T> p = recp[i], m = recm[i];
+  T fx = T(0), fy = T(0), fz = T(0), bx = T(0), by = T(0), bz = T(0);
+  for (int64_t k = k0 + threadIdx.x; k < k1; k += kDsBlock) {
+    const T gk = G[k];
+    if (gk == T(0)) continue;  // exact: the term is G(k) times a finite sum
+    const T kx = kvec[3 * k], ky = kvec[3 * k + 1], kz = kvec[3 * k + 2];
+    const T sc = Sc[k], ss = Ss[k];
+    T s, c;
+    dipole_phase3(kx, ky, kz, p.x, p.y, p.z, s, c);
+    const T f = gk * (c * sc + s * ss);
+    const T b = gk * (m.x * kx + m.y * ky + m.z * kz) * (c * ss - s * sc);
+    fx += f * kx;
+    fy += f * ky;
+    fz += f * kz;
+    bx += b * kx;
+    by += b * ky;
+    bz += b * kz;
+  }
+  fx = wave_sum(fx), fy = wave_sum(fy), fz = wave_sum(fz);
+  bx = wave_sum(bx), by = wave_sum(by), bz = wave_sum(bz);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) {
+    red[wave][0] = fx, red[wave][1] = fy, red[wave][2] = fz;
+    red[wave][3] = bx, red[wave][4] = by, red[wave][5] = bz;
+  }
+  __syncthreads();
+  if (threadIdx.x < 6) {
+    T s = T(0);
+#pragma unroll
+    for (int w = 0; w < kDsWaves; ++w) s += red[w][threadIdx.x];
+    part[(int64_t(blockIdx.y) * N + i) * 6 + threadIdx.x] = s;
+  }
+}
+
+// ---- 3. dipole pair rows -------------------------------------------------------------------------------------------------
+// 16 lanes per atom row, 4 rows per wavefront; the 7^3 table of Cartesian shift vectors in LDS; per entry one word
+// (other | code << 22) and two 16-byte record gathers (position, dipole of the partner).
+//   row_out[6 a + c]     = scale sum_e (T(vec_e) mu_o)_c                      c < 3    (scale = prefactor, or prefactor / 2 for a
+//   row_out[6 a + 3 + c] = scale sum_e (grad_vec (mu_a.T(vec_e).mu_o))_c                full list; both roles)
+//   cell_part[9 b + 3 m + n] = scale sum over the role-i entries of the rows of block b of S_m (grad_vec ...)_n    (CELL, float64)
+template <typename T, bool EXCL, bool CELL>
+__global__ __launch_bounds__(kDsBlock) void dipole_step_rows_kernel(DipPot<T> P, int64_t N, const int* __restrict__ row_ptr,
+                                                                   const int* __restrict__ ent32,
+                                                                   const AtomRecord<T>* __restrict__ recp,
+                                                                   const AtomRecord<T>* __restrict__ recm, const T* __restrict__ cell,
+                                                                   T scale, T* __restrict__ row_out, double* __restrict__ cell_part) {
+  __shared__ AtomRecord<T> shift_tab[kShiftTableSize];
+  __shared__ double red[kDsWaves][9];
+  const int tid = threadIdx.x;
+  {
+    T A[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) A[k] = cell[k];
+    for (int k = tid; k < kShiftTableSize; k += kDsBlock) {
+      const T sx = T(k % kShiftTableBase - kShiftTableRange), sy = T((k / kShiftTableBase) % kShiftTableBase - kShiftTableRange),
+              sz = T(k / (kShiftTableBase * kShiftTableBase) - kShiftTableRange);
+      shift_tab[k] = AtomRecord<T>{sx * A[0] + sy * A[3] + sz * A[6], sx * A[1] + sy * A[4] + sz * A[7],
+                                   sx * A[2] + sy * A[5] + sz * A[8], T(0)};
+    }
+  }
+  __syncthreads();
+  const int sub = tid % 16;
+  int64_t a = int64_t(blockIdx.x) * kDsRowsPerBlock + tid / 16;
+  const bool valid = a < N;
+  if (!valid) a = N - 1;
+  const int* __restrict__ rp = row_ptr + 2 * a;
+  const int beg = rp[0], mid = rp[1], end = valid ? rp[2] : beg;
+  const AtomRecord<T> pa = recp[a], ma = recm[a];
+  const unsigned last_atom = unsigned(N - 1);
+  T fx = T(0), fy = T(0), fz = T(0), gx = T(0), gy = T(0), gz = T(0);
+  T w00 = T(0), w01 = T(0), w02 = T(0), w10 = T(0), w11 = T(0), w12 = T(0), w20 = T(0), w21 = T(0), w22 = T(0);
+  for (int base = beg; base < end; base += 16) {
+    const int e = base + sub;
+    const bool ok = e < end;
+    const unsigned word = unsigned(ent32[ok ? e : beg]);  // (beg < end here: a real entry, left out of the sums)
+    // (a valid stream never needs the two clamps; they keep a damaged one inside the buffers)
+    const unsigned o = min(word & unsigned(kCompactMaxAtoms - 1), last_atom);
+    const unsigned code = min(word >> kCompactAtomBits, unsigned(kShiftTableSize - 1));
+    const AtomRecord<T> po = recp[o], mo = recm[o];
+    const AtomRecord<T> sh = shift_tab[code];
+    const T vx = (po.x - pa.x) + sh.x, vy = (po.y - pa.y) + sh.y, vz = (po.z - pa.z) + sh.z;
+    const T r2 = vx * vx + vy * vy + vz * vz;
+    const T ri = T(1) / fsqrt(r2);
+    T B, C, dB, dC;
+    dipole_bc<T, true, EXCL>(P, r2, ri, B, C, dB, dC);
+    const T cr = C * (mo.x * vx + mo.y * vy + mo.z * vz);
+    T ex = T(0), ey = T(0), ez = T(0);
+    dipole_pair_grad<T>(vx, vy, vz, C, dB, dC, ma.x, ma.y, ma.z, mo.x, mo.y, mo.z, ex, ey, ez);
+    if (ok) {
+      fx += B * mo.x - cr * vx;
+      fy += B * mo.y - cr * vy;
+      fz += B * mo.z - cr * vz;
+      gx += ex;
+      gy += ey;
+      gz += ez;
+      if (CELL && e < mid) {  // role i: the listed pair, its own shift
+        const int ic = int(code);
+        const T sx = T(ic % kShiftTableBase - kShiftTableRange), sy = T((ic / kShiftTableBase) % kShiftTableBase - kShiftTableRange),
+                sz = T(ic / (kShiftTableBase * kShiftTableBase) - kShiftTableRange);
+        w00 += sx * ex, w01 += sx * ey, w02 += sx * ez;
+        w10 += sy * ex, w11 += sy * ey, w12 += sy * ez;
+        w20 += sz * ex, w21 += sz * ey, w22 += sz * ez;
+      }
+    }
+  }
+  fx = row_sum(fx), fy = row_sum(fy), fz = row_sum(fz);
+  gx = row_sum(gx), gy = row_sum(gy), gz = row_sum(gz);
+  if (sub == 0 && valid) {
+    T* o = row_out + 6 * a;
+    o[0] = scale * fx, o[1] = scale * fy, o[2] = scale * fz;
+    o[3] = scale * gx, o[4] = scale * gy, o[5] = scale * gz;
+  }
+  if (CELL) {
+    const int lane = tid & 63, wave = tid >> 6;
+    const double s0 = wave_sum(double(w00)), s1 = wave_sum(double(w01)), s2 = wave_sum(double(w02));
+    const double s3 = wave_sum(double(w10)), s4 = wave_sum(double(w11)), s5 = wave_sum(double(w12));
+    const double s6 = wave_sum(double(w20)), s7 = wave_sum(double(w21)), s8 = wave_sum(double(w22));
+    if (lane == 0) {
+      red[wave][0] = s0, red[wave][1] = s1, red[wave][2] = s2;
+      red[wave][3] = s3, red[wave][4] = s4, red[wave][5] = s5;
+      red[wave][6] = s6, red[wave][7] = s7, red[wave][8] = s8;
+    }
+    __syncthreads();
+    if (tid < 9) {
+      double s = 0.0;
+#pragma unroll
+      for (int w = 0; w < kDsWaves; ++w) s += red[w][tid];
+      cell_part[9 * int64_t(blockIdx.x) + tid] = double(scale) * s;
+    }
+  }
+}
+
+// ---- 4. per-k cell gradient: 32 lanes per k-vector, positions and dipoles streamed through LDS ------------------------------
+// With g = mu, T = S:  gk = dE_raw/dk = dG |S|^2 k + G sum_i [ mu_i (c S_c + s S_s) + r_i (mu_i.k)(c S_s - s S_c) ],  E_raw = 1/2 sum G |S|^2.
+//   k_part[10 b + 3 a + n] = sum over the k-vectors of block b of gk_a k_n;   k_part[10 b + 9] = sum 1/2 G |S|^2        (float64)
+template <typename T>
+__global__ __launch_bounds__(kDsBlock) void dipole_step_cellk_kernel(int64_t N, int64_t K, const T* __restrict__ pos,
+                                                                    const T* __restrict__ mu, const T* __restrict__ kvec,
+                                                                    const T* __restrict__ G, const T* __restrict__ dG,
+                                                                    const T* __restrict__ Sc, const T* __restrict__ Ss,
+                                                                    double* __restrict__ k_part) {
+  __shared__ T sp[kDsTile * 3];
+  __shared__ T sm[kDsTile * 3];
+  __shared__ double red[kDsKPerBlock][kDsCellK];
+  const int al = threadIdx.x % kDsKLanes, kl = threadIdx.x / kDsKLanes;
+  const int64_t k = int64_t(blockIdx.x) * kDsKPerBlock + kl;
+  const bool live = k < K && (G[k] != T(0) || dG[k] != T(0));
+  const int64_t kc = k < K ? k : 0;
+  const T kx = kvec[3 * kc], ky = kvec[3 * kc + 1], kz = kvec[3 * kc + 2];
+  const T lSc = Sc[kc], lSs = Ss[kc];
+  T ax = T(0), ay = T(0), az = T(0);
+  for (int64_t base = 0; base < N; base += kDsTile) {
+    const int n = int(min<int64_t>(kDsTile, N - base));
+    __syncthreads();
+    for (int t = threadIdx.x; t < 3 * n; t += kDsBlock) {
+      sp[t] = pos[3 * base + t];
+      sm[t] = mu[3 * base + t];
+    }
+    __syncthreads();
+    if (live)
+      for (int i = al; i < n; i += kDsKLanes) {
+        const T x = sp[3 * i], y = sp[3 * i + 1], z = sp[3 * i + 2];
+        const T mx = sm[3 * i], my = sm[3 * i + 1], mz = sm[3 * i + 2];
+        T s, c;
+        dipole_phase3(kx, ky, kz, x, y, z, s, c);
+        const T a1 = c * lSc + s * lSs;
+        const T b = (mx * kx + my * ky + mz * kz) * (c * lSs - s * lSc);
+        ax += mx * a1 + b * x;
+        ay += my * a1 + b * y;
+        az += mz * a1 + b * z;
+      }
+  }
+#pragma unroll
+  for (int off = kDsKLanes / 2; off > 0; off >>= 1) {
+    ax += __shfl_xor(ax, off, kDsKLanes);
+    ay += __shfl_xor(ay, off, kDsKLanes);
+    az += __shfl_xor(az, off, kDsKLanes);
+  }
+  if (al == 0) {
+    double g[3] = {0.0, 0.0, 0.0}, e = 0.0;
+    const double kd[3] = {double(kx), double(ky), double(kz)};
+    if (live) {
+      const double gk = double(G[kc]), s2 = double(lSc) * double(lSc) + double(lSs) * double(lSs), d = double(dG[kc]) * s2;
+      g[0] = gk * double(ax) + d * kd[0];
+      g[1] = gk * double(ay) + d * kd[1];
+      g[2] = gk * double(az) + d * kd[2];
+      e = 0.5 * gk * s2;
+    }
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+      for (int n = 0; n < 3; ++n) red[kl][3 * a + n] = g[a] * kd[n];
+    red[kl][9] = e;
+  }
+  __syncthreads();
+  if (threadIdx.x < kDsCellK) {
+    double s = 0.0;
+#pragma unroll
+    for (int q = 0; q < kDsKPerBlock; ++q) s += red[q][threadIdx.x];
+    k_part[kDsCellK * int64_t(blockIdx.x) + threadIdx.x] = s;
+  }
+}
+
+// ---- 5. finish -----------------------------------------------------------------------------------------------------------
+// 16 lanes per atom: lane l adds the slices l, l + 16, ... in that order, then the 16 lanes are added by the shuffle tree of the
+// rows (with few atoms there are hundreds of slices: one thread per atom would walk them one dependent load after the other)
+template <typename T>
+__global__ __launch_bounds__(kDsBlock) void dipole_step_finish_kernel(int64_t N, int n_slices, T inv_vol, T self_term, T bg_over_v,
+                                                                     const AtomRecord<T>* __restrict__ recm,
+                                                                     const T* __restrict__ part, const T* __restrict__ row_out,
+                                                                     const double* __restrict__ mu_part, int64_t n_mu_blocks,
+                                                                     T* __restrict__ forces, T* __restrict__ grad_mu,
+                                                                     double* __restrict__ e_part) {
+  __shared__ double red[kDsWaves];
+  double M[3] = {0.0, 0.0, 0.0};
+  if (bg_over_v != T(0)) {  // (uniform) sum_j mu_j, the same fixed order in every block
+#pragma unroll
+    for (int c = 0; c < 3; ++c) M[c] = ds_strided_sum(mu_part, n_mu_blocks, 3, c, red);
+  }
+  const int sub = threadIdx.x % 16;
+  const int64_t a = int64_t(blockIdx.x) * kDsRowsPerBlock + threadIdx.x / 16;
+  const bool valid = a < N;
+  T f0 = T(0), f1 = T(0), f2 = T(0), b0 = T(0), b1 = T(0), b2 = T(0);
+  if (valid)
+    for (int s = sub; s < n_slices; s += 16) {
+      const T* __restrict__ p = part + (int64_t(s) * N + a) * 6;
+      f0 += p[0], f1 += p[1], f2 += p[2];
+      b0 += p[3], b1 += p[4], b2 += p[5];
+    }
+  f0 = row_sum(f0), f1 = row_sum(f1), f2 = row_sum(f2);
+  b0 = row_sum(b0), b1 = row_sum(b1), b2 = row_sum(b2);
+  double e = 0.0;
+  if (valid && sub == 0) {
+    const T f[3] = {f0, f1, f2}, b[3] = {b0, b1, b2};
+    const AtomRecord<T> m = recm[a];
+    const T mv[3] = {m.x, m.y, m.z};
+    const T* __restrict__ r = row_out + 6 * a;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const T d = (inv_vol * f[c] - self_term * mv[c] + bg_over_v * T(M[c])) + r[c];
+      grad_mu[3 * a + c] = d;
+      forces[3 * a + c] = r[3 + c] - inv_vol * b[c];
+      e += 0.5 * double(mv[c]) * double(d);
+    }
+  }
+  e = ds_block_sum(e, red);
+  if (threadIdx.x == 0) e_part[blockIdx.x] = e;
+}
+
+// ---- 6. final: one block ----------------------------------------------------------------------------------------------------
+template <typename T, bool CELL>
+__global__ __launch_bounds__(kDsBlock) void dipole_step_final_kernel(int64_t n_e_blocks, const double* __restrict__ e_part,
+                                                                    T* __restrict__ energy, int64_t n_row_blocks,
+                                                                    const double* __restrict__ row_cell, int64_t n_k_blocks,
+                                                                    const double* __restrict__ k_cell, int64_t n_mu_blocks,
+                                                                    const double* __restrict__ mu_part, double inv_vol, double bg,
+                                                                    const T* __restrict__ inv_cell, T* __restrict__ grad_cell) {
+  __shared__ double red[kDsWaves];
+  __shared__ double tot[9 + kDsCellK + 3];
+  const double E = ds_strided_sum(e_part, n_e_blocks, 1, 0, red);
+  if (threadIdx.x == 0) energy[0] = T(E);
+  if (CELL) {
+    for (int j = 0; j < 9; ++j) {
+      const double s = ds_strided_sum(row_cell, n_row_blocks, 9, j, red);
+      if (threadIdx.x == 0) tot[j] = s;
+    }
+    for (int j = 0; j < kDsCellK; ++j) {
+      const double s = ds_strided_sum(k_cell, n_k_blocks, kDsCellK, j, red);
+      if (threadIdx.x == 0) tot[9 + j] = s;
+    }
+    for (int j = 0; j < 3; ++j) {
+      const double s = ds_strided_sum(mu_part, n_mu_blocks, 3, j, red);
+      if (threadIdx.x == 0) tot[9 + kDsCellK + j] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x < 9) {
+      const int m = threadIdx.x / 3, n = threadIdx.x % 3;
+      const double* Wr = tot;
+      const double* Wk = tot + 9;
+      const double Ek = tot[9 + 9];
+      const double* M = tot + 9 + kDsCellK;
+      const double e_v = inv_vol * (Ek + 0.5 * bg * (M[0] * M[0] + M[1] * M[1] + M[2] * M[2]));  // what scales with 1/V
+      double chain = 0.0;
+      for (int a = 0; a < 3; ++a) chain += double(inv_cell[3 * a + m]) * Wk[3 * a + n];
+      grad_cell[3 * m + n] = T(Wr[3 * m + n] - inv_vol * chain - e_v * double(inv_cell[3 * n + m]));
+    }
+  }
+}
+
+// ---- host --------------------------------------------------------------------------------------------------------------------
+template <typename T, bool EXCL>
+static void dipole_step_rows_launch(hipStream_t st, const mipme_dipole_step_args_t& a, const DipPot<T>& dp, const DsWork& w,
+                                    const AtomRecord<T>* recp, const AtomRecord<T>* recm) {
+  const unsigned blocks = unsigned((a.n_atoms + kDsRowsPerBlock - 1) / kDsRowsPerBlock);
+  const T scale = T(a.full_list ? 0.5 : 1.0) * dp.pref;
+  if (a.cell_gradient)
+    dipole_step_rows_kernel<T, EXCL, true><<<blocks, kDsBlock, 0, st>>>(dp, a.n_atoms, (const int*)a.row_ptr, (const int*)a.entries,
+                                                                       recp, recm, (const T*)a.cell, scale, (T*)w.row_out, w.row_cell);
+  else
+    dipole_step_rows_kernel<T, EXCL, false><<<blocks, kDsBlock, 0, st>>>(dp, a.n_atoms, (const int*)a.row_ptr, (const int*)a.entries,
+                                                                        recp, recm, (const T*)a.cell, scale, (T*)w.row_out, nullptr);
+}
+
+template <typename T>
+static int dipole_step_t(const mipme_dipole_step_args_t& a, const DipPot<T>& dp) {
+  hipStream_t st = (hipStream_t)a.stream;
+  const int64_t N = a.n_atoms, K = a.n_k;
+  const bool cell = a.cell_gradient != 0;
+  const DsWork w = ds_work_layout(N, K, cell, a.work);
+  AtomRecord<T>* recp = (AtomRecord<T>*)a.records;
+  AtomRecord<T>* recm = recp + N;
+  int rc;
+  dipole_step_records_kernel<T><<<unsigned(w.n_atom_blocks), kDsBlock, 0, st>>>(N, (const T*)a.positions, (const T*)a.dipoles, recp,
+                                                                               recm, w.mu_part);
+  MIPME_LAUNCH_CHECK();
+  if (K > 0) {
+    if ((rc = mipme_dipole_structure(a.stream, a.dtype, N, K, a.positions, a.dipoles, a.kvectors, a.G, cell ? a.dG : nullptr, a.s_cos,
+                                     a.s_sin)))
+      return rc;
+    const int64_t chunk = (K + w.n_slices - 1) / w.n_slices;
+    dipole_step_atom_kernel<T><<<dim3(unsigned(N), unsigned(w.n_slices)), kDsBlock, 0, st>>>(
+        K, chunk, recp, recm, (const T*)a.kvectors, (const T*)a.G, (const T*)a.s_cos, (const T*)a.s_sin, (T*)w.slice_part);
+    MIPME_LAUNCH_CHECK();
+  }
+  if (dp.mode == 2)
+    dipole_step_rows_launch<T, true>(st, a, dp, w, recp, recm);
+  else
+    dipole_step_rows_launch<T, false>(st, a, dp, w, recp, recm);
+  MIPME_LAUNCH_CHECK();
+  if (cell && K > 0) {
+    dipole_step_cellk_kernel<T><<<unsigned(w.n_k_blocks), kDsBlock, 0, st>>>(N, K, (const T*)a.positions, (const T*)a.dipoles,
+                                                                            (const T*)a.kvectors, (const T*)a.G, (const T*)a.dG,
+                                                                            (const T*)a.s_cos, (const T*)a.s_sin, w.k_cell);
+    MIPME_LAUNCH_CHECK();
+  }
+  dipole_step_finish_kernel<T><<<unsigned(w.n_fin_blocks), kDsBlock, 0, st>>>(
+      N, int(w.n_slices), T(a.inv_volume), T(a.self_term), T(a.background * a.inv_volume), recm, (const T*)w.slice_part,
+      (const T*)w.row_out, w.mu_part, w.n_atom_blocks, (T*)a.forces, (T*)a.grad_dipoles, w.e_part);
+  MIPME_LAUNCH_CHECK();
+  if (cell)
+    dipole_step_final_kernel<T, true><<<1, kDsBlock, 0, st>>>(w.n_fin_blocks, w.e_part, (T*)a.energy, w.n_row_blocks, w.row_cell,
+                                                             w.n_k_blocks, w.k_cell, w.n_atom_blocks, w.mu_part, a.inv_volume,
+                                                             a.background, (const T*)a.inv_cell, (T*)a.grad_cell);
+  else
+    dipole_step_final_kernel<T, false><<<1, kDsBlock, 0, st>>>(w.n_fin_blocks, w.e_part, (T*)a.energy, 0, nullptr, 0, nullptr, 0,
+                                                              nullptr, a.inv_volume, a.background, nullptr, nullptr);
+  MIPME_LAUNCH_CHECK();
+  return MIPME_OK;
+}
+
+template <typename T>
+static int dipole_step_run(const mipme_dipole_step_args_t& a) {
+  DipPot<T> dp;
+  int rc = make_dippot<T>(a.pot, dp);
+  if (rc) return rc;
+  return dipole_step_t<T>(a, dp);
+}
+
+}  // namespace mipme
+
+using namespace mipme;
+
+extern "C" {
+
+int64_t mipme_dipole_step_work(int64_t n_atoms, int64_t n_k, int cell_gradient) {
+  if (n_atoms < 1 || n_atoms > kCompactMaxAtoms || n_k < 0 || n_k > int64_t(kDsKPerBlock) * 0x7fffffff) return 0;
+  return ds_work_layout(n_atoms, n_k, cell_gradient != 0, nullptr).total;
+}
+
+int mipme_dipole_step(const mipme_dipole_step_args_t* in) {
+  const char* who = "mipme_dipole_step";
+  MIPME_REQUIRE(in != nullptr, "%s: NULL argument struct", who);
+  MIPME_REQUIRE(in->version == MIPME_DIPOLE_STEP_VERSION, "%s: argument struct version %u, library expects %u", who, in->version,
+                unsigned(MIPME_DIPOLE_STEP_VERSION));
+  MIPME_REQUIRE(in->size >= 16 && in->size <= 4096, "%s: implausible argument struct size %u", who, in->size);
+  mipme_dipole_step_args_t a;
+  std::memset(&a, 0, sizeof(a));
+  std::memcpy(&a, in, in->size < sizeof(a) ? in->size : sizeof(a));
+  // everything the arguments alone decide, before anything touches a device
+  MIPME_REQUIRE(a.dtype == MIPME_F32 || a.dtype == MIPME_F64, "%s: invalid dtype %d", who, int(a.dtype));
+  MIPME_REQUIRE(a.pot != nullptr, "%s: dipole descriptor is NULL", who);
+  MIPME_REQUIRE(!(a.pot->exclusion_radius > 0) || a.pot->exclusion_degree >= 1, "%s: exclusion_degree must be >= 1, got %d", who,
+                int(a.pot->exclusion_degree));
+  MIPME_REQUIRE(a.n_k >= 0 && a.n_k <= int64_t(kDsKPerBlock) * 0x7fffffff, "%s: n_k must be >= 0, got %lld", who, (long long)a.n_k);
+  MIPME_REQUIRE(a.n_k == 0 || a.pot->smearing > 0,
+                "%s: n_k is %lld but the potential has no smearing (`smearing` is %g): a direct potential has no reciprocal part",
+                who, (long long)a.n_k, a.pot->smearing);
+  MIPME_REQUIRE((a.shift_format & 0xff) == 2 && !(a.shift_format & MIPME_ROWS_PADDED),
+                "%s: the rows are read as 4-byte entries, other | code << 22 (shift_format 2), got shift_format %d", who,
+                int(a.shift_format));
+  MIPME_REQUIRE(a.n_atoms > 0 && a.n_atoms <= kCompactMaxAtoms, "%s: n_atoms must be in 1..2^22, got %lld", who, (long long)a.n_atoms);
+  MIPME_REQUIRE(std::isfinite(a.inv_volume) && a.inv_volume > 0, "%s: inv_volume must be positive, got %g", who, a.inv_volume);
+  MIPME_REQUIRE(!a.cell_gradient || (a.grad_cell && a.inv_cell), "%s: cell_gradient needs grad_cell and inv_cell", who);
+  MIPME_REQUIRE(!a.cell_gradient || a.n_k == 0 || a.dG, "%s: cell_gradient needs dG (dG/dk^2 of the compacted k-vectors)", who);
+  MIPME_REQUIRE(a.positions && a.dipoles && a.cell && a.row_ptr && a.entries && a.records && a.energy && a.forces && a.grad_dipoles &&
+                    a.work && (a.n_k == 0 || (a.kvectors && a.G && a.s_cos && a.s_sin)),
+                "%s: NULL required buffer", who);
+  DT_SWITCH(a.dtype, dipole_step_run<float>(a), dipole_step_run<double>(a));
+}
+
+}  // extern "C"

@@ -10,6 +10,7 @@ stay eager and reference-compatible.
 from __future__ import annotations
 
 import ctypes as C
+import math
 
 import numpy as np
 import torch
@@ -985,4 +986,200 @@ class GraphedCombinedStep:
             out += (self.weight_grad,)
         if self.charge_gradient:
             out += (self.charge_grad,)
+        return out
+
+
+def _compact_kvectors(freq: np.ndarray, ns):
+    """Rows of the integer frequencies ``freq`` (K, 3) of a grid with ``ns`` points per axis that the dipole step sums, and their
+    multiplicities: k = 0 is dropped, of every pair +-k whose two members are in the grid the one whose first non-zero component is
+    positive is kept with weight 2, and a vector whose mirror is not in the grid (a component on the -n/2 plane of an even n) is
+    kept with weight 1."""
+    f = np.rint(np.asarray(freq, dtype=np.float64)).astype(np.int64)
+    ns = np.asarray(ns, dtype=np.int64)
+    unpaired = ((ns % 2 == 0)[None, :] & (f == -(ns // 2)[None, :])).any(axis=1)
+    sign = np.sign(f)
+    first = np.where(sign[:, 0] != 0, sign[:, 0], np.where(sign[:, 1] != 0, sign[:, 1], sign[:, 2]))
+    keep = unpaired | (first > 0)
+    rows = np.nonzero(keep)[0]
+    return rows, np.where(unpaired[rows], 1.0, 2.0)
+
+
+class GraphedDipoleStep:
+    """``E, F, dE_dmu = step(positions, dipoles)`` for a :class:`~torchpme_amd.CalculatorDipole`, replayed from one HIP graph: the
+    MD form of the eager call for a fixed neighbour list and cell (dipolar fluids, polarisable models).
+
+    With ``V`` what the eager calculator returns for the same arguments and ``neighbor_vectors = r_j - r_i + S cell`` -- the step
+    forms the pair vectors itself from the list and its cell shifts -- ``E = sum_i mu_i . V_i`` (0-dim), ``F = -dE/dpositions``
+    (N, 3; the total derivative, through the pair vectors and the reciprocal part), ``dE_dmu = dE/ddipoles`` (N, 3; the total
+    derivative: ``2 V`` for a half list, ``V`` plus the transposed half for a full one) and, with ``cell_gradient``, ``dE_dcell``
+    (3, 3) at fixed Cartesian positions (the convention of ``GraphedEnergyForces(cell_gradient=True)``).  The field at dipole i is
+    ``-dE_dmu[i]``, so the torque on it is ``mu_i x (-dE_dmu_i)``: ``torch.linalg.cross(dipoles, -dE_dmu)``.
+
+    All outputs are buffers of the object, overwritten by every call.  A call copies the given positions and dipoles into the
+    object's buffers and replays the graph: no host reads, and -- as on the eager dipole path -- no check for non-finite input.
+    Every sum of the step has a fixed order (no floating-point atomics), so equal inputs give equal bits.  The cell is fixed for
+    the life of the object; a new list needs :meth:`recapture`.
+
+    E is quadratic in the dipoles, so the structure factors are formed once, one kernel evaluates the field and the position
+    gradient from one phase per (atom, k), and only one of every pair +-k of the reciprocal grid is summed (:attr:`n_k` vectors);
+    the pair part is one walk over the transposed list without atomics (``mipme_dipole_step``, csrc/dipole_step.hip).
+
+    :param calculator: a :class:`CalculatorDipole` with any :class:`PotentialDipole` the eager call accepts (direct or range
+        separated, with or without exclusion radius, ``epsilon``, ``prefactor``; half or full list from
+        ``calculator.full_neighbor_list``)
+    :param dipoles: (N, 3)
+    :param cell: (3, 3), rows are the lattice vectors
+    :param positions: (N, 3)
+    :param neighbor_indices, neighbor_shifts: an explicit list (P, 2) with integer cell shifts (P, 3) in [-3, 3]; at most 2^22 atoms
+    :param cell_gradient: also return ``dE/dcell``
+    :param warmup: eager runs before the capture
+    """
+
+    def __init__(self, calculator, dipoles, cell, positions, neighbor_indices, neighbor_shifts, cell_gradient: bool = False,
+                 warmup: int = 3):
+        from .calculators import _integer_frequencies, _reciprocal_and_det
+        from .dipoles import CalculatorDipole
+
+        if not isinstance(calculator, CalculatorDipole):
+            raise TypeError(f"GraphedDipoleStep serves a CalculatorDipole, got a {type(calculator).__name__}: use GraphedEnergyForces "
+                            "or GraphedCombinedStep for charges")
+        if dipoles.dim() != 2 or dipoles.shape[1] != 3:
+            raise ValueError(f"`dipoles` must be a tensor with shape [n_atoms, 3], got tensor with shape {list(dipoles.shape)}")
+        if positions.dim() != 2 or positions.shape[1] != 3 or positions.shape[0] != dipoles.shape[0]:
+            raise ValueError(f"`positions` must be a tensor with shape [n_atoms, 3] with n_atoms = {dipoles.shape[0]} (the dipoles), "
+                             f"got tensor with shape {list(positions.shape)}")
+        if tuple(cell.shape) != (3, 3):
+            raise ValueError(f"`cell` must be a tensor with shape [3, 3], got tensor with shape {list(cell.shape)}")
+        if not (positions.dtype == dipoles.dtype == cell.dtype) or positions.dtype not in (torch.float32, torch.float64):
+            raise ValueError(f"`positions`, `dipoles` and `cell` must share one dtype, float32 or float64, got {positions.dtype}, "
+                             f"{dipoles.dtype} and {cell.dtype}")
+        if positions.shape[0] < 1 or positions.shape[0] > (1 << 22):
+            raise ValueError(f"GraphedDipoleStep handles 1 to 2^22 atoms (the 4-byte pair entries of the row kernel), got "
+                             f"{positions.shape[0]}")
+        self._check_list(neighbor_indices, neighbor_shifts)
+        for t, name in ((positions, "positions"), (dipoles, "dipoles"), (cell, "cell"), (neighbor_indices, "neighbor_indices"),
+                        (neighbor_shifts, "neighbor_shifts")):
+            _lib.require_device(t, name)
+        self.calc = calculator
+        self.cell_gradient = bool(cell_gradient)
+        self.full = bool(calculator.full_neighbor_list)
+        lib = self._lib = _lib.load()
+        device, dtype = positions.device, positions.dtype
+        self.device, self.dtype, self._dt = device, dtype, _lib.dtype_code(dtype)
+        N = self.n_atoms = positions.shape[0]
+        pot = calculator.potential
+        sm, _, eps, pref = pot._host_params()
+        self._desc = pot._descriptor()
+        new = lambda *shape, dt=dtype: torch.empty(shape, dtype=dt, device=device)  # noqa: E731
+        self.cell = cell.detach().clone().contiguous()
+        cell_host = self.cell.to("cpu", torch.float64).numpy()
+        det = float(np.linalg.det(cell_host))
+        if det == 0.0 or not np.isfinite(det):
+            raise ValueError(f"provided `cell` has a determinant of {det}, i.e. it is not a valid unit cell")
+        self._inv_volume = 1.0 / abs(det)
+        self._inv_cell = torch.tensor(np.linalg.inv(cell_host), dtype=dtype, device=device).contiguous()
+        self._self_term, self._background = 0.0, 0.0
+        self._kvec = self._G = self._dG = self._Sc = self._Ss = None
+        self.n_k = 0
+        if sm is not None:
+            # the k-vectors exactly as CalculatorDipole._compute_kspace forms them, then one of every +-k pair
+            recip, _ = _reciprocal_and_det(self.cell)
+            freq, _ = _integer_frequencies(self.cell, calculator.lr_wavelength, None)
+            ns = np.ceil(np.linalg.norm(cell_host, axis=1) / calculator.lr_wavelength).astype(np.int64)
+            rows, weight = _compact_kvectors(freq.cpu().numpy(), ns)
+            kvec = ((2 * math.pi) * freq @ recip)[torch.as_tensor(rows, device=device)].contiguous()
+            K = self.n_k = int(kvec.shape[0])
+            alpha = 0.5 / sm**2
+            self._self_term = pref * 4 * math.pi / 3 * (alpha / math.pi) ** 1.5
+            self._background = pref * 4 * math.pi / (2 * eps + 1) if eps != 0.0 else 0.0
+            if K > 0:
+                G, dG = new(K), new(K)
+                with _lib.on_device(device):
+                    _lib.check(lib.mipme_ewald_filter(_lib.current_stream(device), self._dt, C.byref(pot._coulomb_descriptor()), K,
+                                                      kvec.data_ptr(), G.data_ptr(), dG.data_ptr()))
+                w = torch.as_tensor(weight, dtype=dtype, device=device)
+                self._kvec, self._G = kvec, G * w  # the multiplicity folded into the filter
+                self._dG = dG * w if self.cell_gradient else None
+                self._Sc, self._Ss = new(K), new(K)
+        self.pos = positions.detach().clone().contiguous()
+        self.mu = dipoles.detach().clone().contiguous()
+        self._rec = new(2 * N, 4)
+        self.energy, self.forces, self.dipole_grad = new(), new(N, 3), new(N, 3)
+        self.cell_grad = new(3, 3) if self.cell_gradient else None
+        self._work = new(max(1, int(lib.mipme_dipole_step_work(N, self.n_k, int(self.cell_gradient)))), dt=torch.float64)
+        self._warmup = max(1, int(warmup))
+        self._capture(neighbor_indices, neighbor_shifts)
+
+    @staticmethod
+    def _check_list(neighbor_indices, neighbor_shifts):
+        if neighbor_indices.dim() != 2 or neighbor_indices.shape[1] != 2:
+            raise ValueError(f"`neighbor_indices` must be a tensor with shape [n_pairs, 2], got tensor with shape "
+                             f"{list(neighbor_indices.shape)}")
+        if neighbor_shifts.dim() != 2 or tuple(neighbor_shifts.shape) != (neighbor_indices.shape[0], 3):
+            raise ValueError(f"`neighbor_shifts` must be a tensor with shape [n_pairs, 3] with n_pairs = {neighbor_indices.shape[0]}, "
+                             f"got tensor with shape {list(neighbor_shifts.shape)}")
+        if neighbor_shifts.numel() > 0:
+            s = neighbor_shifts.detach()
+            if bool((s != s.round()).any()) or float(s.abs().max()) > 3:
+                raise ValueError("GraphedDipoleStep: the cell shifts must be integers in [-3, 3] (the 4-byte pair entries of the row "
+                                 "kernel); wrap the positions into the cell or use a shorter cutoff")
+
+    def _capture(self, neighbor_indices, neighbor_shifts):
+        device, N = self.device, self.n_atoms
+        self.pairs = neighbor_indices
+        sh = neighbor_shifts.to(self.dtype).contiguous()
+        topo = ops.get_topology(neighbor_indices, N)
+        ent32 = topo.compact_entries(sh, neighbor_shifts)
+        if ent32 is None:
+            raise ValueError("GraphedDipoleStep: the cell shifts must be integers in [-3, 3] (the 4-byte pair entries of the row "
+                             "kernel) and the system at most 2^22 atoms")
+        self._row_ptr, self._ent32 = topo.row_ptr, ent32
+        self._keepalive = [topo, topo.row_ptr, ent32, sh]  # the captured graph holds raw pointers into these
+        side = torch.cuda.Stream(device)
+        side.wait_stream(torch.cuda.current_stream(device))
+        with torch.cuda.stream(side):
+            for _ in range(self._warmup):
+                self._launch()
+        torch.cuda.current_stream(device).wait_stream(side)
+        torch.cuda.synchronize(device)
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph):
+            self._launch()
+
+    def _launch(self):
+        with _lib.on_device(self.device):
+            a = _lib.DipoleStepArgs(
+                stream=_lib.current_stream(self.device), dtype=self._dt, full_list=int(self.full), pot=C.pointer(self._desc),
+                n_atoms=self.n_atoms, n_k=self.n_k, inv_volume=self._inv_volume, self_term=self._self_term,
+                background=self._background, positions=self.pos.data_ptr(), dipoles=self.mu.data_ptr(), cell=self.cell.data_ptr(),
+                inv_cell=self._inv_cell.data_ptr(), kvectors=_lib.ptr(self._kvec), G=_lib.ptr(self._G), dG=_lib.ptr(self._dG),
+                row_ptr=self._row_ptr.data_ptr(), entries=self._ent32.data_ptr(), shift_format=2,
+                cell_gradient=int(self.cell_gradient), records=self._rec.data_ptr(), s_cos=_lib.ptr(self._Sc), s_sin=_lib.ptr(self._Ss),
+                energy=self.energy.data_ptr(), forces=self.forces.data_ptr(), grad_dipoles=self.dipole_grad.data_ptr(),
+                grad_cell=_lib.ptr(self.cell_grad), work=self._work.data_ptr())
+            _lib.check(self._lib.mipme_dipole_step(C.byref(a)))
+
+    def recapture(self, neighbor_indices, neighbor_shifts, positions: torch.Tensor | None = None,
+                  dipoles: torch.Tensor | None = None) -> None:
+        """New neighbour list: rebuild the pair topology and capture the step again; every other buffer is kept."""
+        self._check_list(neighbor_indices, neighbor_shifts)
+        with torch.no_grad():
+            if positions is not None:
+                self.pos.copy_(positions)
+            if dipoles is not None:
+                self.mu.copy_(dipoles)
+        self._capture(neighbor_indices, neighbor_shifts)
+
+    def __call__(self, positions: torch.Tensor | None = None, dipoles: torch.Tensor | None = None):
+        """``E, F, dE_dmu`` (+ ``dE_dcell`` with ``cell_gradient``) of the current -- or the given -- positions and dipoles: up to
+        two small copies and one graph replay."""
+        with torch.no_grad():
+            if positions is not None:
+                self.pos.copy_(positions)
+            if dipoles is not None:
+                self.mu.copy_(dipoles)
+        self.graph.replay()
+        out = (self.energy, self.forces, self.dipole_grad)
+        if self.cell_gradient:
+            out += (self.cell_grad,)
         return out
