@@ -2,7 +2,7 @@
 -- against the reference's autograd (``tests/golden/combined_step.npz``, written by ``tests/golden/make_combined_step_golden.py``),
 against the single-member steps of ``GraphedEnergyForces`` (linearity), against the eager calculator on a seeded random system
 that exercises the row kernel's edges, and the behaviour of the object: weights and positions followed without a new capture,
-the refusal of a shift beyond the entry format, the deferred NaN flag.
+the refusal of a shift beyond the entry format (which leaves a step that is recaptured as it was), the deferred NaN flag.
 
 Bounds.  float64: ``1e-10 * max|want|`` (the rule of ``tests/test_gpu_combined.py::_check_against_reference``).  float32: the
 larger of (a) that rule's float32 bound -- 5 x the spread of the reference's own float32 run + 4 eps32 x scale; on the random
@@ -319,3 +319,19 @@ def test_shift_out_of_range_and_nan_flag():
     with pytest.raises(ValueError, match=r"NaNs detected in the k-space filter result.*shape: \[1, 32, 32, 32\]"):
         step(pos)
     assert float(step(pos)[0]) == E  # the flag is cleared, the step serves on
+
+
+def test_a_refused_recapture_leaves_the_step_as_it_was():
+    """``recapture`` with a shift of 4 raises before anything of the object changes: ``pairs`` is still the list the replayed graph
+    was captured for, and a further call returns the bits of the first (float64, the 37-atom system, one term)."""
+    s = _random_system("half")
+    q, cell, pos, idx, S = _tensors(s, F64)
+    step = tpa.GraphedCombinedStep(_calculator(_combination(*ONE), "pme", False, s["spacing"]), q, cell, pos, idx, S)
+    first = [x.clone() for x in step()]
+    bad = S.clone()
+    bad[3, 1] = 4.0
+    with pytest.raises(ValueError, match=r"GraphedCombinedStep: the cell shifts must be integers in \[-3, 3\]"):
+        step.recapture(idx.clone(), bad)
+    assert step.pairs is idx
+    for a, b in zip(first, step()):
+        assert torch.equal(a, b)

@@ -889,20 +889,6 @@ static int slab_backward_t(hipStream_t st, int axis, const mipme_mesh_t* m, doub
 
 }  // namespace mipme
 
-// Copy a caller's versioned argument struct into the library's own layout: only the first `size` bytes the caller
-// compiled are read, everything after them stays zero (fields are only ever appended).
-template <typename A>
-static int load_args(const A* in, A& out, const char* what) {
-  MIPME_REQUIRE(in != nullptr, "%s: NULL argument struct", what);
-  MIPME_REQUIRE(in->version == MIPME_ARGS_VERSION, "%s: argument struct version %u, library expects %u", what, in->version,
-                unsigned(MIPME_ARGS_VERSION));
-  MIPME_REQUIRE(in->size >= 16 && in->size <= 4096, "%s: implausible argument struct size %u", what, in->size);
-  memset(&out, 0, sizeof(A));
-  memcpy(&out, in, in->size < sizeof(A) ? in->size : sizeof(A));
-  return MIPME_OK;
-}
-
-
 using namespace mipme;
 
 // `slab` of a step's arguments (0 = off, else the non-periodic axis + 1): the term lives in the gather tail, for one channel and 1/r
@@ -1083,7 +1069,7 @@ int mipme_gather(void* stream, int dtype, const mipme_mesh_t* mesh, int64_t n_at
 int mipme_kspace_forward(const mipme_kspace_forward_args_t* args_in) {
   TraceRange _tr("mipme_kspace_forward");
   mipme_kspace_forward_args_t a;
-  int rc = load_args(args_in, a, "mipme_kspace_forward");
+  int rc = load_args(args_in, a, MIPME_ARGS_VERSION, "mipme_kspace_forward");
   if (rc) return rc;
   if ((rc = validate_mesh(a.mesh))) return rc;
   // (what the arguments alone decide comes before anything that needs a device)
@@ -1196,7 +1182,7 @@ int mipme_md_step(const mipme_md_args_t* args_in) {
 int mipme_kspace_backward(const mipme_kspace_backward_args_t* args_in) {
   TraceRange _tr("mipme_kspace_backward");
   mipme_kspace_backward_args_t a;
-  int rc = load_args(args_in, a, "mipme_kspace_backward");
+  int rc = load_args(args_in, a, MIPME_ARGS_VERSION, "mipme_kspace_backward");
   if (rc) return rc;
   if ((rc = validate_mesh(a.mesh))) return rc;
   if ((rc = check_plan(a.plan, a.dtype, a.mesh))) return rc;

@@ -27,6 +27,7 @@ constexpr int kCsBlock = 256;
 constexpr int kCsMaxTerms = MIPME_COMBINED_MAX_TERMS;
 constexpr int kCsRowsPerBlock = kCsBlock / 16;  // 16 lanes per atom row
 static_assert(kRowLanes == 16, "row_sum of rows_body.h adds up the 16 lanes of a row");
+static_assert(kCompactAtomBits == kStepRowsAtomBits, "check_step_rows of host.h admits what the 4-byte entries hold");
 constexpr int kCsRowPart = 4 + kCsMaxTerms;     // per row block: sum q V_sr, sum q^2, sum q phi, -, sum q u_t
 constexpr int kCsKBlocksMax = 256;              // blocks of the per-term mesh energies
 
@@ -158,12 +159,7 @@ __global__ __launch_bounds__(kCsBlock) void combined_rows_kernel(CsTerms ct, int
     T A[9];
 #pragma unroll
     for (int k = 0; k < 9; ++k) A[k] = cell[k];
-    for (int k = tid; k < kShiftTableSize; k += kCsBlock) {
-      const T sx = T(k % kShiftTableBase - kShiftTableRange), sy = T((k / kShiftTableBase) % kShiftTableBase - kShiftTableRange),
-              sz = T(k / (kShiftTableBase * kShiftTableBase) - kShiftTableRange);
-      shift_tab[k] = AtomRecord<T>{sx * A[0] + sy * A[3] + sz * A[6], sx * A[1] + sy * A[4] + sz * A[7],
-                                   sx * A[2] + sy * A[5] + sz * A[8], T(0)};
-    }
+    fill_shift_table<T, kCsBlock>(shift_tab, A);
   }
   if constexpr (WGRAD) {
     for (int t = 0; t < kCsMaxTerms; ++t) acc_s[t][tid] = T(0);
@@ -313,18 +309,6 @@ __global__ __launch_bounds__(kCsBlock) void combined_kenergy_kernel(int n_terms,
 //   grad_weights[t] = sum q u_t + (1/2V) sum_k mu G_t |rho^|^2 - 1/2 self_t sum q^2 - bg_t Q^2 / V
 // field_has_q: `field` holds q_a field[a] already (meshes without bricks)
 template <typename T>
-__device__ __forceinline__ double cs_block_sum(double v, double (*red)[kCsBlock / 64]) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) (*red)[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double s = 0.0;
-#pragma unroll
-  for (int w = 0; w < kCsBlock / 64; ++w) s += (*red)[w];
-  return s;
-}
-
-template <typename T>
 __global__ __launch_bounds__(kCsBlock) void combined_finish_kernel(CsTerms ct, int64_t N, double inv_vol, const T* __restrict__ q,
                                                                   const T* __restrict__ phi, const T* __restrict__ dc,
                                                                   const double* __restrict__ consts, T* __restrict__ pot,
@@ -357,17 +341,17 @@ __global__ __launch_bounds__(kCsBlock) void combined_finish_kernel(CsTerms ct, i
     s_q2 += row_part[b * kCsRowPart + 1];
     s_phi += row_part[b * kCsRowPart + 2];
   }
-  s_sr = cs_block_sum<T>(s_sr, &red);
-  s_q2 = cs_block_sum<T>(s_q2, &red);
-  s_phi = cs_block_sum<T>(s_phi, &red);
+  s_sr = block_sum<kCsBlock / 64>(s_sr, red);
+  s_q2 = block_sum<kCsBlock / 64>(s_q2, red);
+  s_phi = block_sum<kCsBlock / 64>(s_phi, red);
   if (threadIdx.x == 0) energy[0] = T(s_sr + 0.5 * s_phi - 0.5 * self_c * s_q2 - bg_c * Q * Q * inv_vol);
   if (grad_w) {
     for (int t = 0; t < nt; ++t) {
       double u = 0.0, ek = 0.0;
       for (int64_t b = threadIdx.x; b < n_row_blocks; b += kCsBlock) u += row_part[b * kCsRowPart + 4 + t];
       for (int64_t b = threadIdx.x; b < n_k_blocks; b += kCsBlock) ek += k_part[b * kCsMaxTerms + t];
-      u = cs_block_sum<T>(u, &red);
-      ek = cs_block_sum<T>(ek, &red);
+      u = block_sum<kCsBlock / 64>(u, red);
+      ek = block_sum<kCsBlock / 64>(ek, red);
       if (threadIdx.x == 0)
         grad_w[t] = T(u + 0.5 * inv_vol * ek - 0.5 * ct.self_t[t] * s_q2 - ct.bg_t[t] * Q * Q * inv_vol);
     }
@@ -469,13 +453,9 @@ int64_t mipme_combined_step_work(const mipme_fft_plan* plan, const mipme_mesh_t*
 
 int mipme_combined_step(const mipme_combined_step_args_t* in) {
   const char* who = "mipme_combined_step";
-  MIPME_REQUIRE(in != nullptr, "%s: NULL argument struct", who);
-  MIPME_REQUIRE(in->version == MIPME_COMBINED_STEP_VERSION, "%s: argument struct version %u, library expects %u", who, in->version,
-                unsigned(MIPME_COMBINED_STEP_VERSION));
-  MIPME_REQUIRE(in->size >= 16 && in->size <= 4096, "%s: implausible argument struct size %u", who, in->size);
   mipme_combined_step_args_t a;
-  std::memset(&a, 0, sizeof(a));
-  std::memcpy(&a, in, in->size < sizeof(a) ? in->size : sizeof(a));
+  int rc = load_args(in, a, MIPME_COMBINED_STEP_VERSION, who);
+  if (rc) return rc;
   // (what the arguments alone decide comes before anything that needs a device or reads the plan)
   MIPME_REQUIRE(a.dtype == MIPME_F32 || a.dtype == MIPME_F64, "%s: invalid dtype %d", who, int(a.dtype));
   MIPME_REQUIRE(a.comb != nullptr, "%s: combined descriptor is NULL", who);
@@ -505,16 +485,12 @@ int mipme_combined_step(const mipme_combined_step_args_t* in) {
     const double cheb[kErfcChebTerms] = MIPME_ERFC_CHEB;
     for (int k = 0; k < kErfcChebTerms; ++k) ct.cheb[k] = cheb[k];
   }
-  int rc;
   if ((rc = validate_mesh(a.mesh))) return rc;
   const mipme_mesh_t* m = a.mesh;
   MIPME_REQUIRE(m->n_channels == 1, "%s: the step serves one charge channel, the mesh has %d", who, int(m->n_channels));
   MIPME_REQUIRE(m->nx > 0 && (m->nx & (m->nx - 1)) == 0,
                 "%s: the step runs the fused convolution, which needs a power-of-two nx (the mesh has nx = %d)", who, int(m->nx));
-  MIPME_REQUIRE((a.shift_format & 0xff) == 2 && !(a.shift_format & MIPME_ROWS_PADDED),
-                "%s: the rows are read as 4-byte entries, other | code << 22 (shift_format 2), got shift_format %d", who,
-                int(a.shift_format));
-  MIPME_REQUIRE(a.n_atoms > 0 && a.n_atoms <= kCompactMaxAtoms, "%s: n_atoms must be in 1..2^22, got %lld", who, (long long)a.n_atoms);
+  if ((rc = check_step_rows(a.shift_format, a.n_atoms, who))) return rc;
   MIPME_REQUIRE(!a.grad_charges || !a.full_list,
                 "%s: grad_charges = 2 V needs a half list (a full list need not be symmetric)", who);
   MIPME_REQUIRE(!a.grad_weights || a.rho_hat, "%s: grad_weights needs rho_hat (the per-term mesh energies are sums over rho^)", who);

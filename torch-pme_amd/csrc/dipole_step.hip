@@ -20,7 +20,6 @@
 // The compacted list holds one of every +-k pair (the two terms of every sum above are equal) with the multiplicity folded into
 // G and dG by the caller.  No atomics: every sum has a fixed order, results are the same bits run after run.
 #include <cmath>
-#include <cstring>
 
 #include "dipole_device.h"
 #include "host.h"
@@ -32,6 +31,7 @@ constexpr int kDsBlock = 256;
 constexpr int kDsWaves = kDsBlock / 64;
 constexpr int kDsRowsPerBlock = kDsBlock / 16;  // 16 lanes per atom row
 static_assert(kRowLanes == 16, "row_sum of rows_body.h adds up the 16 lanes of a row");
+static_assert(kCompactAtomBits == kStepRowsAtomBits, "check_step_rows of host.h admits what the 4-byte entries hold");
 constexpr int kDsKPerBlock = 8;                 // k-vectors per block of the cell kernel, 32 lanes each
 constexpr int kDsKLanes = kDsBlock / kDsKPerBlock;
 constexpr int kDsTile = 256;                    // atoms staged per LDS tile of the cell kernel
@@ -74,23 +74,11 @@ static DsWork ds_work_layout(int64_t N, int64_t K, bool cell, void* base) {
   return w;
 }
 
-// sum over the workgroup, the waves in index order (every thread calls it)
-__device__ __forceinline__ double ds_block_sum(double v, double* red) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double s = 0.0;
-#pragma unroll
-  for (int w = 0; w < kDsWaves; ++w) s += red[w];
-  return s;
-}
-
 // sum_b p[b * stride + off], b < n: thread t adds b = t, t + 256, ... in that order, then the threads in a fixed order
 __device__ __forceinline__ double ds_strided_sum(const double* __restrict__ p, int64_t n, int stride, int off, double* red) {
   double s = 0.0;
   for (int64_t b = threadIdx.x; b < n; b += kDsBlock) s += p[b * stride + off];
-  return ds_block_sum(s, red);
+  return block_sum<kDsWaves>(s, red);
 }
 
 // ---- 1. records ------------------------------------------------------------------------------------------------------------
@@ -109,7 +97,7 @@ __global__ __launch_bounds__(kDsBlock) void dipole_step_records_kernel(int64_t N
   }
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
-    const double s = ds_block_sum(m[c], red);
+    const double s = block_sum<kDsWaves>(m[c], red);
     if (threadIdx.x == 0) mu_part[3 * int64_t(blockIdx.x) + c] = s;
   }
 }
@@ -178,12 +166,7 @@ __global__ __launch_bounds__(kDsBlock) void dipole_step_rows_kernel(DipPot<T> P,
     T A[9];
 #pragma unroll
     for (int k = 0; k < 9; ++k) A[k] = cell[k];
-    for (int k = tid; k < kShiftTableSize; k += kDsBlock) {
-      const T sx = T(k % kShiftTableBase - kShiftTableRange), sy = T((k / kShiftTableBase) % kShiftTableBase - kShiftTableRange),
-              sz = T(k / (kShiftTableBase * kShiftTableBase) - kShiftTableRange);
-      shift_tab[k] = AtomRecord<T>{sx * A[0] + sy * A[3] + sz * A[6], sx * A[1] + sy * A[4] + sz * A[7],
-                                   sx * A[2] + sy * A[5] + sz * A[8], T(0)};
-    }
+    fill_shift_table<T, kDsBlock>(shift_tab, A);
   }
   __syncthreads();
   const int sub = tid % 16;
@@ -370,7 +353,7 @@ __global__ __launch_bounds__(kDsBlock) void dipole_step_finish_kernel(int64_t N,
       e += 0.5 * double(mv[c]) * double(d);
     }
   }
-  e = ds_block_sum(e, red);
+  e = block_sum<kDsWaves>(e, red);
   if (threadIdx.x == 0) e_part[blockIdx.x] = e;
 }
 
@@ -496,13 +479,9 @@ int64_t mipme_dipole_step_work(int64_t n_atoms, int64_t n_k, int cell_gradient) 
 
 int mipme_dipole_step(const mipme_dipole_step_args_t* in) {
   const char* who = "mipme_dipole_step";
-  MIPME_REQUIRE(in != nullptr, "%s: NULL argument struct", who);
-  MIPME_REQUIRE(in->version == MIPME_DIPOLE_STEP_VERSION, "%s: argument struct version %u, library expects %u", who, in->version,
-                unsigned(MIPME_DIPOLE_STEP_VERSION));
-  MIPME_REQUIRE(in->size >= 16 && in->size <= 4096, "%s: implausible argument struct size %u", who, in->size);
   mipme_dipole_step_args_t a;
-  std::memset(&a, 0, sizeof(a));
-  std::memcpy(&a, in, in->size < sizeof(a) ? in->size : sizeof(a));
+  int rc = load_args(in, a, MIPME_DIPOLE_STEP_VERSION, who);
+  if (rc) return rc;
   // everything the arguments alone decide, before anything touches a device
   MIPME_REQUIRE(a.dtype == MIPME_F32 || a.dtype == MIPME_F64, "%s: invalid dtype %d", who, int(a.dtype));
   MIPME_REQUIRE(a.pot != nullptr, "%s: dipole descriptor is NULL", who);
@@ -512,10 +491,7 @@ int mipme_dipole_step(const mipme_dipole_step_args_t* in) {
   MIPME_REQUIRE(a.n_k == 0 || a.pot->smearing > 0,
                 "%s: n_k is %lld but the potential has no smearing (`smearing` is %g): a direct potential has no reciprocal part",
                 who, (long long)a.n_k, a.pot->smearing);
-  MIPME_REQUIRE((a.shift_format & 0xff) == 2 && !(a.shift_format & MIPME_ROWS_PADDED),
-                "%s: the rows are read as 4-byte entries, other | code << 22 (shift_format 2), got shift_format %d", who,
-                int(a.shift_format));
-  MIPME_REQUIRE(a.n_atoms > 0 && a.n_atoms <= kCompactMaxAtoms, "%s: n_atoms must be in 1..2^22, got %lld", who, (long long)a.n_atoms);
+  if ((rc = check_step_rows(a.shift_format, a.n_atoms, who))) return rc;
   MIPME_REQUIRE(std::isfinite(a.inv_volume) && a.inv_volume > 0, "%s: inv_volume must be positive, got %g", who, a.inv_volume);
   MIPME_REQUIRE(!a.cell_gradient || (a.grad_cell && a.inv_cell), "%s: cell_gradient needs grad_cell and inv_cell", who);
   MIPME_REQUIRE(!a.cell_gradient || a.n_k == 0 || a.dG, "%s: cell_gradient needs dG (dG/dk^2 of the compacted k-vectors)", who);

@@ -494,6 +494,34 @@ static int frames_table_slab_t(int n_frames, const mipme_frame_t* fr, const mipm
   return MIPME_OK;
 }
 
+// What mipme_frames_forward, mipme_frames_step and mipme_frames_slab_step share, in the order their refusals have always had: the
+// frames and the required buffers, then the entry point's own checks (`own_checks`, a callable returning a status), the plan, the
+// potential -- 1/r or 1/r^6, with the slab term 1/r alone -- and the launches.  cell_work: NULL without the cell gradient
+template <typename OwnChecks>
+static int frames_launch(const char* who, const mipme_frames_step_args_t& a, void* cell_work, bool slab, OwnChecks&& own_checks) {
+  int rc = frames_check(a.dtype, a.n_frames, a.frames);
+  if (rc) return rc;
+  MIPME_REQUIRE(a.plan && a.pot && a.device_table && a.G && a.rho_mesh_all && a.hat_work_all && a.phi_mesh_all && a.dc_all &&
+                    a.G_stride >= 0,
+                "NULL buffer passed to %s", who);
+  if ((rc = own_checks())) return rc;
+  MIPME_REQUIRE(fft_plan_xfused(a.plan) && fft_plan_batch(a.plan) == a.n_frames,
+                "%s needs a plan with batch = n_frames and a power-of-two nx", who);
+  SRPot s;
+  if ((rc = make_srpot(a.pot, s))) return rc;
+  const int pfast = fast_rs_exponent(s);
+  if (slab)
+    MIPME_REQUIRE(pfast == 1, "%s: the slab term exists for 1/r with a smearing", who);
+  else
+    MIPME_REQUIRE(pfast == 1 || pfast == 6, "the frames path covers 1/r and 1/r^6 with a smearing");
+  hipStream_t st = (hipStream_t)a.stream;
+  DT_SWITCH(a.dtype,
+            frames_forward_t<float>(a.plan, st, a.n_frames, a.frames, a.device_table, a.G, a.G_stride, a.rho_mesh_all, a.hat_work_all,
+                                    a.phi_mesh_all, a.dc_all, pfast, cell_work, slab),
+            frames_forward_t<double>(a.plan, st, a.n_frames, a.frames, a.device_table, a.G, a.G_stride, a.rho_mesh_all, a.hat_work_all,
+                                     a.phi_mesh_all, a.dc_all, pfast, cell_work, slab));
+}
+
 extern "C" {
 
 int64_t mipme_frames_slab_work(void) { return kSlabWork; }
@@ -519,28 +547,12 @@ int mipme_frames_slab_step(const mipme_frames_slab_step_args_t* s) {
   MIPME_REQUIRE(a->size == sizeof(mipme_frames_step_args_t) && a->version == MIPME_FRAMES_STEP_VERSION,
                 "mipme_frames_slab_step_args_t.step: size %u / version %u, this library expects %zu / %d", a->size, a->version,
                 sizeof(mipme_frames_step_args_t), MIPME_FRAMES_STEP_VERSION);
-  int rc = frames_check(a->dtype, a->n_frames, a->frames);
-  if (rc) return rc;
-  MIPME_REQUIRE(a->plan && a->pot && a->device_table && a->G && a->rho_mesh_all && a->hat_work_all && a->phi_mesh_all && a->dc_all &&
-                    a->G_stride >= 0,
-                "NULL buffer passed to mipme_frames_slab_step");
-  MIPME_REQUIRE(!a->cell_gradient || a->cell_work, "mipme_frames_slab_step: the cell gradient needs cell_work");
-  if ((rc = frames_slab_check(a->n_frames, a->frames, a->pot, s->slab, s->slab_work, s->slab_work_stride, "mipme_frames_slab_step")))
-    return rc;
-  if ((rc = frames_contract_check(a->n_frames, a->frames, a->cell_gradient != 0))) return rc;
-  MIPME_REQUIRE(fft_plan_xfused(a->plan) && fft_plan_batch(a->plan) == a->n_frames,
-                "mipme_frames_slab_step needs a plan with batch = n_frames and a power-of-two nx");
-  SRPot sp;
-  if ((rc = make_srpot(a->pot, sp))) return rc;
-  const int pfast = fast_rs_exponent(sp);
-  MIPME_REQUIRE(pfast == 1, "mipme_frames_slab_step: the slab term exists for 1/r with a smearing");
-  hipStream_t st = (hipStream_t)a->stream;
-  void* cw = a->cell_gradient ? a->cell_work : nullptr;
-  DT_SWITCH(a->dtype,
-            frames_forward_t<float>(a->plan, st, a->n_frames, a->frames, a->device_table, a->G, a->G_stride, a->rho_mesh_all,
-                                    a->hat_work_all, a->phi_mesh_all, a->dc_all, pfast, cw, true),
-            frames_forward_t<double>(a->plan, st, a->n_frames, a->frames, a->device_table, a->G, a->G_stride, a->rho_mesh_all,
-                                     a->hat_work_all, a->phi_mesh_all, a->dc_all, pfast, cw, true));
+  const char* who = "mipme_frames_slab_step";
+  return frames_launch(who, *a, a->cell_gradient ? a->cell_work : nullptr, true, [&]() -> int {
+    MIPME_REQUIRE(!a->cell_gradient || a->cell_work, "%s: the cell gradient needs cell_work", who);
+    const int rc = frames_slab_check(a->n_frames, a->frames, a->pot, s->slab, s->slab_work, s->slab_work_stride, who);
+    return rc ? rc : frames_contract_check(a->n_frames, a->frames, a->cell_gradient != 0);
+  });
 }
 
 int64_t mipme_frames_table_bytes(int dtype, int n_frames) {
@@ -585,26 +597,10 @@ int mipme_frames_step(const mipme_frames_step_args_t* a) {
                 sizeof(mipme_frames_step_args_t));
   MIPME_REQUIRE(a->version == MIPME_FRAMES_STEP_VERSION, "mipme_frames_step_args_t: version %u, this library expects %d", a->version,
                 MIPME_FRAMES_STEP_VERSION);
-  int rc = frames_check(a->dtype, a->n_frames, a->frames);
-  if (rc) return rc;
-  MIPME_REQUIRE(a->plan && a->pot && a->device_table && a->G && a->rho_mesh_all && a->hat_work_all && a->phi_mesh_all && a->dc_all &&
-                    a->G_stride >= 0,
-                "NULL buffer passed to mipme_frames_step");
-  MIPME_REQUIRE(!a->cell_gradient || a->cell_work, "mipme_frames_step: the cell gradient needs cell_work");
-  if ((rc = frames_contract_check(a->n_frames, a->frames, a->cell_gradient != 0))) return rc;
-  MIPME_REQUIRE(fft_plan_xfused(a->plan) && fft_plan_batch(a->plan) == a->n_frames,
-                "mipme_frames_step needs a plan with batch = n_frames and a power-of-two nx");
-  SRPot s;
-  if ((rc = make_srpot(a->pot, s))) return rc;
-  const int pfast = fast_rs_exponent(s);
-  MIPME_REQUIRE(pfast == 1 || pfast == 6, "the frames path covers 1/r and 1/r^6 with a smearing");
-  hipStream_t st = (hipStream_t)a->stream;
-  void* cw = a->cell_gradient ? a->cell_work : nullptr;
-  DT_SWITCH(a->dtype,
-            frames_forward_t<float>(a->plan, st, a->n_frames, a->frames, a->device_table, a->G, a->G_stride, a->rho_mesh_all,
-                                    a->hat_work_all, a->phi_mesh_all, a->dc_all, pfast, cw),
-            frames_forward_t<double>(a->plan, st, a->n_frames, a->frames, a->device_table, a->G, a->G_stride, a->rho_mesh_all,
-                                     a->hat_work_all, a->phi_mesh_all, a->dc_all, pfast, cw));
+  return frames_launch("mipme_frames_step", *a, a->cell_gradient ? a->cell_work : nullptr, false, [&]() -> int {
+    MIPME_REQUIRE(!a->cell_gradient || a->cell_work, "mipme_frames_step: the cell gradient needs cell_work");
+    return frames_contract_check(a->n_frames, a->frames, a->cell_gradient != 0);
+  });
 }
 
 int mipme_frames_table_build(int dtype, int n_frames, const mipme_frame_t* frames, const mipme_potential_t* pot,
@@ -629,22 +625,11 @@ int mipme_frames_table_energy_log(int dtype, int n_frames, void* host_table, int
 int mipme_frames_forward(mipme_fft_plan* plan, void* stream, int dtype, int n_frames, const mipme_frame_t* frames,
                          const mipme_potential_t* pot, const void* device_table, const void* G, int64_t G_stride,
                          void* rho_mesh_all, void* hat_work_all, void* phi_mesh_all, void* dc_all) {
-  int rc = frames_check(dtype, n_frames, frames);
-  if (rc) return rc;
-  MIPME_REQUIRE(plan && pot && device_table && G && rho_mesh_all && hat_work_all && phi_mesh_all && dc_all && G_stride >= 0,
-                "NULL buffer passed to mipme_frames_forward");
-  MIPME_REQUIRE(fft_plan_xfused(plan) && fft_plan_batch(plan) == n_frames,
-                "mipme_frames_forward needs a plan with batch = n_frames and a power-of-two nx");
-  SRPot s;
-  if ((rc = make_srpot(pot, s))) return rc;
-  const int pfast = fast_rs_exponent(s);
-  MIPME_REQUIRE(pfast == 1 || pfast == 6, "the frames path covers 1/r and 1/r^6 with a smearing");
-  hipStream_t st = (hipStream_t)stream;
-  DT_SWITCH(dtype,
-            frames_forward_t<float>(plan, st, n_frames, frames, device_table, G, G_stride, rho_mesh_all, hat_work_all,
-                                    phi_mesh_all, dc_all, pfast),
-            frames_forward_t<double>(plan, st, n_frames, frames, device_table, G, G_stride, rho_mesh_all, hat_work_all,
-                                     phi_mesh_all, dc_all, pfast));
+  mipme_frames_step_args_t a{};  // (the step's arguments without its flags; neither size nor version is looked at)
+  a.plan = plan, a.stream = stream, a.dtype = dtype, a.n_frames = n_frames, a.frames = frames, a.pot = pot;
+  a.device_table = device_table, a.G = G, a.G_stride = G_stride;
+  a.rho_mesh_all = rho_mesh_all, a.hat_work_all = hat_work_all, a.phi_mesh_all = phi_mesh_all, a.dc_all = dc_all;
+  return frames_launch("mipme_frames_forward", a, nullptr, false, [] { return int(MIPME_OK); });
 }
 
 int64_t mipme_frames_counter_ints(const mipme_mesh_t* mesh, int64_t n_atoms, int dtype) {

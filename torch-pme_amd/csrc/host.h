@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <climits>
 #include <cmath>
+#include <cstring>
 
 #include "common.h"
 
@@ -27,6 +28,29 @@ constexpr int dtype_of() {
 // grid of a grid-stride kernel over n items: one pass of `block`-thread blocks up to 8 per CU of a 256-CU device (block = 256)
 inline unsigned stride_grid(int64_t n, int block) {
   return unsigned(std::max<int64_t>(1, std::min<int64_t>((n + block - 1) / block, 2048)));
+}
+
+// Copy a caller's versioned argument struct into the library's own layout: only the first `size` bytes the caller
+// compiled are read, everything after them stays zero (fields are only ever appended).
+template <typename A>
+int load_args(const A* in, A& out, unsigned version, const char* what) {
+  MIPME_REQUIRE(in != nullptr, "%s: NULL argument struct", what);
+  MIPME_REQUIRE(in->version == version, "%s: argument struct version %u, library expects %u", what, in->version, version);
+  MIPME_REQUIRE(in->size >= 16 && in->size <= 4096, "%s: implausible argument struct size %u", what, in->size);
+  memset(&out, 0, sizeof(A));
+  memcpy(&out, in, in->size < sizeof(A) ? in->size : sizeof(A));
+  return MIPME_OK;
+}
+
+// The rows a step entry point walks itself (mipme_combined_step, mipme_dipole_step): unpadded, 4-byte entries whose low
+// kStepRowsAtomBits bits hold the partner (kCompactAtomBits of rows_body.h, which this header does not include)
+static constexpr int kStepRowsAtomBits = 22;
+inline int check_step_rows(int shift_format, int64_t n_atoms, const char* who) {
+  MIPME_REQUIRE((shift_format & 0xff) == 2 && !(shift_format & MIPME_ROWS_PADDED),
+                "%s: the rows are read as 4-byte entries, other | code << 22 (shift_format 2), got shift_format %d", who, shift_format);
+  MIPME_REQUIRE(n_atoms > 0 && n_atoms <= (int64_t(1) << kStepRowsAtomBits), "%s: n_atoms must be in 1..2^22, got %lld", who,
+                (long long)n_atoms);
+  return MIPME_OK;
 }
 
 // ---- mesh.hip: particle <-> mesh without bins -------------------------------------------------------------------------------

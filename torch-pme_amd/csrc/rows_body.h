@@ -88,6 +88,33 @@ __device__ __forceinline__ T body_wave_sum(T v) {
 #endif
 }
 
+// Sum of v over a workgroup of WAVES wavefronts, the waves added in index order (every thread calls it and gets the sum);
+// red: WAVES doubles of LDS, free again after the call
+template <int WAVES>
+__device__ __forceinline__ double block_sum(double v, double* red) {
+  v = wave_sum(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double s = 0.0;
+#pragma unroll
+  for (int w = 0; w < WAVES; ++w) s += red[w];
+  return s;
+}
+
+// tab[code] = the Cartesian shift vector of table code `code` in the cell A (rows), filled by the BS threads of the workgroup;
+// the caller synchronises.  For the step kernels (combined_step.hip, dipole_step.hip): the three row bodies below keep their own
+// copy of this loop, since calling the helper there changes the instruction text of 48 settled kernels of topology.hip
+template <typename T, int BS>
+__device__ __forceinline__ void fill_shift_table(AtomRecord<T>* tab, const T (&A)[9]) {
+  for (int k = threadIdx.x; k < kShiftTableSize; k += BS) {
+    const T sx = T(k % kShiftTableBase - kShiftTableRange), sy = T((k / kShiftTableBase) % kShiftTableBase - kShiftTableRange),
+            sz = T(k / (kShiftTableBase * kShiftTableBase) - kShiftTableRange);
+    tab[k] = AtomRecord<T>{sx * A[0] + sy * A[3] + sz * A[6], sx * A[1] + sy * A[4] + sz * A[7],
+                           sx * A[2] + sy * A[5] + sz * A[8], T(0)};
+  }
+}
+
 __device__ __forceinline__ int unpack8(int word, int k) { return (word << (24 - 8 * k)) >> 24; }
 
 enum FusedMode {

@@ -15,8 +15,35 @@ import math
 import numpy as np
 import torch
 
-from . import _lib, ops
+from . import _lib, analytic, ops
 
+
+def _capture_graph(device, warm_up, body, between=None):
+    """The capture protocol of every graphed step: ``warm_up()`` on a side stream (plans, caches and lazy module loads get built
+    off the default stream), join, device synchronisation, ``between()`` -- host-side work that must follow the warm-up and
+    precede the capture --, then ``body()`` captured into a new graph, which is returned."""
+    side = torch.cuda.Stream(device)
+    side.wait_stream(torch.cuda.current_stream(device))
+    with torch.cuda.stream(side):
+        warm_up()
+    torch.cuda.current_stream(device).wait_stream(side)
+    torch.cuda.synchronize(device)
+    if between is not None:
+        between()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        body()
+    return graph
+
+
+def _check_slab_potential(potential):
+    """``slab_correction``: the 2-D periodic term exists for 1/r and rides on the mesh part."""
+    desc = potential._descriptor()
+    if not (desc.kind == _lib.COULOMB or desc.exponent == 1):
+        raise ValueError("`slab_correction`: the slab term exists for 1/r only (CoulombPotential, or "
+                         "InversePowerLawPotential(exponent=1))")
+    if potential.smearing is None:
+        raise ValueError("`slab_correction` belongs to the mesh part: the potential needs a smearing")
 
 
 def _refuse_spline(calculator, what: str):
@@ -55,7 +82,7 @@ class _LiveStep:
         self.rec = torch.empty((N, 4), dtype=dtype, device=device)
         self.rec[:, :3] = positions.detach()
         self.rec[:, 3] = charges.detach()[:, 0]
-        cdtype = torch.complex64 if dtype == torch.float32 else torch.complex128
+        cdtype = analytic._complex_dtype(dtype)
         self.cell = cell.detach().to(dtype).contiguous()
         self.rho = torch.empty(geom.ns, dtype=dtype, device=device)
         self.phi = torch.empty(geom.ns, dtype=dtype, device=device)
@@ -239,12 +266,7 @@ class GraphedEnergyForces:
             flags = [bool(p) for p in periodic]
             if len(flags) != 3 or sum(flags) != 2:
                 raise ValueError(f"`slab_correction` needs exactly two periodic axes, got periodic={tuple(flags)}")
-            desc = calculator.potential._descriptor()
-            if not (desc.kind == _lib.COULOMB or desc.exponent == 1):
-                raise ValueError("`slab_correction`: the slab term exists for 1/r only (CoulombPotential, or "
-                                 "InversePowerLawPotential(exponent=1))")
-            if calculator.potential.smearing is None:
-                raise ValueError("`slab_correction` belongs to the mesh part: the potential needs a smearing")
+            _check_slab_potential(calculator.potential)
             self._slab_axis = flags.index(False)
             # the calculator looks the axis up per (tensor, version): the warm-up pays the one host copy, the capture none
             self._periodic = torch.tensor(flags, dtype=torch.bool, device=positions.device)
@@ -311,18 +333,9 @@ class GraphedEnergyForces:
 
     # ---- device neighbour list --------------------------------------------------------------------------------------------
     def _capture_refresh(self):
-        device = self.pos.device
-        side = torch.cuda.Stream(device)
-        side.wait_stream(torch.cuda.current_stream(device))
         if self._live is not None:
             self._live.rows = (self.stream.row_ptr, self.stream.words, 2 | _lib.ROWS_PADDED)
-        with torch.cuda.stream(side):
-            self._refresh_eager()
-        torch.cuda.current_stream(device).wait_stream(side)
-        torch.cuda.synchronize(device)
-        self.refresh_graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.refresh_graph):
-            self._refresh_eager()
+        self.refresh_graph = _capture_graph(self.pos.device, self._refresh_eager, self._refresh_eager)
 
     def _refresh_eager(self):
         self.stream.update()
@@ -368,23 +381,23 @@ class GraphedEnergyForces:
         self._capture(neighbor_indices, neighbor_shifts)
 
     def _capture_live(self):
-        device = self.pos.device
-        side = torch.cuda.Stream(device)
-        side.wait_stream(torch.cuda.current_stream(device))
         self._live.log = None  # (a re-capture after an overflow warms up again: those evaluations are not the caller's)
-        with torch.cuda.stream(side):  # warm-up off the default stream (the plan allocates its scratch on first use)
+
+        def warm_up():  # (the plan allocates its scratch on first use)
             for _ in range(self._warmup):
                 self._live.step()
-        torch.cuda.current_stream(device).wait_stream(side)
-        torch.cuda.synchronize(device)
-        self._keepalive = [self._live, self.stream, getattr(self.calc, "_cache", None)]
-        self._live.log = self.energy_log  # (from here on: the gather of the step appends its energy to the log)
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
+
+        def between():
+            self._keepalive = [self._live, self.stream, getattr(self.calc, "_cache", None)]
+            self._live.log = self.energy_log  # (from here on: the gather of the step appends its energy to the log)
+
+        def body():
             self._live.step()
             self.energy = self._live.energy
             if self._epilogue is not None:
                 self._epilogue(self)
+
+        self.graph = _capture_graph(self.pos.device, warm_up, body, between)
         self.energy, self.forces, self.distances = self._live.energy, self._live.grad, None
         self.charge_grad = self._live.grad_q
         self.cell_grad = None if self._live.grad_cell is None else self._live.grad_cell[18:27].view(3, 3)
@@ -396,9 +409,8 @@ class GraphedEnergyForces:
         calculator, device, warmup = self.calc, self.pos.device, self._warmup
         self.pairs = neighbor_indices
         self.shifts = None if neighbor_shifts is None else neighbor_shifts.to(self.pos.dtype).contiguous()
-        side = torch.cuda.Stream(device)
-        side.wait_stream(torch.cuda.current_stream(device))
-        with torch.cuda.stream(side):  # warm-up off the default stream: plans, topology, filter caches get built
+
+        def warm_up():  # plans, topology, filter caches get built
             for it in range(max(1, warmup) + 1):
                 self.pos.grad = self.cell.grad = self.q.grad = None
                 self._eval()
@@ -414,26 +426,26 @@ class GraphedEnergyForces:
                             self.q = self.q.clone().requires_grad_(True)
                         if self.cell_gradient:
                             self.cell.requires_grad_(True)
-        torch.cuda.current_stream(device).wait_stream(side)
-        torch.cuda.synchronize(device)
-        self.pos.grad = self.cell.grad = self.q.grad = None
-        # The captured graph holds raw pointers into buffers that were built during the warm-up and live in caches: the
-        # transposed pair list (+ packed shifts), the calculator's filter table, the reduction scratch.  Keep them alive
-        # for the lifetime of the graph, whatever the caches evict later.
-        topo = ops.get_topology(self.pairs, self.pos.shape[0]) if ops.PAIR_MODE == "rows" else None
-        self._keepalive = [
-            topo,
-            getattr(calculator, "_cache", None),
-            ops._dot_scratch(device, self.q.data_ptr()),
-        ]
-        if isinstance(topo, ops.PairTopology):
-            # the entry streams are single-slot caches keyed by the shifts tensor: an eager call with the same pairs and other
-            # shifts would replace the slot and free the buffer the graph reads -- pin the concrete tensors
-            self._keepalive += [topo.row_ptr, topo.entries, topo._ent32, topo._ent_sh, topo._packed, topo._pair_sh]
-        elif topo is not None:
-            self._keepalive += [self.stream.row_ptr, self.stream.words]
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
+
+        def between():
+            self.pos.grad = self.cell.grad = self.q.grad = None
+            # The captured graph holds raw pointers into buffers that were built during the warm-up and live in caches: the
+            # transposed pair list (+ packed shifts), the calculator's filter table, the reduction scratch.  Keep them alive
+            # for the lifetime of the graph, whatever the caches evict later.
+            topo = ops.get_topology(self.pairs, self.pos.shape[0]) if ops.PAIR_MODE == "rows" else None
+            self._keepalive = [
+                topo,
+                getattr(calculator, "_cache", None),
+                ops._dot_scratch(device, self.q.data_ptr()),
+            ]
+            if isinstance(topo, ops.PairTopology):
+                # the entry streams are single-slot caches keyed by the shifts tensor: an eager call with the same pairs and other
+                # shifts would replace the slot and free the buffer the graph reads -- pin the concrete tensors
+                self._keepalive += [topo.row_ptr, topo.entries, topo._ent32, topo._ent_sh, topo._packed, topo._pair_sh]
+            elif topo is not None:
+                self._keepalive += [self.stream.row_ptr, self.stream.words]
+
+        def body():
             self.energy = self._eval(log=self.energy_log)
             self.forces = self.pos.grad
             if self.energy_log is not None and not (self._tail is not None and self._tail.get("logged")):
@@ -449,6 +461,8 @@ class GraphedEnergyForces:
                 # the backward pass is seeded with -1 (so that pos.grad is the force): undo the sign for charges and cell
                 self.charge_grad = -self.q.grad if self.charge_gradient else None
                 self.cell_grad = -self.cell.grad if self.cell_gradient else None
+
+        self.graph = _capture_graph(device, warm_up, body, between)
 
     def _eval(self, log=None):
         # the pair kernel of the calculator forms the distances itself (no separate pass over the list); "virtual": in
@@ -609,7 +623,7 @@ class GraphedFrameBatch:
             raise ValueError(f"all frames must give the same mesh, got {[g.ns for g in geoms]}")
         self.ns = ns
         M, Mh = geoms[0].n_mesh, geoms[0].n_half
-        cdtype = torch.complex64 if dtype == torch.float32 else torch.complex128
+        cdtype = analytic._complex_dtype(dtype)
         self._G = torch.stack(Gs).contiguous()
         self._rho = torch.empty((F,) + ns, dtype=dtype, device=device)
         self._phi = torch.empty((F,) + ns, dtype=dtype, device=device)
@@ -714,21 +728,18 @@ class GraphedFrameBatch:
             _lib.check(lib.mipme_frames_table_energy_log(dt, F, host.ctypes.data, nbytes, self.energy_log.values.data_ptr(),
                                                          self.energy_log.cursor.data_ptr(), self.energy_log.capacity))
         self._table = torch.from_numpy(host).to(device)
-        # warm-up (plans, lazy module loads) off the default stream, then capture
-        side = torch.cuda.Stream(device)
-        side.wait_stream(torch.cuda.current_stream(device))
-        with torch.cuda.stream(side):
+
+        def warm_up():  # (plans, lazy module loads)
             for _ in range(max(1, warmup)):
                 self._eval()
-        torch.cuda.current_stream(device).wait_stream(side)
-        torch.cuda.synchronize(device)
-        if self.energy_log is not None:
-            self.energy_log.reset()  # (the warm-up evaluations above appended too)
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
+
+        def body():
             self._eval()
             if epilogue is not None:
                 epilogue(self)
+
+        # (the warm-up evaluations appended to the log too: reset it before the capture)
+        self.graph = _capture_graph(device, warm_up, body, None if self.energy_log is None else self.energy_log.reset)
         self.forces = [p.grad for p in self.pos]
 
     @staticmethod
@@ -755,12 +766,7 @@ class GraphedFrameBatch:
                 raise ValueError(f"frame {k}: `slab_correction` needs exactly two periodic axes (or three: a fully periodic frame), "
                                  f"got periodic={tuple(flags)}")
             codes.append(0 if all(flags) else flags.index(False) + 1)
-        desc = calculator.potential._descriptor()
-        if not (desc.kind == _lib.COULOMB or desc.exponent == 1):
-            raise ValueError("`slab_correction`: the slab term exists for 1/r only (CoulombPotential, or "
-                             "InversePowerLawPotential(exponent=1))")
-        if calculator.potential.smearing is None:
-            raise ValueError("`slab_correction` belongs to the mesh part: the potential needs a smearing")
+        _check_slab_potential(calculator.potential)
         return codes if any(codes) else None
 
     def _launch_forward(self):
@@ -813,6 +819,37 @@ class GraphedFrameBatch:
         return out
 
 
+class _ExplicitListStep:
+    """What :class:`GraphedCombinedStep` and :class:`GraphedDipoleStep` share: a step (``self._launch()``, every launch on the
+    current stream) whose row kernel walks an explicit pair list, captured for that list.  The subclass sets ``device``,
+    ``dtype``, ``n_atoms`` and ``_warmup`` before it calls :meth:`_capture`."""
+
+    _pinned = ()  # what else the captured graph holds raw pointers into (the subclass sets it before the first capture)
+
+    def _capture(self, neighbor_indices, neighbor_shifts, copies=()):
+        """Pack the list into ``row_ptr`` + 4-byte entries (other | code << 22), copy ``copies`` -- (buffer, new values or
+        ``None``) pairs -- and capture the step.  A list the entries do not hold is refused before anything of the object changes:
+        the graph it replays, ``pairs`` and the buffers stay as they were."""
+        sh = neighbor_shifts.to(self.dtype).contiguous()
+        topo = ops.get_topology(neighbor_indices, self.n_atoms)
+        ent32 = topo.compact_entries(sh, neighbor_shifts)
+        if ent32 is None:
+            raise ValueError(f"{type(self).__name__}: the cell shifts must be integers in [-3, 3] (the 4-byte pair entries of the "
+                             "row kernel) and the system at most 2^22 atoms")
+        with torch.no_grad():
+            for buf, new in copies:
+                if new is not None:
+                    buf.copy_(new)
+        self.pairs, self._row_ptr, self._ent32 = neighbor_indices, topo.row_ptr, ent32
+        # the captured graph holds raw pointers into cached buffers (the transposed list, the entry stream)
+        self._keepalive = [topo, topo.row_ptr, ent32, sh, *self._pinned]
+        self.graph = _capture_graph(self.device, self._warm_up, self._launch)
+
+    def _warm_up(self):  # (the plan allocates its scratch on first use)
+        for _ in range(self._warmup):
+            self._launch()
+
+
 def _combined_refusal(pot) -> str | None:
     """Why ``combined.plan`` does not serve this combination in the graphed step (``None``: it does)."""
     from .potentials import CombinedPotential, CoulombPotential, InversePowerLawPotential, SplinePotential
@@ -835,7 +872,7 @@ def _combined_refusal(pot) -> str | None:
     return None
 
 
-class GraphedCombinedStep:
+class GraphedCombinedStep(_ExplicitListStep):
     """``E, F, dE_dw = step(positions)`` for a calculator with a :class:`~torchpme_amd.CombinedPotential` -- Coulomb +
     dispersion, or any weighted sum of range-separated 1/r^p terms -- replayed from one HIP graph: the MD form of the eager call.
 
@@ -862,7 +899,7 @@ class GraphedCombinedStep:
 
     def __init__(self, calculator, charges, cell, positions, neighbor_indices, neighbor_shifts, weight_gradient: bool = True,
                  charge_gradient: bool = False, warmup: int = 3):
-        from . import analytic, combined
+        from . import combined
         from .potentials import CombinedPotential
 
         pot = getattr(calculator, "potential", None)
@@ -901,7 +938,7 @@ class GraphedCombinedStep:
         if not self._plan.xfused:
             raise ValueError(f"GraphedCombinedStep needs a power-of-two mesh along x, the cell gives {geom.ns}")
         new = lambda *shape, dt=dtype: torch.empty(shape, dtype=dt, device=device)  # noqa: E731
-        cdtype = torch.complex64 if dtype == torch.float32 else torch.complex128
+        cdtype = analytic._complex_dtype(dtype)
         self.q = charges.detach().contiguous()
         self.cell = cell.detach().to(dtype).contiguous()
         self.pos = positions.detach().clone().contiguous()
@@ -923,31 +960,12 @@ class GraphedCombinedStep:
         self._nan_flag = calculator._nan_flag_ptr()
         calculator._nan_shape = [1, *geom.ns]
         self._warmup = max(1, int(warmup))
+        self._pinned = (self._tables, self._plan, self._geom, getattr(self.calc, "_plan_store", None))  # members' tables, plan
         self._capture(neighbor_indices, neighbor_shifts)
 
-    def _capture(self, neighbor_indices, neighbor_shifts):
-        device, N = self.device, self.n_atoms
-        self.pairs = neighbor_indices
-        sh = neighbor_shifts.to(self.dtype).contiguous()
-        topo = ops.get_topology(neighbor_indices, N)
-        ent32 = topo.compact_entries(sh, neighbor_shifts)
-        if ent32 is None:
-            raise ValueError("GraphedCombinedStep: the cell shifts must be integers in [-3, 3] (the 4-byte pair entries of the "
-                             "row kernel) and the system at most 2^22 atoms")
-        self._row_ptr, self._ent32 = topo.row_ptr, ent32
-        # the captured graph holds raw pointers into cached buffers (transposed list, entry stream, the members' tables, the plan)
-        self._keepalive = [topo, topo.row_ptr, ent32, sh, self._tables, self._plan, self._geom, getattr(self.calc, "_plan_store", None)]
-        side = torch.cuda.Stream(device)
-        side.wait_stream(torch.cuda.current_stream(device))
-        with torch.cuda.stream(side):  # warm-up off the default stream: the plan allocates its scratch on first use
-            self._w.copy_(self.calc.potential.weights.detach())
-            for _ in range(self._warmup):
-                self._launch()
-        torch.cuda.current_stream(device).wait_stream(side)
-        torch.cuda.synchronize(device)
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
-            self._launch()
+    def _warm_up(self):
+        self._w.copy_(self.calc.potential.weights.detach())
+        super()._warm_up()
 
     def _launch(self):
         with _lib.on_device(self.device):
@@ -967,10 +985,7 @@ class GraphedCombinedStep:
 
     def recapture(self, neighbor_indices, neighbor_shifts, positions: torch.Tensor | None = None) -> None:
         """New neighbour list: rebuild the pair topology and capture the step again; every other buffer is kept."""
-        if positions is not None:
-            with torch.no_grad():
-                self.pos.copy_(positions)
-        self._capture(neighbor_indices, neighbor_shifts)
+        self._capture(neighbor_indices, neighbor_shifts, [(self.pos, positions)])
 
     def __call__(self, positions: torch.Tensor | None = None):
         """``E, F`` (+ ``dE/dweights`` with ``weight_gradient``, + ``dE/dcharges`` with ``charge_gradient``, in that order) of the
@@ -1004,7 +1019,7 @@ def _compact_kvectors(freq: np.ndarray, ns):
     return rows, np.where(unpaired[rows], 1.0, 2.0)
 
 
-class GraphedDipoleStep:
+class GraphedDipoleStep(_ExplicitListStep):
     """``E, F, dE_dmu = step(positions, dipoles)`` for a :class:`~torchpme_amd.CalculatorDipole`, replayed from one HIP graph: the
     MD form of the eager call for a fixed neighbour list and cell (dipolar fluids, polarisable models).
 
@@ -1124,28 +1139,6 @@ class GraphedDipoleStep:
                 raise ValueError("GraphedDipoleStep: the cell shifts must be integers in [-3, 3] (the 4-byte pair entries of the row "
                                  "kernel); wrap the positions into the cell or use a shorter cutoff")
 
-    def _capture(self, neighbor_indices, neighbor_shifts):
-        device, N = self.device, self.n_atoms
-        self.pairs = neighbor_indices
-        sh = neighbor_shifts.to(self.dtype).contiguous()
-        topo = ops.get_topology(neighbor_indices, N)
-        ent32 = topo.compact_entries(sh, neighbor_shifts)
-        if ent32 is None:
-            raise ValueError("GraphedDipoleStep: the cell shifts must be integers in [-3, 3] (the 4-byte pair entries of the row "
-                             "kernel) and the system at most 2^22 atoms")
-        self._row_ptr, self._ent32 = topo.row_ptr, ent32
-        self._keepalive = [topo, topo.row_ptr, ent32, sh]  # the captured graph holds raw pointers into these
-        side = torch.cuda.Stream(device)
-        side.wait_stream(torch.cuda.current_stream(device))
-        with torch.cuda.stream(side):
-            for _ in range(self._warmup):
-                self._launch()
-        torch.cuda.current_stream(device).wait_stream(side)
-        torch.cuda.synchronize(device)
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
-            self._launch()
-
     def _launch(self):
         with _lib.on_device(self.device):
             a = _lib.DipoleStepArgs(
@@ -1163,12 +1156,7 @@ class GraphedDipoleStep:
                   dipoles: torch.Tensor | None = None) -> None:
         """New neighbour list: rebuild the pair topology and capture the step again; every other buffer is kept."""
         self._check_list(neighbor_indices, neighbor_shifts)
-        with torch.no_grad():
-            if positions is not None:
-                self.pos.copy_(positions)
-            if dipoles is not None:
-                self.mu.copy_(dipoles)
-        self._capture(neighbor_indices, neighbor_shifts)
+        self._capture(neighbor_indices, neighbor_shifts, [(self.pos, positions), (self.mu, dipoles)])
 
     def __call__(self, positions: torch.Tensor | None = None, dipoles: torch.Tensor | None = None):
         """``E, F, dE_dmu`` (+ ``dE_dcell`` with ``cell_gradient``) of the current -- or the given -- positions and dipoles: up to
