@@ -545,6 +545,11 @@ def dtype_code(dtype) -> int:
     raise TypeError(f"libmipme supports float32 and float64 tensors, got {dtype}")
 
 
+def complex_dtype(dtype):
+    """The complex dtype of the half-grid arrays that go with a real ``dtype``."""
+    return torch.complex64 if dtype == torch.float32 else torch.complex128
+
+
 def index_code(dtype) -> int:
     if dtype == torch.int64:
         return I64

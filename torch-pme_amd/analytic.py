@@ -137,10 +137,6 @@ class _Gather(torch.autograd.Function):
         return gu, gphi, None, None
 
 
-def _complex_dtype(dtype):
-    return torch.complex64 if dtype == torch.float32 else torch.complex128
-
-
 class _Convolve(torch.autograd.Function):
     """``irfftn(G * rfftn(mesh))``, both transforms un-normalised, ``G`` real on the half grid (``KSpaceFilter.forward``)."""
 
@@ -149,7 +145,7 @@ class _Convolve(torch.autograd.Function):
         mc = mesh.detach().contiguous()
         Gc = G.detach().to(mc.dtype).contiguous()
         n_ch = mc.shape[0]
-        hat = torch.empty((n_ch, geom.n_half), dtype=_complex_dtype(mc.dtype), device=mc.device)
+        hat = torch.empty((n_ch, geom.n_half), dtype=_lib.complex_dtype(mc.dtype), device=mc.device)
         work = torch.empty_like(hat)
         out = torch.empty_like(mc)
         plan = _lib.get_plan(mc.device, mc.dtype, geom.ns, n_ch)
@@ -174,7 +170,7 @@ class _Convolve(torch.autograd.Function):
 def _rfftn(mesh, geom):
     mc = mesh.detach().contiguous()
     n_ch = mc.shape[0]
-    hat = torch.empty((n_ch, geom.ns[0], geom.ns[1], geom.ns[2] // 2 + 1), dtype=_complex_dtype(mc.dtype), device=mc.device)
+    hat = torch.empty((n_ch, geom.ns[0], geom.ns[1], geom.ns[2] // 2 + 1), dtype=_lib.complex_dtype(mc.dtype), device=mc.device)
     plan = _lib.get_plan(mc.device, mc.dtype, geom.ns, n_ch)
     md = geom.desc(n_ch)
     with _lib.on_device(mc.device):

@@ -82,7 +82,7 @@ class _LiveStep:
         self.rec = torch.empty((N, 4), dtype=dtype, device=device)
         self.rec[:, :3] = positions.detach()
         self.rec[:, 3] = charges.detach()[:, 0]
-        cdtype = analytic._complex_dtype(dtype)
+        cdtype = _lib.complex_dtype(dtype)
         self.cell = cell.detach().to(dtype).contiguous()
         self.rho = torch.empty(geom.ns, dtype=dtype, device=device)
         self.phi = torch.empty(geom.ns, dtype=dtype, device=device)
@@ -448,7 +448,7 @@ class GraphedEnergyForces:
         def body():
             self.energy = self._eval(log=self.energy_log)
             self.forces = self.pos.grad
-            if self.energy_log is not None and not (self._tail is not None and self._tail.get("logged")):
+            if self.energy_log is not None and not (self._tail is not None and self._tail["logged"]):
                 self.energy_log.push(self.energy.reshape(1))  # (no gather tail in this step: one more node)
             if self._epilogue is not None:
                 self._epilogue(self)
@@ -623,7 +623,7 @@ class GraphedFrameBatch:
             raise ValueError(f"all frames must give the same mesh, got {[g.ns for g in geoms]}")
         self.ns = ns
         M, Mh = geoms[0].n_mesh, geoms[0].n_half
-        cdtype = analytic._complex_dtype(dtype)
+        cdtype = _lib.complex_dtype(dtype)
         self._G = torch.stack(Gs).contiguous()
         self._rho = torch.empty((F,) + ns, dtype=dtype, device=device)
         self._phi = torch.empty((F,) + ns, dtype=dtype, device=device)
@@ -938,7 +938,7 @@ class GraphedCombinedStep(_ExplicitListStep):
         if not self._plan.xfused:
             raise ValueError(f"GraphedCombinedStep needs a power-of-two mesh along x, the cell gives {geom.ns}")
         new = lambda *shape, dt=dtype: torch.empty(shape, dtype=dt, device=device)  # noqa: E731
-        cdtype = analytic._complex_dtype(dtype)
+        cdtype = _lib.complex_dtype(dtype)
         self.q = charges.detach().contiguous()
         self.cell = cell.detach().to(dtype).contiguous()
         self.pos = positions.detach().clone().contiguous()

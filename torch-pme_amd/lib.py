@@ -221,7 +221,7 @@ class KSpaceFilter:
         dtype, device = self._kfilter.dtype, self._kfilter.device
         mesh = mesh_values.detach().to(dtype).contiguous()
         Cn = mesh.shape[0]
-        cdtype = torch.complex64 if dtype == torch.float32 else torch.complex128
+        cdtype = _lib.complex_dtype(dtype)
         hat = torch.empty((Cn, self._geom.n_half), dtype=cdtype, device=device)
         work = torch.empty_like(hat)
         out = torch.empty_like(mesh)

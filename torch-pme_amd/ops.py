@@ -17,6 +17,7 @@ import ctypes as C
 import os
 import weakref
 from collections import OrderedDict
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -917,6 +918,663 @@ class _SkipGuard:
         return False
 
 
+# ---- the calculator's autograd node: names, route decisions, launch wrappers, steps, the node -------------------------------------
+#: the input slots of :class:`_PMEFunction`, in the order of ``forward``'s parameters: ``needs_input_grad``, the gradients that
+#: ``backward`` returns and the ``apply`` calls of :func:`pme_potential` are all written in these names
+_SLOTS = ("charges", "cell", "positions", "neighbor_distances", "neighbor_indices", "pair_mask", "geom", "G", "pot_desc",
+          "full_list", "slab_axis", "src_positions", "src_cell", "src", "lazy", "nan_flag", "atomic_pairs")
+_SLOT = {name: k for k, name in enumerate(_SLOTS)}
+
+
+def _by_slot(**values):
+    """One value per input slot of the node, ``None`` where not named."""
+    out = [None] * len(_SLOTS)
+    for name, value in values.items():
+        out[_SLOT[name]] = value
+    return tuple(out)
+
+
+class _Wanted(NamedTuple):
+    """``needs_input_grad`` of the node's differentiable slots."""
+
+    q: bool
+    cell: bool
+    pos: bool
+    dist: bool
+    src_pos: bool
+    src_cell: bool
+
+
+_WANTED_SLOTS = tuple(_SLOT[n] for n in ("charges", "cell", "positions", "neighbor_distances", "src_positions", "src_cell"))
+
+
+def _wanted(needs_input_grad) -> _Wanted:
+    return _Wanted(*[needs_input_grad[k] for k in _WANTED_SLOTS])
+
+
+class _Saved(NamedTuple):
+    """``ctx.saved_tensors`` of the node."""
+
+    q: torch.Tensor
+    pos: torch.Tensor
+    dist: torch.Tensor
+    pairs: torch.Tensor
+    mask: torch.Tensor | None
+    G: torch.Tensor | None
+    phi_mesh: torch.Tensor | None
+    rho_hat: torch.Tensor | None
+    rho_dc: torch.Tensor | None
+    phi_atoms: torch.Tensor | None
+    bins: torch.Tensor | None
+    out: torch.Tensor
+
+
+class _MeshRoute(NamedTuple):
+    """What the mesh part of the forward pass does (:func:`_mesh_route`)."""
+
+    field: bool  # speculative: the gather also forms the mesh force per unit gE q_a (the backward's energy mode)
+    records_out: bool  # the binning pass emits the (position, charge) records of the fused pair kernel
+    cosched: bool  # the spread launch carries the row workgroups of the fused distance + pair kernel (mipme_sr_job_t)
+    want_ent32: bool  # ask the topology for the 4-byte entry stream (device work, possibly a bet) ...
+    ent32: bool  # ... and the co-scheduled launch reads it (shift_format 2)
+    tail_q: bool  # the gather tail writes dE/dq
+    tail_cell: bool  # the gather tail writes dE/dcell
+    tail_ok: bool  # energy reduction + force assembly inside the gather launch
+    slab_in_tail: bool  # the slab term rides in the gather tail (else: in launches of its own behind the step)
+    pair_partials: bool  # the pair part's cell sums from the generic pair body, which then runs on its own
+    cell_partials: bool  # the x stage of the fused convolution leaves the k-grid sums of the cell gradient behind
+    rho_keep: bool  # the x stage keeps rfftn(rho) (one channel)
+    rho_hat: bool  # rfftn(rho) from the 3-D plans (no fused convolution)
+    keep_rho_mesh: bool  # the backward pass may read the charge mesh again
+    symmetric: bool  # V is a symmetric bilinear form of the charges: dE/dq = 2 V
+
+
+def _mesh_route(*, energy_fast_path, coschedule, tail_fusion, xfused, request_q, request_cell, want_q, want_cell, want_pos,
+                want_dist, want_src_cell, Cn, N, p_eff, smeared, no_exclusion, full_list, lazy, slab, masked, fused, force,
+                shift_fmt, fmt_flags, bins, same_positions, src_cell, write_dist, has_ent32) -> _MeshRoute:
+    """The route of the forward's mesh part as a function of facts alone: no tensor, no library call, no module global.
+
+    Flags (``ops.ENERGY_FAST_PATH`` ...; ``xfused``: the flag AND the plan's ability) and ``request_*`` (``TAIL_REQUEST``) as the
+    forward read them; ``want_*``: ``needs_input_grad``; ``smeared`` / ``no_exclusion``: ``pot.smearing > 0`` /
+    ``pot.exclusion_radius <= 0``; ``fused`` .. ``write_dist``: the pair plan (``force``: it carries speculative force sums,
+    ``shift_fmt``: its shift format with the topology's ``fmt_flags`` OR-ed in); ``bins``: the mesh has bricks; ``has_ent32``:
+    what ``topo.compact_entries`` gave -- ask with ``False`` first, and again once ``want_ent32`` came back true and the
+    stream exists."""
+    rho_hat = not xfused
+    # (a slab term: only the gather tail folds it into the field -- 1/r, one channel)
+    field = bool(energy_fast_path and bins and Cn == 1 and want_pos and (not slab or p_eff == 1))
+    records_out = bool(fused and bins and Cn == 1 and same_positions)
+    cosched = bool(coschedule and records_out and not masked and (shift_fmt & 0xFF) == 1 and N > 0)
+    # the 4-byte stream is read by the co-scheduled kernel only (mipme.h, shift_format 2): when the library will co-schedule --
+    # force sums wanted, 1/r or 1/r^6 with a smearing and no exclusion radius
+    want_ent32 = bool(cosched and force and p_eff in (1, 6) and smeared and no_exclusion)
+    ent32 = want_ent32 and bool(has_ent32)
+    symmetric = (not full_list) or bool(fmt_flags)
+    tail_q = bool(want_q or request_q) and symmetric
+    tail_cell = bool((want_cell or want_src_cell or request_cell) and ent32 and not write_dist and src_cell)
+    tail_ok = bool(
+        tail_fusion and cosched and field and force and energy_fast_path and not want_dist and (tail_q or not want_q)
+        and (tail_cell or not (want_cell or want_src_cell)) and not rho_hat and p_eff in (1, 6) and no_exclusion
+        and (not lazy or tail_q or tail_cell))  # (lazy distances: only for what the tail adds to this node)
+    if not tail_ok:
+        tail_q = tail_cell = False
+    slab_in_tail = bool(slab and tail_ok)
+    if slab and not tail_ok:
+        field = False  # (it would lack the term)
+    pair_partials = cell_partials = False
+    if not tail_cell:
+        if force and src_cell and want_src_cell:
+            pair_partials, cosched, ent32 = True, False, False  # (no co-scheduled launch with the pair part's cell sums)
+        cell_partials = bool(want_cell and not rho_hat and Cn > 1)
+    rho_keep = bool(want_cell and not rho_hat and Cn == 1)
+    keep_rho_mesh = (cell_partials or tail_cell) and not rho_keep and not rho_hat
+    return _MeshRoute(field, records_out, cosched, want_ent32, ent32, tail_q, tail_cell, tail_ok, slab_in_tail, pair_partials,
+                      cell_partials, rho_keep, rho_hat, keep_rho_mesh, symmetric)
+
+
+class _BackwardPlan(NamedTuple):
+    """What the backward pass launches (:func:`_backward_plan`)."""
+
+    do_kspace: bool  # the mesh part has a gradient to form
+    r2c: bool  # general upstream gradient after a forward that kept the charge mesh instead of rfftn(rho): transform it now
+    energy_q: bool  # dL/dq = gE V (half list, energy mode): no kernel
+    mesh: str | None  # "energy": mipme_kspace_backward with grad_scale; "general": the full adjoint; None: no call
+    kb_q: bool  # energy mode: the C call forms the mesh part of dL/dq
+    from_field: bool  # energy mode: with the field at hand the C call only finalises the cell gradient (no gradient gather)
+    kb_pos: bool  # energy mode: the C call runs the gradient gather
+    fused_cell: bool  # general mode: the cell sums from the kept rfftn(rho) inside the fused convolution (G_deriv)
+    psi_hat: bool  # general mode: the adjoint's k-space array is needed
+    zero_q: bool  # no mesh, pair part still to come: dL/dq starts from zeros
+    atomic_q: bool  # the per-pair kernel also scatters dL/dq (no transposed list)
+    pair_stream: bool  # mipme_rspace_backward runs (dL/dd wanted, or atomic_q)
+    field_left: bool  # the forward's mesh field still serves the forces after the mesh call
+    sr_done: bool  # the pair part's position / cell gradient ends in the forward's per-atom sums (finalize)
+    mesh_done: bool  # ... and so does the mesh part's position gradient
+    one_finalize: bool  # both differentiate the same positions tensor: one kernel, one gradient
+    sr_adjoint: bool  # the general adjoint of the fused pair kernel runs
+    pair_q: str | None  # the pair part of dL/dq: "energy", "fused", "tabulated", "rows" or None
+
+
+def _backward_plan(*, has_geom, scaled, energy, need_q, need_cell, need_pos, need_dist, need_src_pos, need_src_cell, full_list,
+                   Cn, has_rho_hat, has_field, rho_kept, xfused, has_topo, has_fused, has_force, has_partials, has_tab,
+                   same_positions, lazy) -> _BackwardPlan:
+    """The backward pass as a function of facts alone, once the energy mode and the tail's share are known: ``scaled`` -- the
+    upstream gradient is gE * charges (enough for the pair part), ``energy`` -- and the mesh part may use it too; ``need_*``:
+    what is still to be formed; ``has_*``: what the forward left behind (``has_force`` / ``has_partials``: of ``fused``)."""
+    do_kspace = bool(has_geom and (need_q or need_cell or need_pos))
+    r2c = bool(need_cell and not has_rho_hat and not energy and has_geom)
+    energy_q = bool(need_q and energy and not full_list)
+    field = bool(has_field and energy)
+    mesh = None
+    kb_q = from_field = kb_pos = fused_cell = psi_hat = zero_q = False
+    if do_kspace and energy:
+        kb_q = bool(need_q and not energy_q)
+        from_field = field and not kb_q
+        kb_pos = bool((need_pos or need_cell) and not from_field)
+        if kb_pos or kb_q or need_cell:
+            mesh = "energy"
+            if need_cell and not from_field:
+                field = False  # the gradient gather has produced the mesh forces
+    elif do_kspace:
+        mesh = "general"
+        fused_cell = bool(need_cell and rho_kept and xfused and Cn == 1)
+        psi_hat = bool((need_cell and not fused_cell) or not xfused)
+    elif need_q and not energy_q:
+        zero_q = True
+    atomic_q = bool(need_q and not has_topo and not energy_q)
+    sr_wanted = bool(need_src_pos or need_src_cell)
+    sr_done = bool(sr_wanted and scaled and has_force and (has_partials or not need_src_cell))
+    mesh_done = bool(need_pos and field)
+    pair_q = None
+    if energy_q:
+        pair_q = "energy"
+    elif need_q and has_fused:
+        pair_q = "fused"
+    elif need_q and has_topo:
+        pair_q = "tabulated" if has_tab else "rows"
+    return _BackwardPlan(do_kspace, r2c, energy_q, mesh, kb_q, from_field, kb_pos, fused_cell, psi_hat, zero_q, atomic_q,
+                         bool(need_dist or atomic_q), field, sr_done, mesh_done,
+                         bool(sr_done and mesh_done and same_positions and need_src_pos and not lazy),
+                         sr_wanted and not sr_done, pair_q)
+
+
+def _launch_rows_fused(label, st, N, topo, fused, mask, q, pot_desc, full_list, *, src=None, grad_out=None, transpose=0,
+                       accumulate=0, records_ready=0, out=None, force=None, partials=None, grad_cell=None, dist_out=None):
+    """``mipme_sr_rows_fused``: the potential pass (``src`` = charges), its adjoint w.r.t. positions and cell (``grad_out``) and
+    the transposed charge pass (``src`` = upstream gradient, ``transpose``)."""
+    _call(label, _lib.load().mipme_sr_rows_fused, st, _lib.dtype_code(q.dtype), N, topo.row_ptr.data_ptr(),
+          fused["ent_sh"].data_ptr(), topo.entries.data_ptr(), _lib.ptr(mask), fused["pos"].data_ptr(), _lib.ptr(fused["cell"]),
+          q.data_ptr(), _lib.ptr(src), _lib.ptr(grad_out), transpose, int(full_list), C.byref(pot_desc), accumulate, fused["fmt"],
+          fused["records"].data_ptr(), records_ready, _lib.ptr(out), _lib.ptr(force), _lib.ptr(partials), _lib.ptr(grad_cell),
+          _lib.ptr(dist_out))
+
+
+def _launch_rspace_backward(ctx, s, g, sr_scale, grad_dist, grad_q):
+    """``mipme_rspace_backward``: dL/dd as a per-pair stream (no scatter); in "atomic" mode the same kernel also scatters dL/dq.
+    Used by the backward pass and, later, by a :class:`LazyPairGradient` that somebody looks at."""
+    pl = s.pairs if ctx.topo is None else ctx.topo.pairs32
+    device = s.pos.device
+    with _lib.on_device(device):
+        _call("rspace_backward", _lib.load().mipme_rspace_backward, _lib.current_stream(device), _lib.dtype_code(s.pos.dtype),
+              _lib.index_code(pl.dtype), s.pairs.shape[0], s.q.shape[0], s.q.shape[1], pl.data_ptr(), s.dist.data_ptr(),
+              s.q.data_ptr(), _lib.ptr(s.mask), int(ctx.full_list), C.byref(ctx.pot_desc), g.data_ptr(), _lib.ptr(sr_scale),
+              _lib.ptr(grad_dist), _lib.ptr(grad_q))
+
+
+def _launch_finalize(st, q, scale, full_list, force, field, partials, out_pos, out_cell):
+    """``mipme_sr_rows_finalize``: grad_positions[a] = gE q_a (f force_a + field_a), grad_cell = f gE sum(partials)."""
+    _call("forces_finalize", _lib.load().mipme_sr_rows_finalize, st, _lib.dtype_code(q.dtype), q.shape[0], _lib.ptr(force),
+          _lib.ptr(field), q.data_ptr(), scale.data_ptr(), int(full_list), _lib.ptr(partials), _lib.ptr(out_pos),
+          _lib.ptr(out_cell))
+
+
+def _kspace_backward_args(ctx, s, plan, md, st, g, **fields):
+    """``mipme_kspace_backward_args_t`` with what both of its modes pass; ``fields``: the rest."""
+    return _lib.KspaceBackwardArgs(
+        plan=plan.handle, stream=st, dtype=_lib.dtype_code(s.pos.dtype), mesh=C.pointer(md), pot=C.pointer(ctx.pot_desc),
+        n_atoms=s.q.shape[0], positions=s.pos.data_ptr(), charges=s.q.data_ptr(), grad_out=g.data_ptr(), G=s.G.data_ptr(),
+        phi_mesh=s.phi_mesh.data_ptr(), rho_dc=_lib.ptr(s.rho_dc), atom_bins=_lib.ptr(s.bins), **fields)
+
+
+def _distances_written(src):
+    """The fused pair kernel has stored the values of a deferred distance tensor.  Rows adopted on a bet: if it is lost, the
+    rerun (or ``materialize()``) writes the values again."""
+    src.pending = False
+    if _BETS:
+        _ON_LOST.append(lambda src=src: setattr(src, "pending", True))
+
+
+# ---- forward, in the order of the device work ----
+def _pair_plan(want, energy_fast_path, q, pairs, mask, neighbor_distances, geom, pot_desc, full_list, src_positions, src_cell,
+               src, atomic_pairs):
+    """``(topo, full_list, fused, write_dist, tab)``: the transposed list, the buffers of the fused distance + pair kernel (or
+    None), whether that kernel stores the distances, and the table of a constant distance tensor (or None)."""
+    N, Cn = q.shape
+    P = pairs.shape[0]
+    device, dtype = q.device, q.dtype
+    # atomic_pairs: one pass over the list with float atomics -- for lists that are new every call (the flattened pair
+    # list of a padded batch), where building the transposed list would cost more than it saves
+    topo = get_topology(pairs, N) if (PAIR_MODE == "rows" and not atomic_pairs) else None
+    if topo is not None and topo.fmt_flags:
+        full_list = False  # rows of a NeighborStream hold every neighbour once: a half list whatever the calculator says
+    fused = None
+    if src is not None:
+        if isinstance(topo, PairTopology) and src.shifts is not None:
+            topo.adopt_shifts(src.shifts, src.shifts_key)
+        ent_sh, shift_fmt = topo.entries_with_shifts(src.shifts, src.shifts_key, table=mask is None)
+        if ent_sh is not None:
+            fused = dict(
+                ent_sh=ent_sh, fmt=shift_fmt | topo.fmt_flags, pos=src_positions.detach().contiguous(),
+                cell=None if src_cell is None else src_cell.detach().contiguous(), force=None, partials=None,
+                records=torch.empty((N, 4), dtype=dtype, device=device), records_ready=False,
+            )
+            # speculative force sums: if the backward turns out to be in energy mode they ARE the SR forces (the matching
+            # cell sums: decided by the mesh route, once it is known whether the gather tail covers the cell gradient)
+            if energy_fast_path and want.src_pos:
+                fused["force"] = torch.empty((N, 3), dtype=dtype, device=device)
+    # deferred distances (``pair_distances(..., deferred=True)``): the fused kernel writes them as a by-product
+    write_dist = False
+    if src is not None and src.pending:
+        if src.virtual and fused is not None:
+            pass  # nobody reads the values: the fused kernel forms the distances in registers and drops them
+        else:
+            write_dist = fused is not None and mask is None and P > 0 and topo.sorted_by_first
+            if not write_dist:
+                src.materialize()
+    if geom is None and fused is not None and fused["force"] is not None and src_cell is not None and want.src_cell:
+        fused["partials"] = torch.empty((_lib.load().mipme_rows_partials_size(N),), dtype=torch.float64, device=device)
+    # distances that are a plain tensor this list has been evaluated with before: the tabulated pair sum
+    tab = None
+    if (TABULATE and fused is None and topo is not None and Cn == 1 and P > 0 and not want.dist
+            and type(neighbor_distances) is torch.Tensor and neighbor_distances.is_contiguous()):
+        tab = topo.tabulated(neighbor_distances, mask, pot_desc, full_list)  # (keyed on the caller's tensor object)
+    return topo, full_list, fused, write_dist, tab
+
+
+def _pair_forward(accumulate, q, dist, pairs, mask, out, pot_desc, full_list, topo, fused, write_dist, tab, src):
+    """The pair sum in a launch of its own: fused distance + pair kernel, tabulated, rows, or atomics."""
+    lib = _lib.load()
+    N, Cn = q.shape
+    st, dt = _lib.current_stream(q.device), _lib.dtype_code(q.dtype)
+    if fused is not None:
+        _launch_rows_fused("rspace_forward", st, N, topo, fused, mask, q, pot_desc, full_list, src=q, accumulate=accumulate,
+                           records_ready=int(fused["records_ready"]), out=out, force=fused["force"],
+                           partials=fused["partials"], dist_out=dist if write_dist else None)
+        if write_dist:
+            _distances_written(src)
+    elif tab is not None:  # constant distances: v_SR(d) per row entry is already there (PairTopology.tabulated)
+        _call("rspace_forward", lib.mipme_rspace_rows_tabulated, st, dt, N, topo.row_ptr.data_ptr(), tab[0].data_ptr(),
+              q.data_ptr(), 0, int(full_list), accumulate, out.data_ptr())
+    elif topo is not None:
+        _call("rspace_forward", lib.mipme_rspace_rows, st, dt, N, Cn, topo.row_ptr.data_ptr(), topo.entries.data_ptr(),
+              dist.data_ptr(), q.data_ptr(), _lib.ptr(mask), 0, int(full_list), C.byref(pot_desc), accumulate, out.data_ptr())
+    else:
+        _call("rspace_forward", lib.mipme_rspace_forward, st, dt, _lib.index_code(pairs.dtype), pairs.shape[0], N, Cn,
+              pairs.data_ptr(), dist.data_ptr(), q.data_ptr(), _lib.ptr(mask), int(full_list), C.byref(pot_desc), accumulate,
+              out.data_ptr())
+
+
+#: what the forward's argument struct reads where there is no gather tail
+_NO_TAIL = dict(energy=None, grad=None, seed=None, grad_q=None, grad_cell=None, aux_seed=None, G_deriv=None, cell_work=None,
+                log=None, logged=False)
+
+
+def _gather_tail(route, N, dtype, device, aux_seed, geom, pot_desc, plan, md):
+    """The buffers of the gather's tail (``mipme_kspace_forward_args_t.out_energy`` ...): E and the assembled position gradient,
+    speculative like the force sums -- if the caller reduces with ``weighted_sum(V, charges)`` (see ``energy_direct``) neither
+    the energy reduction nor the force assembly is launched --, and on request the rest of the contract (``out_grad_charges``:
+    dE/dq = 2 V for a half list; ``out_grad_cell``: from partial sums of the same launches + one single-workgroup launch), which
+    also serve the energy mode of this node's own backward (lazy distances, plain tensor reductions)."""
+    def scalar_of_ours(t):
+        return t if t is not None and t.dtype == dtype and t.device == device and t.numel() == 1 else None
+
+    log = TAIL_LOG if TAIL_LOG is not None and TAIL_LOG.n_frames == 1 and TAIL_LOG.values.device == device else None
+    tail = dict(energy=torch.empty((), dtype=dtype, device=device), grad=torch.empty((N, 3), dtype=dtype, device=device),
+                seed=scalar_of_ours(SEED_PROMISE), grad_q=None, grad_cell=None, aux_seed=scalar_of_ours(aux_seed), G_deriv=None,
+                cell_work=None, log=log, logged=log is not None)
+    if route.tail_q:
+        tail["grad_q"] = torch.empty((N, 1), dtype=dtype, device=device)
+    if route.tail_cell:
+        tail["grad_cell"] = torch.empty((27,), dtype=dtype, device=device)
+        tail["G_deriv"] = filter_derivative(geom, pot_desc, dtype, device)
+        tail["cell_work"] = torch.empty((_lib.load().mipme_cell_tail_work(plan.handle, C.byref(md), N),), dtype=torch.float64,
+                                        device=device)
+    return tail
+
+
+def _mesh_forward(want, flags, q, pos, dist, mask, out, geom, G, pot_desc, full_list, slab_axis, lazy, nan_flag, topo, fused,
+                  write_dist, same_positions, src):
+    """The mesh part -- binning, spread (+ co-scheduled pair sum), convolution, gather (+ tail) -- added to ``out``, and the
+    slab term where the tail does not carry it.  Returns ``(field, tail, saved, pair_sum_done)``."""
+    lib = _lib.load()
+    energy_fast_path, coschedule, tail_fusion, xfused_flag, mesh_mode = flags
+    device, dtype = q.device, q.dtype
+    N, Cn = q.shape
+    st, dt = _lib.current_stream(device), _lib.dtype_code(dtype)
+    md = geom.desc(Cn)
+    plan = _lib.get_plan(device, dtype, geom.ns, Cn, geom.plan_store)
+    bins = None
+    if mesh_mode == "bricks":
+        nbytes = lib.mipme_atom_bins_bytes(C.byref(md), N, dt)
+        if nbytes > 0:
+            bins = torch.empty((nbytes,), dtype=torch.uint8, device=device)
+    request_q, request_cell, aux_seed = TAIL_REQUEST
+    facts = dict(
+        energy_fast_path=energy_fast_path, coschedule=coschedule, tail_fusion=tail_fusion, xfused=plan.xfused and xfused_flag,
+        request_q=request_q, request_cell=request_cell, want_q=want.q, want_cell=want.cell, want_pos=want.pos,
+        want_dist=want.dist, want_src_cell=want.src_cell, Cn=Cn, N=N,
+        p_eff=1 if pot_desc.kind == _lib.COULOMB else pot_desc.exponent, smeared=pot_desc.smearing > 0,
+        no_exclusion=pot_desc.exclusion_radius <= 0, full_list=full_list, lazy=lazy, slab=slab_axis is not None,
+        masked=mask is not None, fused=fused is not None, force=fused is not None and fused["force"] is not None,
+        shift_fmt=0 if fused is None else fused["fmt"], fmt_flags=0 if topo is None else topo.fmt_flags, bins=bins is not None,
+        same_positions=same_positions, src_cell=fused is not None and fused["cell"] is not None, write_dist=write_dist)
+    route = _mesh_route(has_ent32=False, **facts)
+    ent32 = None
+    if route.want_ent32:  # (device work, possibly a bet: here in the order of the queue, between the two looks at the route)
+        ent32 = topo.compact_entries(src.shifts, src.shifts_key)
+        if ent32 is not None:
+            route = _mesh_route(has_ent32=True, **facts)
+    cdtype = _lib.complex_dtype(dtype)
+    empty = lambda shape, dtype=dtype: torch.empty(shape, dtype=dtype, device=device)  # noqa: E731
+    rho_mesh, phi_mesh = empty((Cn,) + geom.ns), empty((Cn,) + geom.ns)
+    # rfftn(rho) itself is only needed by the cell gradient; without it the convolution runs fused (see mipme.h)
+    rho_hat = empty((Cn, geom.n_half), cdtype) if route.rho_hat else None
+    hat_work, dc = empty((Cn, geom.n_half), cdtype), empty((Cn,))
+    phi_atoms = empty((N, Cn)) if want.cell else None
+    field = empty((N, 3)) if route.field else None
+    records_out = fused["records"] if route.records_out else None
+    if route.pair_partials:
+        fused["partials"] = empty((lib.mipme_rows_partials_size(N),), torch.float64)
+    # speculative, like the force sums: the k-grid sums of the cell gradient for the energy mode (the backward then needs neither
+    # rho^ nor the 3-D plans; a general upstream gradient recomputes rho^ from the saved charge mesh) ...
+    cell_partials = empty((lib.mipme_cellgrad_partials_size(C.byref(md), N),), torch.float64) if route.cell_partials else None
+    # ... one channel: rfftn(rho) itself (a 1 MB store at 64^3) -- the backward pass forms the k-grid sums from it in either
+    # mode, the general one with the fused convolution (mipme.h, G_deriv)
+    rho_keep = empty((Cn, geom.n_half), cdtype) if route.rho_keep else None
+    job = None
+    if route.cosched:
+        job = _lib.SrJob(
+            n_atoms=N, row_ptr=topo.row_ptr.data_ptr(), entries_shift=(ent32 if route.ent32 else fused["ent_sh"]).data_ptr(),
+            entries=topo.entries.data_ptr(), positions=fused["pos"].data_ptr(), cell=_lib.ptr(fused["cell"]),
+            charges=q.data_ptr(), pot=C.pointer(pot_desc), full_list=int(full_list),
+            shift_format=(2 | topo.fmt_flags) if route.ent32 else fused["fmt"], records=records_out.data_ptr(),
+            out=out.data_ptr(), force=_lib.ptr(fused["force"]), dist_out=dist.data_ptr() if write_dist else None)
+    tail = _gather_tail(route, N, dtype, device, aux_seed, geom, pot_desc, plan, md) if route.tail_ok else None
+    t = _NO_TAIL if tail is None else tail
+    log = t["log"]
+    args = _lib.KspaceForwardArgs(
+        plan=plan.handle, stream=st, dtype=dt, accumulate_out=1 if job is not None else 0, mesh=C.pointer(md),
+        pot=C.pointer(pot_desc), n_atoms=N, positions=pos.data_ptr(), charges=q.data_ptr(), G=G.data_ptr(),
+        rho_mesh=rho_mesh.data_ptr(), rho_hat=_lib.ptr(rho_hat), hat_work=hat_work.data_ptr(), phi_mesh=phi_mesh.data_ptr(),
+        dc=dc.data_ptr(), out_lr=out.data_ptr(), out_phi=_lib.ptr(phi_atoms), atom_bins=_lib.ptr(bins), gather_wait_event=None,
+        out_field=_lib.ptr(field), out_records=_lib.ptr(records_out), sr_job=C.pointer(job) if job is not None else None,
+        out_cell_partials=_lib.ptr(cell_partials), out_energy=_lib.ptr(t["energy"]), out_grad_positions=_lib.ptr(t["grad"]),
+        grad_seed=_lib.ptr(t["seed"]), nan_flag=nan_flag, out_grad_charges=_lib.ptr(t["grad_q"]),
+        out_grad_cell=_lib.ptr(t["grad_cell"]), G_deriv=_lib.ptr(t["G_deriv"]), cell_work=_lib.ptr(t["cell_work"]),
+        aux_seed=_lib.ptr(t["aux_seed"]), out_rho_hat=_lib.ptr(rho_keep),
+        # the charge mesh is only read again (fft_r2c in the backward pass) if rfftn(rho) was not kept
+        flags=0 if route.keep_rho_mesh else _lib.FWD_RHO_MESH_UNUSED,
+        energy_log=None if log is None else log.values.data_ptr(),
+        energy_log_cursor=None if log is None else log.cursor.data_ptr(),
+        energy_log_capacity=0 if log is None else log.capacity, slab=slab_axis + 1 if route.slab_in_tail else 0)
+    _call("kspace_forward", lib.mipme_kspace_forward, C.byref(args))
+    if records_out is not None:
+        fused["records_ready"] = True
+    if job is not None and write_dist:
+        _distances_written(src)
+    if slab_axis is not None and not route.slab_in_tail:
+        moments = empty((6 * Cn,), torch.float64)
+        _call("slab_forward", lib.mipme_slab_forward, st, dt, slab_axis, C.byref(md), pot_desc.prefactor, N, pos.data_ptr(),
+              q.data_ptr(), moments.data_ptr(), out.data_ptr())
+    saved = dict(phi_mesh=phi_mesh, rho_hat=(rho_hat if rho_keep is None else rho_keep) if want.cell else None, rho_dc=dc,
+                 phi_atoms=phi_atoms, bins=bins, rho_mesh=rho_mesh if route.keep_rho_mesh else None,
+                 cell_partials=cell_partials, rho_kept=rho_keep is not None, plan_xfused=plan.xfused)
+    return field, tail, saved, job is not None
+
+
+#: ``saved`` of a node without a mesh part
+_NO_MESH = dict(phi_mesh=None, rho_hat=None, rho_dc=None, phi_atoms=None, bins=None, rho_mesh=None, cell_partials=None,
+                rho_kept=False, plan_xfused=False)
+
+
+def _fill_ctx(ctx, want, energy_fast_path, tensors, saved, field, tail, tab, topo, fused, geom, pot_desc, full_list, slab_axis,
+              lazy, same_positions, src_cell_is_cell):
+    """Everything the backward pass, ``_EnergyDirectSum``, the graphed steps and the tests read from the node."""
+    q, pos, dist, pairs, mask, G, out = tensors
+    ctx.save_for_backward(q, pos, dist, pairs, mask, G, saved["phi_mesh"], saved["rho_hat"], saved["rho_dc"],
+                          saved["phi_atoms"], saved["bins"], out)
+    ctx.rho_mesh, ctx.cell_partials, ctx.rho_kept = saved["rho_mesh"], saved["cell_partials"], saved["rho_kept"]
+    ctx.plan_xfused = saved["plan_xfused"]  # (the plan's ability; the backward fetches the plan only where it launches)
+    ctx.tab = tab
+    ctx.field = field
+    ctx.tail = tail  # {energy, grad, seed, ...} written by the gather's tail, or None
+    ctx.same_positions = same_positions
+    #: the pair part's gradient leaves through the neighbor_distances slot as a LazyPairGradient (see pme_potential)
+    ctx.lazy = bool(lazy) and fused is not None
+    ctx.geom, ctx.pot_desc, ctx.full_list, ctx.slab_axis = geom, pot_desc, full_list, slab_axis
+    #: the gather tail of the forward carries the slab term: potentials, energy, field and the tail's gradients include it
+    ctx.slab_in_tail = slab_in_tail = bool(geom is not None and slab_axis is not None and tail is not None)
+    ctx.topo = topo
+    ctx.fused = fused  # plain tensors made here, none of them an input or output of this node
+    # E = weighted_sum(out, charges) can be differentiated without this node (see _EnergyDirectSum) when its gradient is
+    # gE q_a (f F_a + field_a) with both per-atom sums already formed above and nothing else asks for a gradient
+    want_cell = want.cell or want.src_cell
+    covered = tail is not None and (tail["grad_q"] is not None or not want.q) and (
+        tail["grad_cell"] is not None or not want_cell)
+    ctx.energy_direct = bool(
+        energy_fast_path and q.shape[1] == 1 and fused is not None and fused["force"] is not None and same_positions
+        and (covered or not (want.q or want_cell)) and not want.dist and (slab_axis is None or slab_in_tail)
+        and (geom is None or field is not None) and not lazy
+    )
+    ctx.src_cell_is_cell = src_cell_is_cell
+
+
+# ---- backward, in the order of the device work ----
+def _energy_mode(ctx, s, grad_out, g, st, guard, need, do_kspace):
+    """``(sr_scale, select)``.  Energy mode: if the upstream gradient was produced by ``weighted_sum(V, charges)`` with OUR
+    charges it is exactly gE * charges (``sr_scale`` = gE, a device scalar).  Then (a) the adjoint mesh is a multiple of the
+    forward one (no second spread / FFT), (b) the forces are gE q_a times the per-atom sums the forward pass already formed
+    (``field`` from the gather, ``force`` from the fused pair kernel), (c) for a half list dL/dq = gE * V (V is a symmetric
+    bilinear form).  ``select``: the verdict stays on the device and ``mipme_energy_select`` acts on it."""
+    lib = _lib.load()
+    q, fused, topo = s.q, ctx.fused, ctx.topo
+    N, Cn = q.shape
+    device, dtype = q.device, q.dtype
+    need_q, need_cell, need_pos, need_dist, need_src_pos, need_src_cell = need
+    tag = getattr(grad_out, "_mipme_scaled", None) if ENERGY_FAST_PATH else None
+    if tag is not None and tag[0] == q.data_ptr() and tag[1] == tuple(q.shape) and tag[2] == q._version:
+        return tag[3], None  # enough for the pair part
+    if not (ENERGY_FAST_PATH and ENERGY_DETECT and tag is None and N > 0 and (fused is not None or do_kspace)
+            and not (N > 1 and grad_out.stride(0) == 0)  # an expanded scalar (``V.sum().backward()``): not gE * charges
+            and not torch.cuda.is_current_stream_capturing()):
+        return None, None
+    # no tag: the caller reduced with plain tensor ops, ``(charges * V).sum()`` (README.rst:112-114) -- ask the
+    # device whether the gradient is a multiple of the charges (one small kernel + a 2-value read; the general
+    # adjoint it saves is a second spread, an FFT pair and a gradient gather).  Not during graph capture.
+    res = torch.empty((2,), dtype=dtype, device=device)
+    dt = _lib.dtype_code(dtype)
+    # (rows of a NeighborStream: the general pair kernel reads 8-byte entries, which would have to be expanded from
+    # the stream's words on every call -- those keep the host poll)
+    on_device = (DEVICE_SELECT and N >= DEVICE_SELECT_MIN_ATOMS and Cn == 1 and fused is not None
+                 and fused["force"] is not None
+                 and not (topo is not None and topo.fmt_flags)
+                 and ctx.slab_axis is None and not (need_q or need_cell or need_dist or need_src_cell)
+                 and (ctx.geom is None or ctx.field is not None) and (need_pos or need_src_pos))
+    if on_device:
+        # only position gradients are wanted: run the GENERAL adjoint with every kernel told to return at once when the
+        # verdict is a match, then let one kernel replace its outputs by the energy-mode expressions in that case -- no host
+        # read, the host keeps running ahead of the GPU
+        select = dict(res=res, flag=torch.empty((1,), dtype=torch.int32, device=device))
+        _scaled_match(lib, st, dt, N * Cn, g, q, res, select["flag"].data_ptr())
+        lib.mipme_set_skip_flag(select["flag"].data_ptr())
+        guard.armed = True
+        return None, select
+    flag, flag_np = _match_flag(device)
+    flag_np[0] = -1
+    _scaled_match(lib, st, dt, N * Cn, g, q, res, flag.data_ptr())
+    # the kernel also writes its verdict to pinned host memory: poll that word instead of a device-to-host copy
+    # (hipMemcpy of 4 bytes costs 20-30 us on this stack; the poll ends a few us after the kernel does)
+    spins = 0
+    while flag_np[0] == -1:
+        spins += 1
+        if spins > 2_000_000:  # never seen; a stream synchronisation is the fallback
+            SPIN_TIMEOUTS["match"] += 1
+            torch.cuda.current_stream(device).synchronize()
+            break
+    return (res[:1] if flag_np[0] == 1 else None), None
+
+
+def _tail_gradients(tail, gscale, sr_scale, need_q, need_cell, need_src_cell):
+    """``(grad_q, grad_cell, grad_src_cell)`` that the forward's gather tail already holds for exactly this upstream gradient
+    (mipme.h, out_grad_charges / out_grad_cell): dE/dq = 2 V and dE/dcell (mesh part, pair part) per unit of the tail's seed."""
+    grad_q = grad_cell = grad_src_cell = None
+    if gscale is not None and tail is not None and (tail["grad_q"] is not None or tail["grad_cell"] is not None):
+        base = tail["aux_seed"] if tail["aux_seed"] is not None else tail["seed"]
+        tscale = sr_scale if base is None else sr_scale / base
+        if need_q and tail["grad_q"] is not None:
+            # (the tail holds the TOTAL dE/dq = 2 V of E = sum q V; through this node flows the half that comes from
+            # V's dependence on the charges, the other half is the reduction's own)
+            grad_q = tail["grad_q"] * (0.5 * tscale)
+        if tail["grad_cell"] is not None and (need_cell or need_src_cell):
+            gc = tail["grad_cell"] * tscale
+            if need_cell:
+                grad_cell = gc[0:9].view(3, 3)
+            if need_src_cell:
+                grad_src_cell = gc[9:18].view(3, 3)
+    return grad_q, grad_cell, grad_src_cell
+
+
+def _mesh_adjoint_energy(ctx, s, p, plan, st, g, gscale, rho_hat, need_pos, need_cell):
+    """Energy mode: ``(grad_pos, grad_q, grad_cell)`` of the mesh part from the forward's meshes -- no second spread / FFTs."""
+    lib = _lib.load()
+    N, Cn = s.q.shape
+    empty = lambda shape, dtype=s.q.dtype: torch.empty(shape, dtype=dtype, device=s.q.device)  # noqa: E731
+    md = ctx.geom.desc(Cn)
+    grad_pos = empty((N, 3)) if p.kb_pos else None
+    grad_q = empty((N, Cn)) if p.kb_q else None
+    grad_cell = partials = None
+    kgrid_ready = 0
+    if need_cell:  # the k-grid sums come from rho^ alone ...
+        grad_cell = empty((3, 3))
+        if ctx.cell_partials is not None:  # ... and the forward's fused convolution has already formed them
+            partials, kgrid_ready = ctx.cell_partials, plan.kgrid_blocks
+        else:
+            partials = empty((lib.mipme_cellgrad_partials_size(C.byref(md), N),), torch.float64)
+    args = _kspace_backward_args(
+        ctx, s, plan, md, st, g, rho_hat=_lib.ptr(rho_hat) if need_cell else None,
+        phi_atoms=_lib.ptr(s.phi_atoms) if need_cell else None, partials=_lib.ptr(partials), grad_positions=_lib.ptr(grad_pos),
+        grad_charges=_lib.ptr(grad_q), grad_cell=_lib.ptr(grad_cell), grad_scale=gscale.data_ptr(),
+        mesh_field=_lib.ptr(ctx.field) if p.from_field else None, kgrid_blocks_ready=kgrid_ready)
+    _call("kspace_backward", lib.mipme_kspace_backward, C.byref(args))
+    return (grad_pos if need_pos else None), grad_q, grad_cell
+
+
+def _mesh_adjoint_general(ctx, s, p, plan, st, g, rho_hat, need_q, need_cell, need_pos):
+    """General upstream gradient: ``(grad_pos, grad_q, grad_cell)`` of the mesh part from a second spread + convolution +
+    gradient gather, and of the slab term from its own launch."""
+    lib = _lib.load()
+    geom, pot_desc = ctx.geom, ctx.pot_desc
+    N, Cn = s.q.shape
+    dtype = s.q.dtype
+    cdtype = _lib.complex_dtype(dtype)
+    empty = lambda shape, dtype=dtype: torch.empty(shape, dtype=dtype, device=s.q.device)  # noqa: E731
+    md = geom.desc(Cn)
+    psi_mesh, chi_mesh = empty((Cn,) + geom.ns), empty((Cn,) + geom.ns)
+    psi_hat = empty((Cn, geom.n_half), cdtype) if p.psi_hat else None
+    hat_work, dc = empty((Cn, geom.n_half), cdtype), empty((Cn,))
+    grad_pos = empty((N, 3)) if need_pos or need_cell else None
+    grad_q = empty((N, Cn)) if need_q else None
+    grad_cell = partials = None
+    if need_cell:
+        grad_cell = empty((3, 3))
+        partials = empty((lib.mipme_cellgrad_partials_size(C.byref(md), N),), torch.float64)
+    args = _kspace_backward_args(
+        ctx, s, plan, md, st, g, rho_hat=_lib.ptr(rho_hat), phi_atoms=_lib.ptr(s.phi_atoms), psi_mesh=psi_mesh.data_ptr(),
+        psi_hat=_lib.ptr(psi_hat), hat_work=hat_work.data_ptr(), chi_mesh=chi_mesh.data_ptr(), dc=dc.data_ptr(),
+        partials=_lib.ptr(partials), grad_positions=_lib.ptr(grad_pos), grad_charges=_lib.ptr(grad_q),
+        grad_cell=_lib.ptr(grad_cell),
+        G_deriv=filter_derivative(geom, pot_desc, dtype, s.q.device).data_ptr() if p.fused_cell else None)
+    _call("kspace_backward", lib.mipme_kspace_backward, C.byref(args))
+    if ctx.slab_axis is not None:
+        moments = empty((6 * Cn,), torch.float64)
+        _call("slab_backward", lib.mipme_slab_backward, st, _lib.dtype_code(dtype), ctx.slab_axis, C.byref(md),
+              pot_desc.prefactor, N, s.pos.data_ptr(), s.q.data_ptr(), g.data_ptr(), moments.data_ptr(), _lib.ptr(grad_pos),
+              _lib.ptr(grad_q), _lib.ptr(grad_cell))
+    return (grad_pos if need_pos else None), grad_q, grad_cell
+
+
+def _finalize_gradients(ctx, s, p, st, sr_scale, grad_pos, need_src_pos, need_src_cell):
+    """``(grad_pos, grad_src_pos, grad_src_cell)`` of the gradients that end in per-atom sums formed by the forward pass (energy
+    mode): ``mipme_sr_rows_finalize`` once for both parts where they differentiate the same tensor, else once per part."""
+    fused, q = ctx.fused, s.q
+    empty = lambda shape: torch.empty(shape, dtype=q.dtype, device=q.device)  # noqa: E731
+    grad_src_pos = None
+    grad_src_cell = empty((3, 3)) if p.sr_done and need_src_cell else None
+    if p.one_finalize:
+        grad_pos = empty((q.shape[0], 3))
+        _launch_finalize(st, q, sr_scale, ctx.full_list, fused["force"], ctx.field, fused["partials"], grad_pos, grad_src_cell)
+        return grad_pos, grad_src_pos, grad_src_cell
+    if p.mesh_done:
+        grad_pos = empty((q.shape[0], 3))
+        _launch_finalize(st, q, sr_scale, ctx.full_list, None, ctx.field, None, grad_pos, None)
+    if p.sr_done:
+        if need_src_pos:
+            grad_src_pos = empty((q.shape[0], 3))
+        _launch_finalize(st, q, sr_scale, ctx.full_list, fused["force"], None, fused["partials"], grad_src_pos, grad_src_cell)
+    return grad_pos, grad_src_pos, grad_src_cell
+
+
+def _pair_adjoint(ctx, s, st, g, need_src_pos, need_src_cell):
+    """``(grad_src_pos, grad_src_cell)`` from the general adjoint of the fused distance + pair kernel."""
+    q = s.q
+    N = q.shape[0]
+    grad_src_pos = torch.empty((N, 3), dtype=q.dtype, device=q.device)
+    grad_src_cell = partials = None
+    if need_src_cell:
+        grad_src_cell = torch.empty((3, 3), dtype=q.dtype, device=q.device)
+        partials = torch.empty((_lib.load().mipme_rows_partials_size(N),), dtype=torch.float64, device=q.device)
+    _launch_rows_fused("rspace_backward", st, N, ctx.topo, ctx.fused, s.mask, q, ctx.pot_desc, ctx.full_list, grad_out=g,
+                       force=grad_src_pos, partials=partials, grad_cell=grad_src_cell)
+    return (grad_src_pos if need_src_pos else None), grad_src_cell
+
+
+def _pair_charge_gradient(ctx, s, p, st, grad_out, g, sr_scale, grad_q):
+    """The pair part of dL/dq, added to the mesh part in ``grad_q`` (energy mode, half list: all of it, gE * V)."""
+    lib = _lib.load()
+    q, topo = s.q, ctx.topo
+    N, Cn = q.shape
+    dt, full = _lib.dtype_code(q.dtype), int(ctx.full_list)
+    if p.pair_q == "energy":
+        return s.out * sr_scale
+    if p.pair_q == "fused":
+        _launch_rows_fused("rspace_backward_charges", st, N, topo, ctx.fused, s.mask, q, ctx.pot_desc, full, src=g, transpose=1,
+                           accumulate=1, out=grad_q)
+    elif p.pair_q == "tabulated":
+        if N > 1 and grad_out.stride(0) == 0 and grad_out.stride(1) in (0, 1):
+            # a uniform upstream gradient (``result.sum().backward()``): c times the table's row sums
+            grad_q.addcmul_(ctx.tab[1], grad_out[:1])
+        else:
+            _call("rspace_backward_charges", lib.mipme_rspace_rows_tabulated, st, dt, N, topo.row_ptr.data_ptr(),
+                  ctx.tab[0].data_ptr(), g.data_ptr(), 1, full, 1, grad_q.data_ptr())
+    elif p.pair_q == "rows":
+        _call("rspace_backward_charges", lib.mipme_rspace_rows, st, dt, N, Cn, topo.row_ptr.data_ptr(), topo.entries.data_ptr(),
+              s.dist.data_ptr(), g.data_ptr(), _lib.ptr(s.mask), 1, full, C.byref(ctx.pot_desc), 1, grad_q.data_ptr())
+    return grad_q
+
+
+def _lazy_pair_gradient(ctx, s, g, sr_scale, grad_src_pos, grad_src_cell):
+    """The pair part leaves through the neighbor_distances slot: the products with the distance Jacobian ride in the
+    placeholder, the (P,) gradient is formed on demand."""
+    P = s.pairs.shape[0]
+
+    def make_grad_dist():
+        out_d = torch.empty((P,), dtype=s.pos.dtype, device=s.pos.device)
+        _launch_rspace_backward(ctx, s, g, sr_scale, out_d, None)
+        return out_d
+
+    return LazyPairGradient(P, s.pos.dtype, s.pos.device, grad_src_pos, grad_src_cell, make_grad_dist)
+
+
 class _PMEFunction(torch.autograd.Function):
     """SR + LR per-atom potentials as one autograd node."""
 
@@ -924,569 +1582,113 @@ class _PMEFunction(torch.autograd.Function):
     def forward(ctx, charges, cell, positions, neighbor_distances, neighbor_indices, pair_mask, geom, G, pot_desc,
                 full_list, slab_axis, src_positions=None, src_cell=None, src=None, lazy=False, nan_flag=None,
                 atomic_pairs=False):
-        lib = _lib.load()
+        # the route flags, read once (and here, so that a test may monkeypatch them)
+        energy_fast_path = ENERGY_FAST_PATH
+        flags = (energy_fast_path, COSCHEDULE, TAIL_FUSION, XFUSED, MESH_MODE)
+        want = _wanted(ctx.needs_input_grad)
         device, dtype = positions.device, positions.dtype
-        dt = _lib.dtype_code(dtype)
-        N, Cn = charges.shape
-        P = neighbor_indices.shape[0]
         q = charges.detach().contiguous()
         pos = positions.detach().contiguous()
         dist = neighbor_distances.detach().contiguous()
         pairs = neighbor_indices.contiguous()
         mask = None if pair_mask is None else pair_mask.contiguous()
-        out = torch.empty((N, Cn), dtype=dtype, device=device)
-        need_cell = ctx.needs_input_grad[1]
-        saved = {}
+        out = torch.empty(tuple(charges.shape), dtype=dtype, device=device)
+        same_positions = src_positions is positions
         field = tail = None
+        saved, pair_sum_done = _NO_MESH, False
         with _lib.on_device(device):
-            st = _lib.current_stream(device)
-            # atomic_pairs: one pass over the list with float atomics -- for lists that are new every call (the flattened pair
-            # list of a padded batch), where building the transposed list would cost more than it saves
-            topo = get_topology(pairs, N) if (PAIR_MODE == "rows" and not atomic_pairs) else None
-            if topo is not None and topo.fmt_flags:
-                full_list = False  # rows of a NeighborStream hold every neighbour once: a half list whatever the calculator says
-            fused = None
-            if src is not None:
-                if isinstance(topo, PairTopology) and src.shifts is not None:
-                    topo.adopt_shifts(src.shifts, src.shifts_key)
-                ent_sh, shift_fmt = topo.entries_with_shifts(src.shifts, src.shifts_key, table=mask is None)
-                if ent_sh is not None:
-                    fused = dict(
-                        ent_sh=ent_sh, fmt=shift_fmt | topo.fmt_flags, pos=src_positions.detach().contiguous(),
-                        cell=None if src_cell is None else src_cell.detach().contiguous(), force=None, partials=None,
-                        records=torch.empty((N, 4), dtype=dtype, device=device),
-                    )
-                    # speculative force sums: if the backward turns out to be in energy mode they ARE the SR forces (the
-                    # matching cell sums: decided below, once it is known whether the gather tail covers the cell gradient)
-                    if ENERGY_FAST_PATH and ctx.needs_input_grad[11]:
-                        fused["force"] = torch.empty((N, 3), dtype=dtype, device=device)
-            # deferred distances (``pair_distances(..., deferred=True)``): the fused kernel writes them as a by-product
-            write_dist = False
-            if src is not None and src.pending:
-                if src.virtual and fused is not None:
-                    pass  # nobody reads the values: the fused kernel forms the distances in registers and drops them
-                else:
-                    write_dist = fused is not None and mask is None and P > 0 and topo.sorted_by_first
-                    if not write_dist:
-                        src.materialize()
-
-            want_pair_partials = bool(fused is not None and fused["force"] is not None and src_cell is not None
-                                      and ctx.needs_input_grad[12])
-            if want_pair_partials and geom is None:
-                fused["partials"] = torch.empty((lib.mipme_rows_partials_size(N),), dtype=torch.float64, device=device)
-
-            # distances that are a plain tensor this list has been evaluated with before: the tabulated pair sum
-            tab = None
-            if (TABULATE and fused is None and topo is not None and Cn == 1 and P > 0 and not ctx.needs_input_grad[3]
-                    and type(neighbor_distances) is torch.Tensor and neighbor_distances.is_contiguous()):
-                tab = topo.tabulated(neighbor_distances, mask, pot_desc, full_list)  # (keyed on the caller's tensor object)
-            ctx.tab = tab
-
-            def run_rspace(accumulate):
-                stream = _lib.current_stream(device)
-                if fused is not None:
-                    _call(
-                        "rspace_forward", lib.mipme_sr_rows_fused,
-                        stream, dt, N, topo.row_ptr.data_ptr(), fused["ent_sh"].data_ptr(), topo.entries.data_ptr(),
-                        _lib.ptr(mask), fused["pos"].data_ptr(), _lib.ptr(fused["cell"]), q.data_ptr(), q.data_ptr(), None,
-                        0, int(full_list), C.byref(pot_desc), accumulate, fused["fmt"], fused["records"].data_ptr(),
-                        int(fused.get("records_ready", False)), out.data_ptr(), _lib.ptr(fused["force"]),
-                        _lib.ptr(fused["partials"]), None, dist.data_ptr() if write_dist else None,
-                    )
-                    if write_dist:
-                        src.pending = False
-                        if _BETS:  # rows adopted on a bet: if it is lost, the rerun (or materialize()) writes the values again
-                            _ON_LOST.append(lambda src=src: setattr(src, "pending", True))
-                elif topo is not None:
-                    if tab is not None:  # constant distances: v_SR(d) per row entry is already there (PairTopology.tabulated)
-                        _call(
-                            "rspace_forward", lib.mipme_rspace_rows_tabulated,
-                            stream, dt, N, topo.row_ptr.data_ptr(), tab[0].data_ptr(), q.data_ptr(), 0, int(full_list),
-                            accumulate, out.data_ptr(),
-                        )
-                        return
-                    _call(
-                        "rspace_forward", lib.mipme_rspace_rows,
-                        stream, dt, N, Cn, topo.row_ptr.data_ptr(), topo.entries.data_ptr(), dist.data_ptr(),
-                        q.data_ptr(), _lib.ptr(mask), 0, int(full_list), C.byref(pot_desc), accumulate, out.data_ptr(),
-                    )
-                else:
-                    _call(
-                        "rspace_forward", lib.mipme_rspace_forward,
-                        stream, dt, _lib.index_code(pairs.dtype), P, N, Cn, pairs.data_ptr(), dist.data_ptr(),
-                        q.data_ptr(), _lib.ptr(mask), int(full_list), C.byref(pot_desc), accumulate, out.data_ptr(),
-                    )
-
+            topo, full_list, fused, write_dist, tab = _pair_plan(
+                want, energy_fast_path, q, pairs, mask, neighbor_distances, geom, pot_desc, full_list, src_positions, src_cell,
+                src, atomic_pairs)
             if geom is not None:
-                md = geom.desc(Cn)
-                plan = _lib.get_plan(device, dtype, geom.ns, Cn, geom.plan_store)
-                cdtype = torch.complex64 if dtype == torch.float32 else torch.complex128
-                rho_mesh = torch.empty((Cn,) + geom.ns, dtype=dtype, device=device)
-                phi_mesh = torch.empty((Cn,) + geom.ns, dtype=dtype, device=device)
-                # rfftn(rho) itself is only needed by the cell gradient; without it the convolution runs fused (see mipme.h)
-                rho_hat = cell_partials = None
-                if not plan.xfused or not XFUSED:
-                    rho_hat = torch.empty((Cn, geom.n_half), dtype=cdtype, device=device)
-                hat_work = torch.empty((Cn, geom.n_half), dtype=cdtype, device=device)
-                dc = torch.empty((Cn,), dtype=dtype, device=device)
-                phi_atoms = torch.empty((N, Cn), dtype=dtype, device=device) if need_cell else None
-                bins = None
-                if MESH_MODE == "bricks":
-                    nbytes = lib.mipme_atom_bins_bytes(C.byref(md), N, dt)
-                    if nbytes > 0:
-                        bins = torch.empty((nbytes,), dtype=torch.uint8, device=device)
-                # speculative: the mesh force per unit gE q_a, formed by the same gather (see the backward's energy mode)
-                # (a slab term: only the gather tail folds it into the field -- 1/r, one channel; decided below)
-                p_eff = 1 if pot_desc.kind == _lib.COULOMB else pot_desc.exponent
-                slab_fusable = slab_axis is None or (Cn == 1 and p_eff == 1)
-                if ENERGY_FAST_PATH and bins is not None and Cn == 1 and ctx.needs_input_grad[2] and slab_fusable:
-                    field = torch.empty((N, 3), dtype=dtype, device=device)
-                # the binning pass can emit the (position, charge) records of the fused pair kernel for free
-                records_out = None
-                if fused is not None and bins is not None and Cn == 1 and src_positions is positions:
-                    records_out = fused["records"]
-                # co-scheduled pair sum: the spread launch also carries the row workgroups of the fused distance + pair kernel
-                # (mipme_sr_job_t); the gather then adds the mesh part to the potentials the pair sum wrote
-                ni = ctx.needs_input_grad
-                cosched = bool(COSCHEDULE and records_out is not None and mask is None and (fused["fmt"] & 0xFF) == 1 and N > 0)
-                # the 4-byte entry stream is read by the co-scheduled kernel only (mipme.h, shift_format 2): use it when the
-                # library will co-schedule -- force sums wanted, 1/r or 1/r^6 with a smearing and no exclusion radius
-                ent32 = None
-                if (cosched and fused["force"] is not None and p_eff in (1, 6) and pot_desc.smearing > 0
-                        and pot_desc.exclusion_radius <= 0):
-                    ent32 = topo.compact_entries(src.shifts, src.shifts_key)
-                # Tail of an energy step in the gather launch (mipme_kspace_forward_args_t.out_energy ...): speculative like the
-                # force sums.  If the caller reduces with weighted_sum(V, charges) (see energy_direct below), E and the assembled
-                # position gradient are already there and neither the energy reduction nor the force assembly is launched; and
-                # the rest of the contract rides along (out_grad_charges / out_grad_cell): dE/dq = 2 V for a half list, dE/dcell
-                # from partial sums of the same launches + one single-workgroup launch -- those two also serve the energy mode
-                # of THIS node's backward (lazy distances, plain tensor reductions).
-                symmetric = (not full_list) or bool(topo is not None and topo.fmt_flags)
-                want_q, want_cell, aux_seed = TAIL_REQUEST
-                tail_q = bool(ni[0] or want_q) and symmetric
-                tail_cell = (bool(ni[1] or ni[12] or want_cell) and ent32 is not None and not write_dist and src_cell is not None)
-                tail_ok = bool(
-                    TAIL_FUSION and cosched and field is not None and fused["force"] is not None and ENERGY_FAST_PATH
-                    and not ni[3] and (tail_q or not ni[0]) and (tail_cell or not (ni[1] or ni[12])) and rho_hat is None
-                    and p_eff in (1, 6) and pot_desc.exclusion_radius <= 0
-                    and (not lazy or tail_q or tail_cell))  # (lazy distances: only for what the tail adds to this node)
-                if not tail_ok:
-                    tail_q = tail_cell = False
-                # the slab term rides in the gather tail (mipme_kspace_forward_args_t.slab) or, for every other call, in the
-                # launches of its own behind the step -- and then without the speculative field, which would lack the term
-                slab_in_tail = slab_axis is not None and tail_ok
-                if slab_axis is not None and not tail_ok:
-                    field = None
-                if not tail_cell:
-                    if want_pair_partials:
-                        # the pair part's cell sums from the generic pair body (no co-scheduled launch with them)
-                        fused["partials"] = torch.empty((lib.mipme_rows_partials_size(N),), dtype=torch.float64, device=device)
-                        cosched = False
-                    if need_cell and rho_hat is None and Cn > 1:
-                        # speculative, like the force sums: the k-grid sums of the cell gradient for the energy mode, formed by
-                        # the x stage of the fused convolution while rfftn(rho) is in LDS (the backward then needs neither rho^
-                        # nor the 3-D plans; a general upstream gradient recomputes rho^ from the saved charge mesh)
-                        cell_partials = torch.empty((lib.mipme_cellgrad_partials_size(C.byref(md), N),), dtype=torch.float64,
-                                                    device=device)
-                # one channel: the x stage keeps rfftn(rho) itself (a 1 MB store at 64^3) -- the backward pass forms the k-grid
-                # sums from it in either mode, the general one with the fused convolution (mipme.h, G_deriv)
-                rho_keep = None
-                if need_cell and rho_hat is None and Cn == 1:
-                    rho_keep = torch.empty((Cn, geom.n_half), dtype=cdtype, device=device)
-                job = None
-                if cosched:
-                    job = _lib.SrJob(
-                        n_atoms=N, row_ptr=topo.row_ptr.data_ptr(),
-                        entries_shift=(fused["ent_sh"] if ent32 is None else ent32).data_ptr(),
-                        entries=topo.entries.data_ptr(), positions=fused["pos"].data_ptr(), cell=_lib.ptr(fused["cell"]),
-                        charges=q.data_ptr(), pot=C.pointer(pot_desc), full_list=int(full_list),
-                        shift_format=fused["fmt"] if ent32 is None else (2 | topo.fmt_flags),
-                        records=records_out.data_ptr(), out=out.data_ptr(), force=_lib.ptr(fused["force"]),
-                        dist_out=dist.data_ptr() if write_dist else None,
-                    )
-                if tail_ok:
-                    seed = SEED_PROMISE
-                    if seed is not None and (seed.dtype != dtype or seed.device != device or seed.numel() != 1):
-                        seed = None
-                    if aux_seed is not None and (aux_seed.dtype != dtype or aux_seed.device != device or aux_seed.numel() != 1):
-                        aux_seed = None
-                    tail = dict(energy=torch.empty((), dtype=dtype, device=device),
-                                grad=torch.empty((N, 3), dtype=dtype, device=device), seed=seed, grad_q=None, grad_cell=None,
-                                aux_seed=aux_seed)
-                    if tail_q:
-                        tail["grad_q"] = torch.empty((N, 1), dtype=dtype, device=device)
-                    if TAIL_LOG is not None and TAIL_LOG.n_frames == 1 and TAIL_LOG.values.device == device:
-                        tail["log"], tail["logged"] = TAIL_LOG, True
-                    if tail_cell:
-                        tail["grad_cell"] = torch.empty((27,), dtype=dtype, device=device)
-                        tail["G_deriv"] = filter_derivative(geom, pot_desc, dtype, device)
-                        tail["cell_work"] = torch.empty((lib.mipme_cell_tail_work(plan.handle, C.byref(md), N),),
-                                                        dtype=torch.float64, device=device)
-                keep_rho_mesh = (cell_partials is not None or tail_cell) and rho_keep is None and rho_hat is None
-                args = _lib.KspaceForwardArgs(
-                    plan=plan.handle, stream=st, dtype=dt, accumulate_out=1 if job is not None else 0,
-                    mesh=C.pointer(md), pot=C.pointer(pot_desc), n_atoms=N, positions=pos.data_ptr(), charges=q.data_ptr(),
-                    G=G.data_ptr(), rho_mesh=rho_mesh.data_ptr(), rho_hat=_lib.ptr(rho_hat), hat_work=hat_work.data_ptr(),
-                    phi_mesh=phi_mesh.data_ptr(), dc=dc.data_ptr(), out_lr=out.data_ptr(), out_phi=_lib.ptr(phi_atoms),
-                    atom_bins=_lib.ptr(bins), gather_wait_event=None,
-                    out_field=_lib.ptr(field), out_records=_lib.ptr(records_out),
-                    sr_job=C.pointer(job) if job is not None else None, out_cell_partials=_lib.ptr(cell_partials),
-                    out_energy=None if tail is None else tail["energy"].data_ptr(),
-                    out_grad_positions=None if tail is None else tail["grad"].data_ptr(),
-                    grad_seed=None if tail is None else _lib.ptr(tail["seed"]), nan_flag=nan_flag,
-                    out_grad_charges=None if tail is None else _lib.ptr(tail["grad_q"]),
-                    out_grad_cell=None if tail is None else _lib.ptr(tail["grad_cell"]),
-                    G_deriv=None if tail is None else _lib.ptr(tail.get("G_deriv")),
-                    cell_work=None if tail is None else _lib.ptr(tail.get("cell_work")),
-                    aux_seed=None if tail is None else _lib.ptr(tail["aux_seed"]), out_rho_hat=_lib.ptr(rho_keep),
-                    # the charge mesh is only read again (fft_r2c in the backward pass) if rfftn(rho) was not kept
-                    flags=0 if keep_rho_mesh else _lib.FWD_RHO_MESH_UNUSED,
-                    energy_log=None if tail is None or "log" not in tail else tail["log"].values.data_ptr(),
-                    energy_log_cursor=None if tail is None or "log" not in tail else tail["log"].cursor.data_ptr(),
-                    energy_log_capacity=0 if tail is None or "log" not in tail else tail["log"].capacity,
-                    slab=slab_axis + 1 if slab_in_tail else 0,
-                )
-                _call("kspace_forward", lib.mipme_kspace_forward, C.byref(args))
-                if records_out is not None:
-                    fused["records_ready"] = True
-                if job is not None and write_dist:
-                    src.pending = False
-                    if _BETS:
-                        _ON_LOST.append(lambda src=src: setattr(src, "pending", True))
-                if slab_axis is not None and not slab_in_tail:
-                    moments = torch.empty((6 * Cn,), dtype=torch.float64, device=device)
-                    _call(
-                        "slab_forward", lib.mipme_slab_forward, st, dt, slab_axis, C.byref(md), pot_desc.prefactor, N,
-                        pos.data_ptr(), q.data_ptr(), moments.data_ptr(), out.data_ptr(),
-                    )
-                ctx.rho_kept = rho_keep is not None
-                saved = dict(phi_mesh=phi_mesh, rho_hat=(rho_hat if rho_keep is None else rho_keep) if need_cell else None,
-                             rho_dc=dc, phi_atoms=phi_atoms,
-                             bins=bins, rho_mesh=rho_mesh if keep_rho_mesh else None,
-                             cell_partials=cell_partials)
-                if job is None:
-                    run_rspace(1)
-            else:
-                run_rspace(0)
-        ctx.save_for_backward(q, pos, dist, pairs, mask, G, *(saved.get(k) for k in ("phi_mesh", "rho_hat", "rho_dc", "phi_atoms", "bins")), out)
-        ctx.rho_mesh, ctx.cell_partials = saved.get("rho_mesh"), saved.get("cell_partials")
-        ctx.field = field
-        ctx.tail = tail  # {energy, grad, seed} written by the gather's tail, or None
-        ctx.same_positions = src_positions is positions
-        #: the pair part's gradient leaves through the neighbor_distances slot as a LazyPairGradient (see pme_potential)
-        ctx.lazy = bool(lazy) and fused is not None
-        ctx.geom, ctx.pot_desc, ctx.full_list, ctx.slab_axis = geom, pot_desc, full_list, slab_axis
-        #: the gather tail of the forward carries the slab term: potentials, energy, field and the tail's gradients include it
-        ctx.slab_in_tail = slab_in_tail = bool(geom is not None and slab_axis is not None and tail is not None)
-        ctx.topo = topo
-        ctx.fused = fused  # plain tensors made here, none of them an input or output of this node
-        # E = weighted_sum(out, charges) can be differentiated without this node (see _EnergyDirectSum) when its gradient is
-        # gE q_a (f F_a + field_a) with both per-atom sums already formed above and nothing else asks for a gradient
-        ni = ctx.needs_input_grad
-        covered = tail is not None and (tail["grad_q"] is not None or not ni[0]) and (
-            tail["grad_cell"] is not None or not (ni[1] or ni[12]))
-        ctx.energy_direct = bool(
-            ENERGY_FAST_PATH and Cn == 1 and fused is not None and fused["force"] is not None and src_positions is positions
-            and (covered or not (ni[0] or ni[1] or ni[12])) and not ni[3] and (slab_axis is None or slab_in_tail)
-            and (geom is None or field is not None) and not lazy
-        )
-        ctx.src_cell_is_cell = src_cell is cell
+                field, tail, saved, pair_sum_done = _mesh_forward(
+                    want, flags, q, pos, dist, mask, out, geom, G, pot_desc, full_list, slab_axis, lazy, nan_flag, topo, fused,
+                    write_dist, same_positions, src)
+            if not pair_sum_done:
+                _pair_forward(0 if geom is None else 1, q, dist, pairs, mask, out, pot_desc, full_list, topo, fused, write_dist,
+                              tab, src)
+        _fill_ctx(ctx, want, energy_fast_path, (q, pos, dist, pairs, mask, G, out), saved, field, tail, tab, topo, fused, geom,
+                  pot_desc, full_list, slab_axis, lazy, same_positions, src_cell is cell)
         return out
 
     @staticmethod
     @first_order
     def backward(ctx, grad_out):
-        lib = _lib.load()
-        q, pos, dist, pairs, mask, G, phi_mesh, rho_hat, rho_dc, phi_atoms, bins, out = ctx.saved_tensors
-        geom, pot_desc, fused, topo = ctx.geom, ctx.pot_desc, ctx.fused, ctx.topo
-        need_q, need_cell, need_pos, need_dist = ctx.needs_input_grad[:4]
-        lazy = ctx.lazy
-        if lazy:  # the (P,) gradient is only formed if somebody other than the distance node asks for it (see below)
-            need_dist = False
-        need_src_pos = fused is not None and ctx.needs_input_grad[11]
-        need_src_cell = fused is not None and fused["cell"] is not None and ctx.needs_input_grad[12]
-        device, dtype = pos.device, pos.dtype
-        dt = _lib.dtype_code(dtype)
-        N, Cn = q.shape
-        P = pairs.shape[0]
-        full = int(ctx.full_list)
+        s = _Saved(*ctx.saved_tensors)
+        want = _wanted(ctx.needs_input_grad)
+        geom, fused, lazy = ctx.geom, ctx.fused, ctx.lazy
+        need_q, need_cell, need_pos = want.q, want.cell, want.pos
+        # lazy: the (P,) gradient is only formed if somebody other than the distance node asks for it (see below)
+        need_dist = want.dist and not lazy
+        need_src_pos = fused is not None and want.src_pos
+        need_src_cell = fused is not None and fused["cell"] is not None and want.src_cell
+        device, dtype = s.pos.device, s.pos.dtype
+        N, Cn = s.q.shape
         g = grad_out.contiguous()
-        grad_q = grad_pos = grad_cell = grad_dist = grad_src_pos = grad_src_cell = None
+        grad_dist = None
         guard = _SkipGuard()
         with _lib.on_device(device), guard:
             st = _lib.current_stream(device)
-            do_kspace = geom is not None and (need_q or need_cell or need_pos)
-            # Energy mode: if the upstream gradient was produced by ``weighted_sum(V, charges)`` with OUR charges it is
-            # exactly gE * charges.  Then (a) the adjoint mesh is a multiple of the forward one (no second spread / FFT),
-            # (b) the forces are gE q_a times the per-atom sums the forward pass already formed (``field`` from the gather,
-            # ``force`` from the fused pair kernel), (c) for a half list dL/dq = gE * V (V is a symmetric bilinear form).
-            tag = getattr(grad_out, "_mipme_scaled", None) if ENERGY_FAST_PATH else None
-            gscale = sr_scale = select = None
-            if tag is not None and tag[0] == q.data_ptr() and tag[1] == tuple(q.shape) and tag[2] == q._version:
-                sr_scale = tag[3]  # enough for the pair part
-            elif (ENERGY_FAST_PATH and ENERGY_DETECT and tag is None and N > 0 and (fused is not None or do_kspace)
-                  and not (N > 1 and grad_out.stride(0) == 0)  # an expanded scalar (``V.sum().backward()``): not gE * charges
-                  and not torch.cuda.is_current_stream_capturing()):
-                # no tag: the caller reduced with plain tensor ops, ``(charges * V).sum()`` (README.rst:112-114) -- ask the
-                # device whether the gradient is a multiple of the charges (one small kernel + a 2-value read; the general
-                # adjoint it saves is a second spread, an FFT pair and a gradient gather).  Not during graph capture.
-                res = torch.empty((2,), dtype=dtype, device=device)
-                # (rows of a NeighborStream: the general pair kernel reads 8-byte entries, which would have to be expanded from
-                # the stream's words on every call -- those keep the host poll)
-                on_device = (DEVICE_SELECT and N >= DEVICE_SELECT_MIN_ATOMS and Cn == 1 and fused is not None
-                             and fused["force"] is not None
-                             and not (topo is not None and topo.fmt_flags)
-                             and ctx.slab_axis is None and not (need_q or need_cell or need_dist or need_src_cell)
-                             and (geom is None or ctx.field is not None) and (need_pos or need_src_pos))
-                if on_device:
-                    # only position gradients are wanted: run the GENERAL adjoint below with every kernel told to return at
-                    # once when the verdict is a match, then let one kernel replace its outputs by the energy-mode expressions
-                    # in that case -- no host read, the host keeps running ahead of the GPU
-                    select = dict(res=res, flag=torch.empty((1,), dtype=torch.int32, device=device))
-                    _scaled_match(lib, st, dt, N * Cn, g, q, res, select["flag"].data_ptr())
-                    lib.mipme_set_skip_flag(select["flag"].data_ptr())
-                    guard.armed = True
-                else:
-                    flag, flag_np = _match_flag(device)
-                    flag_np[0] = -1
-                    _scaled_match(lib, st, dt, N * Cn, g, q, res, flag.data_ptr())
-                    # the kernel also writes its verdict to pinned host memory: poll that word instead of a device-to-host copy
-                    # (hipMemcpy of 4 bytes costs 20-30 us on this stack; the poll ends a few us after the kernel does)
-                    spins = 0
-                    while flag_np[0] == -1:
-                        spins += 1
-                        if spins > 2_000_000:  # never seen; a stream synchronisation is the fallback
-                            SPIN_TIMEOUTS["match"] += 1
-                            torch.cuda.current_stream(device).synchronize()
-                            break
-                    if flag_np[0] == 1:
-                        sr_scale = res[:1]
-            if sr_scale is not None and (ctx.slab_axis is None or ctx.slab_in_tail):
-                gscale = sr_scale
-            # what the forward's gather tail already holds for exactly this upstream gradient (mipme.h, out_grad_charges /
-            # out_grad_cell): dE/dq = 2 V and dE/dcell (mesh part, pair part) per unit of the tail's seed
-            tail = ctx.tail
-            if gscale is not None and tail is not None and (tail["grad_q"] is not None or tail["grad_cell"] is not None):
-                base = tail["aux_seed"] if tail["aux_seed"] is not None else tail["seed"]
-                tscale = sr_scale if base is None else sr_scale / base
-                if need_q and tail["grad_q"] is not None:
-                    # (the tail holds the TOTAL dE/dq = 2 V of E = sum q V; through this node flows the half that comes from
-                    # V's dependence on the charges, the other half is the reduction's own)
-                    grad_q = tail["grad_q"] * (0.5 * tscale)
-                    need_q = False
-                if tail["grad_cell"] is not None and (need_cell or need_src_cell):
-                    gc = tail["grad_cell"] * tscale
-                    if need_cell:
-                        grad_cell = gc[0:9].view(3, 3)
-                        need_cell = False
-                    if need_src_cell:
-                        grad_src_cell = gc[9:18].view(3, 3)
-                        need_src_cell = False
-                do_kspace = geom is not None and (need_q or need_cell or need_pos)
-            # the mesh force field of the forward gather serves the forces AND (through cellgrad_finalize) the cell gradient
-            field = ctx.field if gscale is not None else None
-            cell_partials = ctx.cell_partials
-            if need_cell and rho_hat is None and gscale is None and geom is not None:
-                # general upstream gradient after a forward that kept the charge mesh instead of rfftn(rho): transform it now
+            sr_scale, select = _energy_mode(ctx, s, grad_out, g, st, guard,
+                                            (need_q, need_cell, need_pos, need_dist, need_src_pos, need_src_cell),
+                                            geom is not None and (need_q or need_cell or need_pos))
+            gscale = sr_scale if sr_scale is not None and (ctx.slab_axis is None or ctx.slab_in_tail) else None
+            grad_q, grad_cell, grad_src_cell = _tail_gradients(ctx.tail, gscale, sr_scale, need_q, need_cell, need_src_cell)
+            need_q, need_cell = need_q and grad_q is None, need_cell and grad_cell is None
+            need_src_cell = need_src_cell and grad_src_cell is None
+            p = _backward_plan(
+                has_geom=geom is not None, scaled=sr_scale is not None, energy=gscale is not None, need_q=need_q,
+                need_cell=need_cell, need_pos=need_pos, need_dist=need_dist, need_src_pos=need_src_pos,
+                need_src_cell=need_src_cell, full_list=ctx.full_list, Cn=Cn, has_rho_hat=s.rho_hat is not None,
+                has_field=ctx.field is not None, rho_kept=ctx.rho_kept, xfused=ctx.plan_xfused and XFUSED,
+                has_topo=ctx.topo is not None, has_fused=fused is not None,
+                has_force=fused is not None and fused["force"] is not None,
+                has_partials=fused is not None and fused["partials"] is not None, has_tab=ctx.tab is not None,
+                same_positions=ctx.same_positions, lazy=lazy)
+            rho_hat = s.rho_hat
+            plan = _lib.get_plan(device, dtype, geom.ns, Cn, geom.plan_store) if p.r2c or p.mesh is not None else None
+            if p.r2c:
                 # (with the calculator's own plan: torch.fft shares hipFFT state with it and broke later plans when tried)
-                md0 = geom.desc(Cn)
-                rho_hat = torch.empty((Cn, geom.n_half), device=device,
-                                      dtype=torch.complex64 if dtype == torch.float32 else torch.complex128)
-                _call("fft_r2c", lib.mipme_fft_r2c, _lib.get_plan(device, dtype, geom.ns, Cn, geom.plan_store).handle, st, dt,
-                      C.byref(md0), ctx.rho_mesh.data_ptr(), rho_hat.data_ptr())
-            energy_q = need_q and gscale is not None and not ctx.full_list
+                rho_hat = torch.empty((Cn, geom.n_half), device=device, dtype=_lib.complex_dtype(dtype))
+                _call("fft_r2c", _lib.load().mipme_fft_r2c, plan.handle, st, _lib.dtype_code(dtype), C.byref(geom.desc(Cn)),
+                      ctx.rho_mesh.data_ptr(), rho_hat.data_ptr())
             if need_dist:
-                grad_dist = torch.empty((P,), dtype=dtype, device=device)
-
-            def run_grad_dist(with_charges):
-                # grad_dist is a per-pair stream (no scatter); in "atomic" mode the same kernel also scatters grad_q
-                pl = pairs if topo is None else topo.pairs32
-                _call(
-                    "rspace_backward", lib.mipme_rspace_backward,
-                    _lib.current_stream(device), dt, _lib.index_code(pl.dtype), P, N, Cn, pl.data_ptr(),
-                    dist.data_ptr(), q.data_ptr(), _lib.ptr(mask), full, C.byref(pot_desc), g.data_ptr(),
-                    _lib.ptr(sr_scale), _lib.ptr(grad_dist), _lib.ptr(grad_q) if with_charges else None,
-                )
-
-            if do_kspace and gscale is not None:
-                kb_q = need_q and not energy_q
-                # with the field at hand the C call only finalises the cell gradient (no gradient gather)
-                from_field = field is not None and not kb_q
-                kb_pos = (need_pos or need_cell) and not from_field
-                if kb_pos or kb_q or need_cell:
-                    md = geom.desc(Cn)
-                    plan = _lib.get_plan(device, dtype, geom.ns, Cn, geom.plan_store)
-                    if kb_pos:
-                        grad_pos = torch.empty((N, 3), dtype=dtype, device=device)
-                    if kb_q:
-                        grad_q = torch.empty((N, Cn), dtype=dtype, device=device)
-                    partials, kgrid_ready = None, 0
-                    if need_cell:  # energy mode: the k-grid sums come from rho^ alone (no second spread / FFTs) ...
-                        grad_cell = torch.empty((3, 3), dtype=dtype, device=device)
-                        if cell_partials is not None:  # ... and the forward's fused convolution has already formed them
-                            partials, kgrid_ready = cell_partials, plan.kgrid_blocks
-                        else:
-                            partials = torch.empty((lib.mipme_cellgrad_partials_size(C.byref(md), N),), dtype=torch.float64,
-                                                   device=device)
-                    args = _lib.KspaceBackwardArgs(
-                        plan=plan.handle, stream=st, dtype=dt, mesh=C.pointer(md), pot=C.pointer(pot_desc), n_atoms=N,
-                        positions=pos.data_ptr(), charges=q.data_ptr(), grad_out=g.data_ptr(), G=G.data_ptr(),
-                        phi_mesh=phi_mesh.data_ptr(), rho_hat=_lib.ptr(rho_hat) if need_cell else None,
-                        rho_dc=_lib.ptr(rho_dc), phi_atoms=_lib.ptr(phi_atoms) if need_cell else None,
-                        partials=_lib.ptr(partials), grad_positions=_lib.ptr(grad_pos), grad_charges=_lib.ptr(grad_q),
-                        grad_cell=_lib.ptr(grad_cell), atom_bins=_lib.ptr(bins), grad_scale=gscale.data_ptr(),
-                        mesh_field=_lib.ptr(field) if from_field else None, kgrid_blocks_ready=kgrid_ready,
-                    )
-                    _call("kspace_backward", lib.mipme_kspace_backward, C.byref(args))
-                    if not need_pos:
-                        grad_pos = None
-                    if need_cell and not from_field:
-                        field = None  # the gradient gather above has produced the mesh forces
-            elif do_kspace:
-                md = geom.desc(Cn)
-                plan = _lib.get_plan(device, dtype, geom.ns, Cn, geom.plan_store)
-                cdtype = torch.complex64 if dtype == torch.float32 else torch.complex128
-                psi_mesh = torch.empty((Cn,) + geom.ns, dtype=dtype, device=device)
-                chi_mesh = torch.empty((Cn,) + geom.ns, dtype=dtype, device=device)
-                psi_hat = None
-                fused_cell = bool(need_cell and getattr(ctx, "rho_kept", False) and plan.xfused and XFUSED and Cn == 1)
-                if (need_cell and not fused_cell) or not plan.xfused or not XFUSED:
-                    psi_hat = torch.empty((Cn, geom.n_half), dtype=cdtype, device=device)
-                hat_work = torch.empty((Cn, geom.n_half), dtype=cdtype, device=device)
-                dc = torch.empty((Cn,), dtype=dtype, device=device)
-                if need_pos or need_cell:
-                    grad_pos = torch.empty((N, 3), dtype=dtype, device=device)
-                if need_q:
-                    grad_q = torch.empty((N, Cn), dtype=dtype, device=device)
-                partials = None
-                if need_cell:
-                    grad_cell = torch.empty((3, 3), dtype=dtype, device=device)
-                    partials = torch.empty((lib.mipme_cellgrad_partials_size(C.byref(md), N),), dtype=torch.float64, device=device)
-                args = _lib.KspaceBackwardArgs(
-                    plan=plan.handle, stream=st, dtype=dt, mesh=C.pointer(md), pot=C.pointer(pot_desc), n_atoms=N,
-                    positions=pos.data_ptr(), charges=q.data_ptr(), grad_out=g.data_ptr(), G=G.data_ptr(),
-                    phi_mesh=phi_mesh.data_ptr(), rho_hat=_lib.ptr(rho_hat), rho_dc=_lib.ptr(rho_dc),
-                    phi_atoms=_lib.ptr(phi_atoms), psi_mesh=psi_mesh.data_ptr(), psi_hat=_lib.ptr(psi_hat),
-                    hat_work=hat_work.data_ptr(), chi_mesh=chi_mesh.data_ptr(), dc=dc.data_ptr(),
-                    partials=_lib.ptr(partials), grad_positions=_lib.ptr(grad_pos), grad_charges=_lib.ptr(grad_q),
-                    grad_cell=_lib.ptr(grad_cell), atom_bins=_lib.ptr(bins),
-                    G_deriv=filter_derivative(geom, pot_desc, dtype, device).data_ptr() if fused_cell else None,
-                )
-                _call("kspace_backward", lib.mipme_kspace_backward, C.byref(args))
-                if ctx.slab_axis is not None:
-                    moments = torch.empty((6 * Cn,), dtype=torch.float64, device=device)
-                    _call(
-                        "slab_backward", lib.mipme_slab_backward, st, dt, ctx.slab_axis, C.byref(md), pot_desc.prefactor,
-                        N, pos.data_ptr(), q.data_ptr(), g.data_ptr(), moments.data_ptr(), _lib.ptr(grad_pos),
-                        _lib.ptr(grad_q), _lib.ptr(grad_cell),
-                    )
-                if not need_pos:
-                    grad_pos = None
-            elif need_q and not energy_q:
+                grad_dist = torch.empty((s.pairs.shape[0],), dtype=dtype, device=device)
+            mesh = (None, None, None)  # (grad_pos, grad_q, grad_cell) of the mesh part
+            if p.mesh == "energy":
+                mesh = _mesh_adjoint_energy(ctx, s, p, plan, st, g, gscale, rho_hat, need_pos, need_cell)
+            elif p.mesh == "general":
+                mesh = _mesh_adjoint_general(ctx, s, p, plan, st, g, rho_hat, need_q, need_cell, need_pos)
+            elif p.zero_q:
                 grad_q = torch.zeros((N, Cn), dtype=dtype, device=device)
-            atomic_q = need_q and topo is None and not energy_q
-            if need_dist or atomic_q:
-                run_grad_dist(atomic_q)
-
-            # ---- gradients that end in per-atom sums formed by the forward pass (energy mode) ----
-            sr_done = (need_src_pos or need_src_cell) and sr_scale is not None and fused["force"] is not None and (
-                fused["partials"] is not None or not need_src_cell)
-            mesh_done = need_pos and field is not None
-
-            def finalize(force_t, field_t, partials_t, out_pos, out_cell):
-                _call(
-                    "forces_finalize", lib.mipme_sr_rows_finalize,
-                    st, dt, N, _lib.ptr(force_t), _lib.ptr(field_t), q.data_ptr(), sr_scale.data_ptr(), full,
-                    _lib.ptr(partials_t), _lib.ptr(out_pos), _lib.ptr(out_cell),
-                )
-
-            if sr_done and need_src_cell:
-                grad_src_cell = torch.empty((3, 3), dtype=dtype, device=device)
-            if sr_done and mesh_done and ctx.same_positions and need_src_pos and not lazy:
-                # both parts differentiate the same ``positions`` tensor: one kernel, one gradient
-                grad_pos = torch.empty((N, 3), dtype=dtype, device=device)
-                finalize(fused["force"], field, fused["partials"], grad_pos, grad_src_cell if need_src_cell else None)
-            else:
-                if mesh_done:
-                    grad_pos = torch.empty((N, 3), dtype=dtype, device=device)
-                    finalize(None, field, None, grad_pos, None)
-                if sr_done:
-                    if need_src_pos:
-                        grad_src_pos = torch.empty((N, 3), dtype=dtype, device=device)
-                    finalize(fused["force"], None, fused["partials"], grad_src_pos, grad_src_cell if need_src_cell else None)
-            if (need_src_pos or need_src_cell) and not sr_done:
-                grad_src_pos = torch.empty((N, 3), dtype=dtype, device=device)
-                partials = None
-                if need_src_cell:
-                    grad_src_cell = torch.empty((3, 3), dtype=dtype, device=device)
-                    partials = torch.empty((lib.mipme_rows_partials_size(N),), dtype=torch.float64, device=device)
-                _call(
-                    "rspace_backward", lib.mipme_sr_rows_fused,
-                    st, dt, N, topo.row_ptr.data_ptr(), fused["ent_sh"].data_ptr(), topo.entries.data_ptr(),
-                    _lib.ptr(mask), fused["pos"].data_ptr(), _lib.ptr(fused["cell"]), q.data_ptr(), None, g.data_ptr(),
-                    0, full, C.byref(pot_desc), 0, fused["fmt"], fused["records"].data_ptr(), 0, None, grad_src_pos.data_ptr(),
-                    _lib.ptr(partials), _lib.ptr(grad_src_cell), None,
-                )
-                if not need_src_pos:
-                    grad_src_pos = None
-
+            grad_pos = mesh[0]
+            grad_q = grad_q if mesh[1] is None else mesh[1]
+            grad_cell = grad_cell if mesh[2] is None else mesh[2]
+            if p.pair_stream:
+                _launch_rspace_backward(ctx, s, g, sr_scale, grad_dist, grad_q if p.atomic_q else None)
+            grad_pos, grad_src_pos, src_cell_sums = _finalize_gradients(ctx, s, p, st, sr_scale, grad_pos, need_src_pos,
+                                                                        need_src_cell)
+            if p.sr_adjoint:
+                grad_src_pos, src_cell_sums = _pair_adjoint(ctx, s, st, g, need_src_pos, need_src_cell)
+            if need_src_cell:
+                grad_src_cell = src_cell_sums
             if select is not None:
-                lib.mipme_set_skip_flag(None)
+                _lib.load().mipme_set_skip_flag(None)
                 guard.armed = False
-                _call("energy_select", lib.mipme_energy_select, st, dt, N, select["res"].data_ptr(), q.data_ptr(),
-                      _lib.ptr(fused["force"]), _lib.ptr(ctx.field), full, _lib.ptr(grad_pos) if geom is not None else None,
-                      _lib.ptr(grad_src_pos))
-
-            # ---- charge gradient of the pair part ----
-            if energy_q:
-                grad_q = out * sr_scale
-            elif need_q and fused is not None:
-                _call(
-                    "rspace_backward_charges", lib.mipme_sr_rows_fused,
-                    st, dt, N, topo.row_ptr.data_ptr(), fused["ent_sh"].data_ptr(), topo.entries.data_ptr(),
-                    _lib.ptr(mask), fused["pos"].data_ptr(), _lib.ptr(fused["cell"]), q.data_ptr(), g.data_ptr(), None,
-                    1, full, C.byref(pot_desc), 1, fused["fmt"], fused["records"].data_ptr(), 0, grad_q.data_ptr(), None, None,
-                    None, None,
-                )
-            elif need_q and topo is not None and getattr(ctx, "tab", None) is not None:
-                if N > 1 and grad_out.stride(0) == 0 and grad_out.stride(1) in (0, 1):
-                    # a uniform upstream gradient (``result.sum().backward()``): c times the table's row sums
-                    grad_q.addcmul_(ctx.tab[1], grad_out[:1])
-                else:
-                    _call(
-                        "rspace_backward_charges", lib.mipme_rspace_rows_tabulated,
-                        st, dt, N, topo.row_ptr.data_ptr(), ctx.tab[0].data_ptr(), g.data_ptr(), 1, full, 1, grad_q.data_ptr(),
-                    )
-            elif need_q and topo is not None:
-                _call(
-                    "rspace_backward_charges", lib.mipme_rspace_rows,
-                    st, dt, N, Cn, topo.row_ptr.data_ptr(), topo.entries.data_ptr(), dist.data_ptr(), g.data_ptr(),
-                    _lib.ptr(mask), 1, full, C.byref(pot_desc), 1, grad_q.data_ptr(),
-                )
+                _call("energy_select", _lib.load().mipme_energy_select, st, _lib.dtype_code(dtype), N, select["res"].data_ptr(),
+                      s.q.data_ptr(), _lib.ptr(fused["force"]), _lib.ptr(ctx.field), int(ctx.full_list),
+                      _lib.ptr(grad_pos) if geom is not None else None, _lib.ptr(grad_src_pos))
+            grad_q = _pair_charge_gradient(ctx, s, p, st, grad_out, g, sr_scale, grad_q)
             if geom is None:
                 if need_pos:
                     grad_pos = torch.zeros((N, 3), dtype=dtype, device=device)
                 if need_cell:
                     grad_cell = torch.zeros((3, 3), dtype=dtype, device=device)
-            if lazy and ctx.needs_input_grad[3]:
-                # the pair part leaves through the neighbor_distances slot: the products with the distance Jacobian ride in
-                # the placeholder, the (P,) gradient is formed on demand
-                def make_grad_dist(g=g, sr_scale=sr_scale):
-                    out_d = torch.empty((P,), dtype=dtype, device=device)
-                    pl = pairs if topo is None else topo.pairs32
-                    with _lib.on_device(device):
-                        _call(
-                            "rspace_backward", lib.mipme_rspace_backward,
-                            _lib.current_stream(device), dt, _lib.index_code(pl.dtype), P, N, Cn, pl.data_ptr(),
-                            dist.data_ptr(), q.data_ptr(), _lib.ptr(mask), full, C.byref(pot_desc), g.data_ptr(),
-                            _lib.ptr(sr_scale), out_d.data_ptr(), None,
-                        )
-                    return out_d
-
-                grad_dist = LazyPairGradient(P, dtype, device, grad_src_pos, grad_src_cell, make_grad_dist)
+            if lazy and want.dist:
+                grad_dist = _lazy_pair_gradient(ctx, s, g, sr_scale, grad_src_pos, grad_src_cell)
                 grad_src_pos = grad_src_cell = None
-        return (grad_q, grad_cell, grad_pos, grad_dist, None, None, None, None, None, None, None, grad_src_pos,
-                grad_src_cell, None, None, None, None)
+        return _by_slot(charges=grad_q, cell=grad_cell, positions=grad_pos, neighbor_distances=grad_dist,
+                        src_positions=grad_src_pos, src_cell=grad_src_cell)
 
 
 def pme_potential(charges, cell, positions, neighbor_indices, neighbor_distances, pair_mask, geom, G, pot_desc,
@@ -1499,29 +1701,33 @@ def pme_potential(charges, cell, positions, neighbor_indices, neighbor_distances
                 "the handles of a NeighborStream serve single-channel calculators without a pair mask, together with the "
                 "distances from `stream.distances(positions, cell)` of the current positions; use `stream.pairs()` for a list in "
                 "the reference's format")
+
+    def node(neighbor_distances=neighbor_distances, **more):
+        return _PMEFunction.apply(*_by_slot(
+            charges=charges, cell=cell, positions=positions, neighbor_distances=neighbor_distances,
+            neighbor_indices=neighbor_indices, pair_mask=pair_mask, geom=geom, G=G, pot_desc=pot_desc, full_list=full_list,
+            slab_axis=slab_axis, nan_flag=nan_flag, **more))
+
     if atomic_pairs:
         if src is not None and src.pending:
             src.materialize()
-        return _PMEFunction.apply(charges, cell, positions, neighbor_distances, neighbor_indices, pair_mask, geom, G,
-                                  pot_desc, full_list, slab_axis, None, None, None, False, nan_flag, True)
+        return node(lazy=False, atomic_pairs=True)
     if src is not None and src.usable_for(neighbor_distances, neighbor_indices, charges.shape[1]):
         # the fused kernels differentiate through the distances in the same pass (see FUSE_DISTANCES)
         if not src.direct:
             # default: the pair part's gradient flows through ``neighbor_distances`` (lazily, LazyPairGradient) and on to
             # positions / cell via that tensor's own node -- the reference's autograd graph
-            return _PMEFunction.apply(charges, cell, positions, neighbor_distances, neighbor_indices, pair_mask, geom,
-                                      G, pot_desc, full_list, slab_axis, src.positions, src.cell, src, True, nan_flag)
+            return node(src_positions=src.positions, src_cell=src.cell, src=src, lazy=True, atomic_pairs=False)
         # opt-in (``deferred=True``): straight to the tensors the distances were built from, bypassing ``d``
-        out = _PMEFunction.apply(charges, cell, positions, neighbor_distances.detach(), neighbor_indices, pair_mask, geom,
-                                 G, pot_desc, full_list, slab_axis, src.positions, src.cell, src, False, nan_flag)
-        node = out.grad_fn
-        if node is not None and getattr(node, "energy_direct", False):
-            out._mipme_energy = (node, positions, charges, charges._version, cell, src.cell)
+        out = node(neighbor_distances.detach(), src_positions=src.positions, src_cell=src.cell, src=src, lazy=False,
+                   atomic_pairs=False)
+        fn = out.grad_fn
+        if fn is not None and getattr(fn, "energy_direct", False):
+            out._mipme_energy = (fn, positions, charges, charges._version, cell, src.cell)
         return out
     if src is not None and src.pending:
         src.materialize()
-    return _PMEFunction.apply(charges, cell, positions, neighbor_distances, neighbor_indices, pair_mask, geom, G,
-                              pot_desc, full_list, slab_axis, None, None, None, False, nan_flag)
+    return node(lazy=False, atomic_pairs=False)
 
 
 def _launch_pair_distances(pos, cl, pairs, sh, shifts_key, out):
@@ -1922,7 +2128,7 @@ class _EnergyDirectSum(torch.autograd.Function):
     def forward(ctx, V, q, positions, node, cell=None, src_cell=None):
         lib = _lib.load()
         q_c = q.detach().contiguous()
-        ctx.tail = tail = getattr(node, "tail", None)
+        ctx.tail = tail = node.tail
         if tail is not None:
             out = tail["energy"].detach()  # formed by the gather's tail: no reduction launch
         else:
@@ -1939,7 +2145,6 @@ class _EnergyDirectSum(torch.autograd.Function):
     @staticmethod
     @first_order
     def backward(ctx, g):
-        lib = _lib.load()
         q = ctx.q
         tail = ctx.tail
         need_q, need_pos, need_cell, need_src_cell = (ctx.needs_input_grad[k] for k in (1, 2, 4, 5))
@@ -1973,9 +2178,7 @@ class _EnergyDirectSum(torch.autograd.Function):
         grad_pos = torch.empty((q.shape[0], 3), dtype=q.dtype, device=q.device)
         g = g.contiguous()
         with _lib.on_device(q.device):
-            _call("forces_finalize", lib.mipme_sr_rows_finalize, _lib.current_stream(q.device), _lib.dtype_code(q.dtype),
-                  q.shape[0], _lib.ptr(ctx.force), _lib.ptr(ctx.field), q.data_ptr(), g.data_ptr(), ctx.full, None,
-                  grad_pos.data_ptr(), None)
+            _launch_finalize(_lib.current_stream(q.device), q, g, ctx.full, ctx.force, ctx.field, None, grad_pos, None)
         return None, grad_q, grad_pos, None, grad_cell, grad_src_cell
 
 
