@@ -1024,6 +1024,90 @@ typedef struct mipme_dipole_step_args {
 int mipme_dipole_step(const mipme_dipole_step_args_t* args);
 int64_t mipme_dipole_step_work(int64_t n_atoms, int64_t n_k, int cell_gradient);
 
+/* Energy, forces and dE/dq of point charges by the explicit Ewald sum in ONE step whose CELL is an input of every call, the MD
+ * form of EwaldCalculator for constant-pressure runs: GraphedEwaldStep, graphed.py.
+ * With V what the eager calculator returns for the distances |r_j - r_i + S cell| and the CURRENT contents of `cell` (the step
+ * forms the pair vectors itself from the rows), summed over the k grid given by `frequencies`:
+ *   energy        = E = sum_a q_a V_a                           (one value of `dtype`; NaN when status bit 1 is set)
+ *   forces        = -dE/dpositions    (N,3)                     (total: pair part and reciprocal part)
+ *   grad_charges  = dE/dcharges       (N,1)                     (total: 2 V for a half list; V plus the transposed half for a full one)
+ *   grad_cell     = dE/dcell          (3,3) at fixed Cartesian positions, with cell_gradient
+ *   status        = one int32: bit 0 -- some ceil(|a_d| / lr_wavelength) of the current cell differs from ns[d], i.e. the eager call
+ *                   would sum another k grid (the step keeps the grid it was given); bit 1 -- det(cell) is zero or not finite
+ * Formulas.  With S_c(k) = sum_j q_j cos(k r_j), S_s likewise, V = |det cell|, p the exponent:
+ *   k = 2 pi F cell^-T for every frequency triple F;  G(k) = mult v_LR^(k^2), dG = mult dv_LR^/dk^2       (lr_from_k_sq)
+ *   dE/dq_a = (1/V) sum_k G (c_a S_c + s_a S_s) - self q_a - 2 bg Q / V + c sum_e q_o v_SR(d_e)           (c = 1, or 1/2: full list)
+ *   F_a     = -(q_a / V) sum_k G k (c_a S_s - s_a S_c) + c q_a sum_e q_o v_SR'(d_e)/d_e u_e,   E = 1/2 sum_a q_a dE/dq_a
+ *   dE/dcell = sum_p S_p (x) dE/du_p - cell^-T W / V - (E_k + E_bg) cell^-T,   W = sum_k gk (x) k,
+ *              gk = dG |S|^2 k + G sum_j q_j r_j (c_j S_s - s_j S_c),  E_k = (1/2V) sum_k G |S|^2,  E_bg = -bg Q^2 / V
+ *   self = prefactor / Gamma(p/2 + 1) / (2 sigma^2)^(p/2); bg = the background term (p < 3) minus v_LR^(0) / 2 (p > 3: the k = 0
+ *   term of the eager sum); the sums over e run over both roles of the row of a, u_e = r_o - r_a + S'_e cell.
+ * The caller supplies what does NOT depend on the cell's values: the COMPACTED integer frequencies int32 (n_k, 3) -- k = 0 dropped,
+ * one of every +-k pair -- with their multiplicities int32 (n_k) (2, or 1 where the mirror is not in the grid), ns and
+ * lr_wavelength of the construction cell (read for `status` alone), the potential and full_list.  positions (N,3), charges (N,1)
+ * and cell (3,3, rows = lattice vectors) are device buffers in `dtype`, read by every call.  Nothing that depends on the cell's
+ * values is a by-value argument: the same argument struct serves every cell.
+ * Launches, one after the other on `stream` (capturable; nothing runs beside anything else):
+ *   prep        k blocks: every thread inverts the 3 x 3 cell in float64 and writes k, G, dG of one compacted frequency; block 0
+ *               also the geometry record (cell^-1, 1/|det|) and `status`.  Atom blocks: records (x, y, z, q), float64 block
+ *               partials of Q = sum q.  For a singular cell the k table is zeros.
+ *   structure   S_c, S_s over the compacted list, 32 lanes per k-vector (the mapping of mipme_ewald_structure, with the phase
+ *               function of the two launches that read S: see csrc/ewald_step.hip)                                 [n_k > 0]
+ *   atoms       block per (atom, k slice), one phase per (atom, k): G (c S_c + s S_s) and G k (c S_s - s S_c), four sums per
+ *               thread, written as slice partials                                                                  [n_k > 0]
+ *   rows        16 lanes per atom row over row_ptr int32[2N+1] / entries int32[2P+1] = other | code << 22 (shift_format 2,
+ *               the only one served), the 7^3 shift table in LDS filled from the device cell, one record gather per entry, the
+ *               pair function of srpot.h (exclusion radius included): per atom c sum_e q_o v_SR and the pair force over both
+ *               roles; with cell_gradient float64 block partials of sum_p S_p (x) dE/du_p over the role-i entries
+ *   cell k      gk contracted with k to 3 x 3 float64 block partials, and 1/2 G |S|^2                    [cell_gradient, n_k > 0]
+ *   finish      per atom: slice partials in slice order, 1/V, self and background terms, + the row results; float64 block
+ *               partials of 1/2 q_a dE/dq_a
+ *   final       one block: E and grad_cell from the partials, in index order
+ * No atomics anywhere and no workgroup waits for another: every sum has a fixed order, equal inputs give equal bits.
+ * Scratch, all written: records 4 N reals (16-byte aligned); kvectors 3 n_k, G, dG (with cell_gradient), s_cos, s_sin n_k reals
+ * each; work: float64[mipme_ewald_step_work(n_atoms, n_k, cell_gradient)] (0 for invalid sizes).
+ * MIPME_EINVAL before anything is launched: a NULL struct or required buffer, another struct version, an implausible size, a bad
+ * dtype, a NULL descriptor, a potential without smearing, an exclusion radius with exclusion_degree < 1, an exponent outside
+ * 1..6, another shift format, n_atoms outside 1..2^22, n_k < 0, lr_wavelength <= 0 or an ns < 1, cell_gradient without grad_cell
+ * (or without dG when n_k > 0).  Versioned like mipme_dipole_step_args_t: size and version first, fields only ever appended. */
+#define MIPME_EWALD_STEP_VERSION 1
+typedef struct mipme_ewald_step_args {
+  uint32_t size;
+  uint32_t version;
+  void* stream;
+  int32_t dtype;
+  int32_t full_list;
+  const mipme_potential_t* pot;
+  int64_t n_atoms;
+  int64_t n_k;
+  double lr_wavelength;
+  int32_t ns[3];
+  int32_t cell_gradient;
+  const void* positions;
+  const void* charges;
+  const void* cell;
+  const void* frequencies;
+  const void* multiplicities;
+  const void* row_ptr;
+  const void* entries;
+  int32_t shift_format;
+  int32_t _pad;
+  void* records;
+  void* kvectors;
+  void* G;
+  void* dG;
+  void* s_cos;
+  void* s_sin;
+  void* energy;
+  void* forces;
+  void* grad_charges;
+  void* grad_cell;
+  void* status;
+  void* work;
+} mipme_ewald_step_args_t;
+int mipme_ewald_step(const mipme_ewald_step_args_t* args);
+int64_t mipme_ewald_step_work(int64_t n_atoms, int64_t n_k, int cell_gradient);
+
 /* ---- device neighbour list (the reference uses third-party vesin on the host,
  * tests/helpers.py:240-275, and hands a fresh list to every call, examples/02-neighbor-lists-usage.py:97-164) -------------
  * One cell-list traversal, two products:

@@ -45,6 +45,7 @@ EXPORTS = (
     "mipme_combined_sr_eval", "mipme_combined_kfilter_build",
     "mipme_combined_step", "mipme_combined_step_work",
     "mipme_dipole_step", "mipme_dipole_step_work",
+    "mipme_ewald_step", "mipme_ewald_step_work",
 )
 
 
@@ -350,6 +351,33 @@ class DipoleStepArgs(_VersionedArgs):
         C.Structure.__init__(self, size=C.sizeof(type(self)), version=DIPOLE_STEP_VERSION, **fields)
 
 
+EWALD_STEP_VERSION = 1
+
+
+class EwaldStepArgs(_VersionedArgs):
+    """``mipme_ewald_step_args_t`` (version ``MIPME_EWALD_STEP_VERSION``)"""
+
+    _fields_ = [
+        ("size", C.c_uint32), ("version", C.c_uint32),
+        ("stream", C.c_void_p), ("dtype", C.c_int32), ("full_list", C.c_int32),
+        ("pot", C.POINTER(PotentialDesc)), ("n_atoms", C.c_int64), ("n_k", C.c_int64),
+        ("lr_wavelength", C.c_double), ("ns", C.c_int32 * 3), ("cell_gradient", C.c_int32),
+        ("positions", C.c_void_p), ("charges", C.c_void_p), ("cell", C.c_void_p),
+        ("frequencies", C.c_void_p), ("multiplicities", C.c_void_p),
+        ("row_ptr", C.c_void_p), ("entries", C.c_void_p), ("shift_format", C.c_int32), ("_pad", C.c_int32),
+        ("records", C.c_void_p), ("kvectors", C.c_void_p), ("G", C.c_void_p), ("dG", C.c_void_p),
+        ("s_cos", C.c_void_p), ("s_sin", C.c_void_p),
+        ("energy", C.c_void_p), ("forces", C.c_void_p), ("grad_charges", C.c_void_p), ("grad_cell", C.c_void_p),
+        ("status", C.c_void_p), ("work", C.c_void_p),
+    ]
+
+    def __init__(self, **fields):
+        unknown = set(fields) - {name for name, _ in self._fields_}
+        if unknown:
+            raise TypeError(f"{type(self).__name__}: unknown field(s) {sorted(unknown)}")
+        C.Structure.__init__(self, size=C.sizeof(type(self)), version=EWALD_STEP_VERSION, **fields)
+
+
 #: OR-ed into a shift format: rows written by ``mipme_nl_stream`` (``row_ptr`` int32[3N+1], every neighbour once per row)
 ROWS_PADDED = 0x100
 FWD_RHO_MESH_UNUSED = 1  # mipme_kspace_forward_args_t.flags: the caller never reads rho_mesh after the call
@@ -424,6 +452,7 @@ def _declare(lib):
         "mipme_combined_kfilter_build": [vp, ci, MP, C.POINTER(CombinedDesc), vp],
         "mipme_combined_step": [C.POINTER(CombinedStepArgs)],
         "mipme_dipole_step": [C.POINTER(DipoleStepArgs)],
+        "mipme_ewald_step": [C.POINTER(EwaldStepArgs)],
         "mipme_dot_forward": [vp, ci, i64, vp, vp, vp, vp],
         "mipme_dot_backward": [vp, ci, i64, vp, vp, vp, vp, vp],
         "mipme_energy_log_push": [vp, ci, ci, vp, vp, vp, ci],
@@ -497,6 +526,8 @@ def _declare(lib):
     lib.mipme_combined_step_work.argtypes = [vp, MP, i64, ci]
     lib.mipme_dipole_step_work.restype = i64
     lib.mipme_dipole_step_work.argtypes = [i64, i64, ci]
+    lib.mipme_ewald_step_work.restype = i64
+    lib.mipme_ewald_step_work.argtypes = [i64, i64, ci]
     lib.mipme_frames_slab_work.restype = i64
     lib.mipme_frames_slab_work.argtypes = []
     lib.mipme_frames_table_bytes.restype = i64

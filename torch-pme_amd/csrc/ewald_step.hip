@@ -1,0 +1,606 @@
+// Energy, forces and dE/dq (+ dE/dcell) of point charges by the explicit Ewald sum in ONE step (mipme_ewald_step,
+// include/mipme.h): the MD form of EwaldCalculator, every launch on one stream so that the whole step is one captured graph --
+// and the first step whose CELL is an input of the replay: everything that depends on the cell's values (k-vectors, G, dG/dk^2,
+// A^-1, 1/V, the Cartesian shift vectors) is rebuilt on the device from the nine values of the cell buffer in every call.
+//
+// E = sum_a q_a V_a is quadratic in the charges, so dE/dq_a = lr_a + c sum_e q_o v_SR(d_e) over both roles of the row of a
+// (c = 1, or 1/2 for a full list: V plus the transposed pair half) and E = 1/2 sum_a q_a dE/dq_a.  With S the structure factors
+// of the charges and the COMPACTED k list (one of every +-k pair, the multiplicity folded into G and dG; k = 0 left out):
+//
+//   prep       k blocks: A^-T, det from the device cell (every thread inverts the 3 x 3 itself), k = 2 pi F A^-T,
+//              G = mult v_LR(k^2), dG = mult dv_LR/dk^2 per compacted frequency; the geometry record and the status word.
+//              atom blocks: records (x, y, z, q), float64 block partials of Q = sum q                     ewald_step_prep_kernel
+//   structure  S_c(k) = sum_j q_j cos(k r_j), S_s likewise, with the phase function of the launches below  ewald_step_structure_kernel
+//   atoms      per (atom, k slice), one phase per (atom, k): phi_a += G (c S_c + s S_s), bracket_a += G k (c S_s - s S_c)
+//                                                                                                          ewald_step_atom_kernel
+//   rows       per atom a over both roles of its row: c sum_e q_o v_SR(d_e) and c q_a sum_e q_o v_SR'(d_e)/d_e u_e,
+//              u_e = r_o - r_a + S'_e cell (role-adjusted shift, table built from the DEVICE cell); with CELL
+//              sum_p S_p (x) dE/du_p over role i                                                            ewald_step_rows_kernel
+//   cell k     per k: gk = dG |S|^2 k + G sum_j q_j r_j (c S_s - s S_c), contracted with k to 3 x 3, and 1/2 G |S|^2
+//                                                                                                          ewald_step_cellk_kernel
+//   finish     16 lanes per atom over the slices: dE/dq_a = phi_a / V - self q_a - 2 bg Q / V + rows;
+//              F_a = rows - q_a bracket_a / V; float64 block partials of 1/2 q_a dE/dq_a                  ewald_step_finish_kernel
+//   final      one block: E, and dE/dcell = rows - A^-T W / V - (E_k + E_bg) A^-T  with W = sum_k gk (x) k
+//              (k = 2 pi F A^-T, so sum_k dE/dk . dk/dA = -A^-T W; the 1/V factors give the last term)     ewald_step_final_kernel
+//
+// bg = background term minus half the k = 0 limit of v_LR (non-zero for p > 3, where the eager sum keeps its k = 0 term): both
+// are a constant times Q / V per atom.  No atomics and no workgroup that waits for another: every cross-block sum is float64
+// block partials added in index order by a later launch, so equal inputs give equal bits, in fp32 too.
+#include <cmath>
+
+#include "dipole_device.h"
+#include "host.h"
+#include "kpot.h"
+#include "rows_body.h"
+
+namespace mipme {
+
+constexpr int kEsBlock = 256;
+constexpr int kEsWaves = kEsBlock / 64;
+constexpr int kEsRowsPerBlock = kEsBlock / 16;  // 16 lanes per atom row
+static_assert(kRowLanes == 16, "row_sum of rows_body.h adds up the 16 lanes of a row");
+static_assert(kCompactAtomBits == kStepRowsAtomBits, "check_step_rows of host.h admits what the 4-byte entries hold");
+constexpr int kEsKPerBlock = 8;                 // k-vectors per block of the structure and cell kernels, 32 lanes each
+constexpr int kEsKLanes = kEsBlock / kEsKPerBlock;
+constexpr int kEsTile = 256;                    // atoms staged per LDS tile of the structure and cell kernels
+constexpr int kEsCellK = 10;                    // per k block: W (9), 1/2 sum G |S|^2
+constexpr int kEsGeom = 16;                     // geometry record: A^-1 (9, row-major), 1/|det|, bad (0 / 1), padding
+constexpr int64_t kEsTargetBlocks = 2048;       // 256 CUs x 8 workgroups
+constexpr int64_t kEsMinSlice = 256;            // k-vectors per slice at least (one per thread)
+constexpr int64_t kEsMaxK = int64_t(kEsKPerBlock) * 0x7fffffff;
+
+static int64_t es_slices(int64_t N, int64_t K) {
+  if (N <= 0 || K <= 0) return 0;
+  int64_t s = (kEsTargetBlocks + N - 1) / N;
+  s = std::min<int64_t>(s, std::max<int64_t>(1, K / kEsMinSlice));
+  return std::max<int64_t>(1, std::min<int64_t>(s, 65535));
+}
+
+// work (float64 slots): [geometry 16][q partials 1 per atom block][energy partials 1 per finish block]
+//                       [row cell partials 9 per row block][k cell partials 10 per k block][row results 4 N (values of T)]
+//                       [slice partials 4 N S (values of T)]
+struct EsWork {
+  int64_t n_table_blocks, n_atom_blocks, n_fin_blocks, n_row_blocks, n_k_blocks, n_slices;
+  double *geom, *q_part, *e_part, *row_cell, *k_cell;
+  void *row_out, *slice_part;
+  int64_t total;
+};
+static EsWork es_work_layout(int64_t N, int64_t K, bool cell, void* base) {
+  EsWork w;
+  w.n_table_blocks = std::max<int64_t>(1, (K + kEsBlock - 1) / kEsBlock);  // (block 0 writes the geometry: at least one)
+  w.n_atom_blocks = (N + kEsBlock - 1) / kEsBlock;
+  w.n_fin_blocks = (N + kEsRowsPerBlock - 1) / kEsRowsPerBlock;
+  w.n_row_blocks = cell ? w.n_fin_blocks : 0;
+  w.n_k_blocks = cell ? (K + kEsKPerBlock - 1) / kEsKPerBlock : 0;
+  w.n_slices = es_slices(N, K);
+  double* b = (double*)base;
+  w.geom = b;
+  w.q_part = w.geom + kEsGeom;
+  w.e_part = w.q_part + w.n_atom_blocks;
+  w.row_cell = w.e_part + w.n_fin_blocks;
+  w.k_cell = w.row_cell + 9 * w.n_row_blocks;
+  double* row_out = w.k_cell + kEsCellK * w.n_k_blocks;
+  double* slice_part = row_out + 4 * N;
+  w.row_out = row_out;
+  w.slice_part = slice_part;
+  w.total = kEsGeom + w.n_atom_blocks + w.n_fin_blocks + 9 * w.n_row_blocks + kEsCellK * w.n_k_blocks + 4 * N + 4 * N * w.n_slices;
+  return w;
+}
+
+// sum_b p[b * stride + off], b < n: thread t adds b = t, t + 256, ... in that order, then the threads in a fixed order
+__device__ __forceinline__ double es_strided_sum(const double* __restrict__ p, int64_t n, int stride, int off, double* red) {
+  double s = 0.0;
+  for (int64_t b = threadIdx.x; b < n; b += kEsBlock) s += p[b * stride + off];
+  return block_sum<kEsWaves>(s, red);
+}
+
+// A^-T (rows b x c / det, c x a / det, a x b / det), 1 / |det| and "det is zero or not finite" of the cell, in float64
+struct EsCell {
+  double recip[9], inv_vol;
+  bool bad;
+};
+template <typename T>
+__device__ __forceinline__ EsCell es_invert_cell(const T* __restrict__ cell, double (&A)[9]) {
+#pragma unroll
+  for (int k = 0; k < 9; ++k) A[k] = double(cell[k]);
+  EsCell g;
+  const double* a = A;
+  const double* b = A + 3;
+  const double* c = A + 6;
+  g.recip[0] = b[1] * c[2] - b[2] * c[1], g.recip[1] = b[2] * c[0] - b[0] * c[2], g.recip[2] = b[0] * c[1] - b[1] * c[0];
+  g.recip[3] = c[1] * a[2] - c[2] * a[1], g.recip[4] = c[2] * a[0] - c[0] * a[2], g.recip[5] = c[0] * a[1] - c[1] * a[0];
+  g.recip[6] = a[1] * b[2] - a[2] * b[1], g.recip[7] = a[2] * b[0] - a[0] * b[2], g.recip[8] = a[0] * b[1] - a[1] * b[0];
+  const double det = a[0] * g.recip[0] + a[1] * g.recip[1] + a[2] * g.recip[2];
+  g.bad = !(det != 0.0) || !isfinite(det);
+  const double inv_det = 1.0 / det;
+#pragma unroll
+  for (int k = 0; k < 9; ++k) g.recip[k] *= inv_det;
+  g.inv_vol = fabs(inv_det);
+  return g;
+}
+
+// ---- 1. prep: k table and geometry (blocks < n_table_blocks), records and charge partials (the blocks behind them) ---------
+template <typename T>
+__global__ __launch_bounds__(kEsBlock) void ewald_step_prep_kernel(KPot kp, int64_t N, int64_t K, int n_table_blocks,
+                                                                  const T* __restrict__ cell, const int* __restrict__ freq,
+                                                                  const int* __restrict__ mult, int ns0, int ns1, int ns2,
+                                                                  double lr_wavelength, const T* __restrict__ pos,
+                                                                  const T* __restrict__ q, T* __restrict__ kvec, T* __restrict__ G,
+                                                                  T* __restrict__ dG, AtomRecord<T>* __restrict__ rec,
+                                                                  double* __restrict__ q_part, double* __restrict__ geom,
+                                                                  int* __restrict__ status) {
+  __shared__ double red[kEsWaves];
+  if (int(blockIdx.x) >= n_table_blocks) {  // (uniform per block)
+    const int64_t a = int64_t(int(blockIdx.x) - n_table_blocks) * kEsBlock + threadIdx.x;
+    double qa = 0.0;
+    if (a < N) {
+      const T qv = q[a];
+      rec[a] = AtomRecord<T>{pos[3 * a], pos[3 * a + 1], pos[3 * a + 2], qv};
+      qa = double(qv);
+    }
+    const double s = block_sum<kEsWaves>(qa, red);
+    if (threadIdx.x == 0) q_part[int(blockIdx.x) - n_table_blocks] = s;
+    return;
+  }
+  double A[9];
+  const EsCell g = es_invert_cell(cell, A);
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    // A^-1 = (A^-T)^T, row-major
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+      for (int c = 0; c < 3; ++c) geom[3 * r + c] = g.recip[3 * c + r];
+    geom[9] = g.inv_vol;
+    geom[10] = g.bad ? 1.0 : 0.0;
+    // bit 0: the eager call would choose another k grid for this cell, ns_d = ceil(|a_d| / lr_wavelength)
+    const int ns[3] = {ns0, ns1, ns2};
+    int st = g.bad ? 2 : 0;
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+      const double norm = sqrt(A[3 * d] * A[3 * d] + A[3 * d + 1] * A[3 * d + 1] + A[3 * d + 2] * A[3 * d + 2]);
+      if (!(ceil(norm / lr_wavelength) == double(ns[d]))) st |= 1;
+    }
+    status[0] = st;
+  }
+  const int64_t k = int64_t(blockIdx.x) * kEsBlock + threadIdx.x;
+  if (k >= K) return;
+  double kv[3] = {0.0, 0.0, 0.0}, v = 0.0, dv = 0.0;
+  if (!g.bad) {  // (a singular cell: a table of zeros, and the final launch writes NaN as the energy)
+    const double f0 = double(freq[3 * k]), f1 = double(freq[3 * k + 1]), f2 = double(freq[3 * k + 2]);
+#pragma unroll
+    for (int n = 0; n < 3; ++n) kv[n] = (2.0 * kPi) * (f0 * g.recip[n] + f1 * g.recip[3 + n] + f2 * g.recip[6 + n]);
+    lr_kernel_dev(kp, kv[0] * kv[0] + kv[1] * kv[1] + kv[2] * kv[2], v, dv);
+    const double m = double(mult[k]);
+    v *= m;
+    dv *= m;
+  }
+  kvec[3 * k] = T(kv[0]), kvec[3 * k + 1] = T(kv[1]), kvec[3 * k + 2] = T(kv[2]);
+  G[k] = T(v);
+  if (dG) dG[k] = T(dv);
+}
+
+// ---- 2. structure factors: 32 lanes per k-vector, the records streamed through LDS -------------------------------------------
+// The mapping of ewald_structure_kernel (ewald.hip) for one channel, with the phase of the atom and cell kernels below
+// (dipole_phase3: in float the phase is formed and reduced in double).  That kernel itself rounds a float phase before sincosf,
+// and then S and the (c, s) of the later launches disagree by |k.r| ulps per term: c S_s - s S_c of an atom with its own
+// contribution to S no longer cancels, which is the whole force on a single atom.
+template <typename T>
+__global__ __launch_bounds__(kEsBlock) void ewald_step_structure_kernel(int64_t N, int64_t K, const AtomRecord<T>* __restrict__ rec,
+                                                                       const T* __restrict__ kvec, T* __restrict__ Sc,
+                                                                       T* __restrict__ Ss) {
+  __shared__ AtomRecord<T> sr[kEsTile];
+  const int al = threadIdx.x % kEsKLanes;
+  const int64_t k = int64_t(blockIdx.x) * kEsKPerBlock + threadIdx.x / kEsKLanes;
+  const bool valid = k < K;
+  const int64_t kc = valid ? k : 0;
+  const T kx = kvec[3 * kc], ky = kvec[3 * kc + 1], kz = kvec[3 * kc + 2];
+  T ac = T(0), as = T(0);
+  for (int64_t base = 0; base < N; base += kEsTile) {
+    const int n = int(min<int64_t>(kEsTile, N - base));
+    __syncthreads();
+    for (int t = threadIdx.x; t < n; t += kEsBlock) sr[t] = rec[base + t];
+    __syncthreads();
+    for (int i = al; i < n; i += kEsKLanes) {
+      const AtomRecord<T> r = sr[i];
+      T s, c;
+      dipole_phase3(kx, ky, kz, r.x, r.y, r.z, s, c);
+      ac += r.w * c;
+      as += r.w * s;
+    }
+  }
+#pragma unroll
+  for (int off = kEsKLanes / 2; off > 0; off >>= 1) {
+    ac += __shfl_xor(ac, off, kEsKLanes);
+    as += __shfl_xor(as, off, kEsKLanes);
+  }
+  if (valid && al == 0) Sc[k] = ac, Ss[k] = as;
+}
+
+// ---- 3. fused atom kernel: block (i, slice), atom i against the k-vectors [slice * chunk, (slice + 1) * chunk) ---------------
+// part[(slice N + i) 4 + c]: c = 0 the potential sum_k G (c S_c + s S_s), c >= 1 the bracket sum_k G k (c S_s - s S_c)
+template <typename T>
+__global__ __launch_bounds__(kEsBlock) void ewald_step_atom_kernel(int64_t K, int64_t chunk, const AtomRecord<T>* __restrict__ rec,
+                                                                  const T* __restrict__ kvec, const T* __restrict__ G,
+                                                                  const T* __restrict__ Sc, const T* __restrict__ Ss,
+                                                                  T* __restrict__ part) {
+  __shared__ T red[kEsWaves][4];
+  const int64_t i = blockIdx.x, N = gridDim.x;
+  const int64_t k0 = int64_t(blockIdx.y) * chunk, k1 = min<int64_t>(K, k0 + chunk);
+  const AtomRecord<T> p = rec[i];
+  T phi = T(0), bx = T(0), by = T(0), bz = T(0);
+  for (int64_t k = k0 + threadIdx.x; k < k1; k += kEsBlock) {
+    const T gk = G[k];
+    if (gk == T(0)) continue;  // exact: the term is G(k) times a finite sum
+    const T kx = kvec[3 * k], ky = kvec[3 * k + 1], kz = kvec[3 * k + 2];
+    const T sc = Sc[k], ss = Ss[k];
+    T s, c;
+    dipole_phase3(kx, ky, kz, p.x, p.y, p.z, s, c);
+    phi += gk * (c * sc + s * ss);
+    const T b = gk * (c * ss - s * sc);
+    bx += b * kx;
+    by += b * ky;
+    bz += b * kz;
+  }
+  phi = wave_sum(phi), bx = wave_sum(bx), by = wave_sum(by), bz = wave_sum(bz);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) red[wave][0] = phi, red[wave][1] = bx, red[wave][2] = by, red[wave][3] = bz;
+  __syncthreads();
+  if (threadIdx.x < 4) {
+    T s = T(0);
+#pragma unroll
+    for (int w = 0; w < kEsWaves; ++w) s += red[w][threadIdx.x];
+    part[(int64_t(blockIdx.y) * N + i) * 4 + threadIdx.x] = s;
+  }
+}
+
+// ---- 4. pair rows ----------------------------------------------------------------------------------------------------------
+// 16 lanes per atom row, 4 rows per wavefront; the 7^3 table of Cartesian shift vectors in LDS, filled from the device cell; per
+// entry one word (other | code << 22) and one 16- or 32-byte record gather (position and charge of the partner).
+//   row_out[4 a]         = scale sum_e q_o v_SR(d_e)                               (scale = 1, or 1/2 for a full list; both roles)
+//   row_out[4 a + 1 + c] = scale q_a sum_e q_o v_SR'(d_e)/d_e (u_e)_c              (= the pair force on a)
+//   cell_part[9 b + 3 m + n] = scale sum over the role-i entries of the rows of block b of S_m q_a q_o v_SR'/d (u_e)_n   (CELL, float64)
+// PFAST: the exponent of fast_rs_eval (range separated, no exclusion: 1 or 6), 0: the general sr_eval
+template <typename T, int PFAST, bool CELL>
+__global__ __launch_bounds__(kEsBlock) void ewald_step_rows_kernel(SRPot sp, FastRS cf, int64_t N, const int* __restrict__ row_ptr,
+                                                                  const int* __restrict__ ent32,
+                                                                  const AtomRecord<T>* __restrict__ rec, const T* __restrict__ cell,
+                                                                  T scale, T* __restrict__ row_out, double* __restrict__ cell_part) {
+  __shared__ AtomRecord<T> shift_tab[kShiftTableSize];
+  __shared__ double red[kEsWaves][9];
+  const int tid = threadIdx.x;
+  {
+    T A[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) A[k] = cell[k];
+    fill_shift_table<T, kEsBlock>(shift_tab, A);
+  }
+  __syncthreads();
+  const T c_inv2s2 = T(cf.inv_2s2), c1 = T(cf.c1), cpref = T(cf.pref);
+  const int sub = tid % 16;
+  int64_t a = int64_t(blockIdx.x) * kEsRowsPerBlock + tid / 16;
+  const bool valid = a < N;
+  if (!valid) a = N - 1;
+  const int* __restrict__ rp = row_ptr + 2 * a;
+  const int beg = rp[0], mid = rp[1], end = valid ? rp[2] : beg;
+  const AtomRecord<T> pa = rec[a];
+  const unsigned last_atom = unsigned(N - 1);
+  T pot = T(0), fx = T(0), fy = T(0), fz = T(0);
+  T w00 = T(0), w01 = T(0), w02 = T(0), w10 = T(0), w11 = T(0), w12 = T(0), w20 = T(0), w21 = T(0), w22 = T(0);
+  for (int base = beg; base < end; base += 16) {
+    const int e = base + sub;
+    const bool ok = e < end;
+    const unsigned word = unsigned(ent32[ok ? e : beg]);  // (beg < end here: a real entry, left out of the sums)
+    // (a valid stream never needs the two clamps; they keep a damaged one inside the buffers)
+    const unsigned o = min(word & unsigned(kCompactMaxAtoms - 1), last_atom);
+    const unsigned code = min(word >> kCompactAtomBits, unsigned(kShiftTableSize - 1));
+    const AtomRecord<T> po = rec[o];
+    const AtomRecord<T> sh = shift_tab[code];
+    const T vx = (po.x - pa.x) + sh.x, vy = (po.y - pa.y) + sh.y, vz = (po.z - pa.z) + sh.z;
+    const T d2 = vx * vx + vy * vy + vz * vz;
+    T v, dvd;  // v_SR(d) and v_SR'(d) / d
+    if constexpr (PFAST > 0) {
+      fast_rs_eval<PFAST, true, T>(c_inv2s2, c1, cpref, d2, v, dvd, cf.cheb);
+    } else {
+      const T d = fsqrt(d2);
+      T dv;
+      sr_eval<T, true>(sp, d, v, dv);
+      dvd = dv / d;
+    }
+    if (ok) {
+      pot += po.w * v;
+      const T w = po.w * dvd;
+      const T ex = w * vx, ey = w * vy, ez = w * vz;
+      fx += ex;
+      fy += ey;
+      fz += ez;
+      if (CELL && e < mid) {  // role i: the listed pair, its own shift
+        const int ic = int(code);
+        const T sx = T(ic % kShiftTableBase - kShiftTableRange), sy = T((ic / kShiftTableBase) % kShiftTableBase - kShiftTableRange),
+                sz = T(ic / (kShiftTableBase * kShiftTableBase) - kShiftTableRange);
+        w00 += sx * ex, w01 += sx * ey, w02 += sx * ez;
+        w10 += sy * ex, w11 += sy * ey, w12 += sy * ez;
+        w20 += sz * ex, w21 += sz * ey, w22 += sz * ez;
+      }
+    }
+  }
+  pot = row_sum(pot), fx = row_sum(fx), fy = row_sum(fy), fz = row_sum(fz);
+  if (sub == 0 && valid) {
+    T* o = row_out + 4 * a;
+    const T sq = scale * pa.w;
+    o[0] = scale * pot, o[1] = sq * fx, o[2] = sq * fy, o[3] = sq * fz;
+  }
+  if (CELL) {
+    const int lane = tid & 63, wave = tid >> 6;
+    const double qa = double(pa.w);  // (the rows of a wavefront belong to different atoms: q_a goes in before the wave sum)
+    const double s0 = wave_sum(qa * double(w00)), s1 = wave_sum(qa * double(w01)), s2 = wave_sum(qa * double(w02));
+    const double s3 = wave_sum(qa * double(w10)), s4 = wave_sum(qa * double(w11)), s5 = wave_sum(qa * double(w12));
+    const double s6 = wave_sum(qa * double(w20)), s7 = wave_sum(qa * double(w21)), s8 = wave_sum(qa * double(w22));
+    if (lane == 0) {
+      red[wave][0] = s0, red[wave][1] = s1, red[wave][2] = s2;
+      red[wave][3] = s3, red[wave][4] = s4, red[wave][5] = s5;
+      red[wave][6] = s6, red[wave][7] = s7, red[wave][8] = s8;
+    }
+    __syncthreads();
+    if (tid < 9) {
+      double s = 0.0;
+#pragma unroll
+      for (int w = 0; w < kEsWaves; ++w) s += red[w][tid];
+      cell_part[9 * int64_t(blockIdx.x) + tid] = double(scale) * s;
+    }
+  }
+}
+
+// ---- 5. per-k cell gradient: 32 lanes per k-vector, the records streamed through LDS ---------------------------------------
+// gk = dE_raw/dk = dG |S|^2 k + G sum_j q_j r_j (c S_s - s S_c),  E_raw = 1/2 sum G |S|^2  (E_k = E_raw / V).
+//   k_part[10 b + 3 a + n] = sum over the k-vectors of block b of gk_a k_n;   k_part[10 b + 9] = sum 1/2 G |S|^2        (float64)
+template <typename T>
+__global__ __launch_bounds__(kEsBlock) void ewald_step_cellk_kernel(int64_t N, int64_t K, const AtomRecord<T>* __restrict__ rec,
+                                                                   const T* __restrict__ kvec, const T* __restrict__ G,
+                                                                   const T* __restrict__ dG, const T* __restrict__ Sc,
+                                                                   const T* __restrict__ Ss, double* __restrict__ k_part) {
+  __shared__ AtomRecord<T> sr[kEsTile];
+  __shared__ double red[kEsKPerBlock][kEsCellK];
+  const int al = threadIdx.x % kEsKLanes, kl = threadIdx.x / kEsKLanes;
+  const int64_t k = int64_t(blockIdx.x) * kEsKPerBlock + kl;
+  const bool live = k < K && (G[k] != T(0) || dG[k] != T(0));
+  const int64_t kc = k < K ? k : 0;
+  const T kx = kvec[3 * kc], ky = kvec[3 * kc + 1], kz = kvec[3 * kc + 2];
+  const T lSc = Sc[kc], lSs = Ss[kc];
+  T ax = T(0), ay = T(0), az = T(0);
+  for (int64_t base = 0; base < N; base += kEsTile) {
+    const int n = int(min<int64_t>(kEsTile, N - base));
+    __syncthreads();
+    for (int t = threadIdx.x; t < n; t += kEsBlock) sr[t] = rec[base + t];
+    __syncthreads();
+    if (live)
+      for (int i = al; i < n; i += kEsKLanes) {
+        const AtomRecord<T> r = sr[i];
+        T s, c;
+        dipole_phase3(kx, ky, kz, r.x, r.y, r.z, s, c);
+        const T b = r.w * (c * lSs - s * lSc);
+        ax += b * r.x;
+        ay += b * r.y;
+        az += b * r.z;
+      }
+  }
+#pragma unroll
+  for (int off = kEsKLanes / 2; off > 0; off >>= 1) {
+    ax += __shfl_xor(ax, off, kEsKLanes);
+    ay += __shfl_xor(ay, off, kEsKLanes);
+    az += __shfl_xor(az, off, kEsKLanes);
+  }
+  if (al == 0) {
+    double g[3] = {0.0, 0.0, 0.0}, e = 0.0;
+    const double kd[3] = {double(kx), double(ky), double(kz)};
+    if (live) {
+      const double gk = double(G[kc]), s2 = double(lSc) * double(lSc) + double(lSs) * double(lSs), d = double(dG[kc]) * s2;
+      g[0] = gk * double(ax) + d * kd[0];
+      g[1] = gk * double(ay) + d * kd[1];
+      g[2] = gk * double(az) + d * kd[2];
+      e = 0.5 * gk * s2;
+    }
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+      for (int n = 0; n < 3; ++n) red[kl][3 * a + n] = g[a] * kd[n];
+    red[kl][9] = e;
+  }
+  __syncthreads();
+  if (threadIdx.x < kEsCellK) {
+    double s = 0.0;
+#pragma unroll
+    for (int q = 0; q < kEsKPerBlock; ++q) s += red[q][threadIdx.x];
+    k_part[kEsCellK * int64_t(blockIdx.x) + threadIdx.x] = s;
+  }
+}
+
+// ---- 6. finish -----------------------------------------------------------------------------------------------------------
+// 16 lanes per atom: lane l adds the slices l, l + 16, ... in that order, then the 16 lanes are added by the shuffle tree of the
+// rows (with few atoms there are hundreds of slices: one thread per atom would walk them one dependent load after the other)
+template <typename T>
+__global__ __launch_bounds__(kEsBlock) void ewald_step_finish_kernel(int64_t N, int n_slices, T self_c, double two_bg,
+                                                                    const double* __restrict__ geom,
+                                                                    const AtomRecord<T>* __restrict__ rec, const T* __restrict__ part,
+                                                                    const T* __restrict__ row_out, const double* __restrict__ q_part,
+                                                                    int64_t n_q_blocks, T* __restrict__ forces,
+                                                                    T* __restrict__ grad_q, double* __restrict__ e_part) {
+  __shared__ double red[kEsWaves];
+  const double inv_vol_d = geom[9];
+  double Q = 0.0;
+  if (two_bg != 0.0) Q = es_strided_sum(q_part, n_q_blocks, 1, 0, red);  // (uniform) the same fixed order in every block
+  const T inv_vol = T(inv_vol_d), bg_term = T(two_bg * Q * inv_vol_d);
+  const int sub = threadIdx.x % 16;
+  const int64_t a = int64_t(blockIdx.x) * kEsRowsPerBlock + threadIdx.x / 16;
+  const bool valid = a < N;
+  T phi = T(0), b0 = T(0), b1 = T(0), b2 = T(0);
+  if (valid)
+    for (int s = sub; s < n_slices; s += 16) {
+      const T* __restrict__ p = part + (int64_t(s) * N + a) * 4;
+      phi += p[0], b0 += p[1], b1 += p[2], b2 += p[3];
+    }
+  phi = row_sum(phi), b0 = row_sum(b0), b1 = row_sum(b1), b2 = row_sum(b2);
+  double e = 0.0;
+  if (valid && sub == 0) {
+    const T qa = rec[a].w;
+    const T* __restrict__ r = row_out + 4 * a;
+    const T d = ((inv_vol * phi - self_c * qa) - bg_term) + r[0];
+    grad_q[a] = d;
+    const T qv = qa * inv_vol;
+    forces[3 * a] = r[1] - qv * b0;
+    forces[3 * a + 1] = r[2] - qv * b1;
+    forces[3 * a + 2] = r[3] - qv * b2;
+    e = 0.5 * double(qa) * double(d);
+  }
+  e = block_sum<kEsWaves>(e, red);
+  if (threadIdx.x == 0) e_part[blockIdx.x] = e;
+}
+
+// ---- 7. final: one block ----------------------------------------------------------------------------------------------------
+template <typename T, bool CELL>
+__global__ __launch_bounds__(kEsBlock) void ewald_step_final_kernel(int64_t n_e_blocks, const double* __restrict__ e_part,
+                                                                   T* __restrict__ energy, int64_t n_row_blocks,
+                                                                   const double* __restrict__ row_cell, int64_t n_k_blocks,
+                                                                   const double* __restrict__ k_cell, int64_t n_q_blocks,
+                                                                   const double* __restrict__ q_part, double bg,
+                                                                   const double* __restrict__ geom, T* __restrict__ grad_cell) {
+  __shared__ double red[kEsWaves];
+  __shared__ double tot[9 + kEsCellK + 1];
+  const bool bad = geom[10] != 0.0;
+  const double E = es_strided_sum(e_part, n_e_blocks, 1, 0, red);
+  if (threadIdx.x == 0) energy[0] = bad ? T(NAN) : T(E);
+  if (CELL) {
+    for (int j = 0; j < 9; ++j) {
+      const double s = es_strided_sum(row_cell, n_row_blocks, 9, j, red);
+      if (threadIdx.x == 0) tot[j] = s;
+    }
+    for (int j = 0; j < kEsCellK; ++j) {
+      const double s = es_strided_sum(k_cell, n_k_blocks, kEsCellK, j, red);
+      if (threadIdx.x == 0) tot[9 + j] = s;
+    }
+    {
+      const double s = es_strided_sum(q_part, n_q_blocks, 1, 0, red);
+      if (threadIdx.x == 0) tot[9 + kEsCellK] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x < 9) {
+      const int m = threadIdx.x / 3, n = threadIdx.x % 3;
+      const double* Wr = tot;
+      const double* Wk = tot + 9;
+      const double Ek = tot[9 + 9], Q = tot[9 + kEsCellK], inv_vol = geom[9];
+      const double e_v = inv_vol * (Ek - bg * Q * Q);  // what scales with 1/V
+      double chain = 0.0;
+      for (int a = 0; a < 3; ++a) chain += geom[3 * a + m] * Wk[3 * a + n];
+      grad_cell[3 * m + n] = bad ? T(NAN) : T(Wr[3 * m + n] - inv_vol * chain - e_v * geom[3 * n + m]);
+    }
+  }
+}
+
+// ---- host --------------------------------------------------------------------------------------------------------------------
+template <typename T, int PFAST>
+static void ewald_step_rows_launch(hipStream_t st, const mipme_ewald_step_args_t& a, const SRPot& sp, const FastRS& cf, const EsWork& w,
+                                   const AtomRecord<T>* rec) {
+  const unsigned blocks = unsigned((a.n_atoms + kEsRowsPerBlock - 1) / kEsRowsPerBlock);
+  const T scale = T(a.full_list ? 0.5 : 1.0);
+  if (a.cell_gradient)
+    ewald_step_rows_kernel<T, PFAST, true><<<blocks, kEsBlock, 0, st>>>(sp, cf, a.n_atoms, (const int*)a.row_ptr, (const int*)a.entries,
+                                                                       rec, (const T*)a.cell, scale, (T*)w.row_out, w.row_cell);
+  else
+    ewald_step_rows_kernel<T, PFAST, false><<<blocks, kEsBlock, 0, st>>>(sp, cf, a.n_atoms, (const int*)a.row_ptr, (const int*)a.entries,
+                                                                        rec, (const T*)a.cell, scale, (T*)w.row_out, nullptr);
+}
+
+template <typename T>
+static int ewald_step_t(const mipme_ewald_step_args_t& a, const KPot& kp, const SRPot& sp) {
+  hipStream_t st = (hipStream_t)a.stream;
+  const int64_t N = a.n_atoms, K = a.n_k;
+  const bool cell = a.cell_gradient != 0;
+  const EsWork w = es_work_layout(N, K, cell, a.work);
+  AtomRecord<T>* rec = (AtomRecord<T>*)a.records;
+  const FastRS cf = make_fast_rs(sp);
+  double self_c, bg_c;
+  correction_terms(a.pot, self_c, bg_c);
+  const double bg = bg_c - 0.5 * kp.k0;  // (the k = 0 term of the eager sum: v_LR(0) Q / V per atom, non-zero for p > 3)
+  ewald_step_prep_kernel<T><<<unsigned(w.n_table_blocks + w.n_atom_blocks), kEsBlock, 0, st>>>(
+      kp, N, K, int(w.n_table_blocks), (const T*)a.cell, (const int*)a.frequencies, (const int*)a.multiplicities, a.ns[0], a.ns[1],
+      a.ns[2], a.lr_wavelength, (const T*)a.positions, (const T*)a.charges, (T*)a.kvectors, (T*)a.G, cell ? (T*)a.dG : nullptr, rec,
+      w.q_part, w.geom, (int*)a.status);
+  MIPME_LAUNCH_CHECK();
+  if (K > 0) {
+    ewald_step_structure_kernel<T><<<unsigned((K + kEsKPerBlock - 1) / kEsKPerBlock), kEsBlock, 0, st>>>(
+        N, K, rec, (const T*)a.kvectors, (T*)a.s_cos, (T*)a.s_sin);
+    MIPME_LAUNCH_CHECK();
+    const int64_t chunk = (K + w.n_slices - 1) / w.n_slices;
+    ewald_step_atom_kernel<T><<<dim3(unsigned(N), unsigned(w.n_slices)), kEsBlock, 0, st>>>(
+        K, chunk, rec, (const T*)a.kvectors, (const T*)a.G, (const T*)a.s_cos, (const T*)a.s_sin, (T*)w.slice_part);
+    MIPME_LAUNCH_CHECK();
+  }
+  switch (fast_rs_exponent(sp)) {
+    case 1: ewald_step_rows_launch<T, 1>(st, a, sp, cf, w, rec); break;
+    case 6: ewald_step_rows_launch<T, 6>(st, a, sp, cf, w, rec); break;
+    default: ewald_step_rows_launch<T, 0>(st, a, sp, cf, w, rec); break;
+  }
+  MIPME_LAUNCH_CHECK();
+  if (cell && K > 0) {
+    ewald_step_cellk_kernel<T><<<unsigned(w.n_k_blocks), kEsBlock, 0, st>>>(N, K, rec, (const T*)a.kvectors, (const T*)a.G,
+                                                                           (const T*)a.dG, (const T*)a.s_cos, (const T*)a.s_sin,
+                                                                           w.k_cell);
+    MIPME_LAUNCH_CHECK();
+  }
+  ewald_step_finish_kernel<T><<<unsigned(w.n_fin_blocks), kEsBlock, 0, st>>>(N, int(w.n_slices), T(self_c), 2.0 * bg, w.geom, rec,
+                                                                            (const T*)w.slice_part, (const T*)w.row_out, w.q_part,
+                                                                            w.n_atom_blocks, (T*)a.forces, (T*)a.grad_charges,
+                                                                            w.e_part);
+  MIPME_LAUNCH_CHECK();
+  if (cell)
+    ewald_step_final_kernel<T, true><<<1, kEsBlock, 0, st>>>(w.n_fin_blocks, w.e_part, (T*)a.energy, w.n_row_blocks, w.row_cell,
+                                                            w.n_k_blocks, w.k_cell, w.n_atom_blocks, w.q_part, bg, w.geom,
+                                                            (T*)a.grad_cell);
+  else
+    ewald_step_final_kernel<T, false><<<1, kEsBlock, 0, st>>>(w.n_fin_blocks, w.e_part, (T*)a.energy, 0, nullptr, 0, nullptr, 0, nullptr,
+                                                             bg, w.geom, nullptr);
+  MIPME_LAUNCH_CHECK();
+  return MIPME_OK;
+}
+
+}  // namespace mipme
+
+using namespace mipme;
+
+extern "C" {
+
+int64_t mipme_ewald_step_work(int64_t n_atoms, int64_t n_k, int cell_gradient) {
+  if (n_atoms < 1 || n_atoms > kCompactMaxAtoms || n_k < 0 || n_k > kEsMaxK) return 0;
+  return es_work_layout(n_atoms, n_k, cell_gradient != 0, nullptr).total;
+}
+
+int mipme_ewald_step(const mipme_ewald_step_args_t* in) {
+  const char* who = "mipme_ewald_step";
+  mipme_ewald_step_args_t a;
+  int rc = load_args(in, a, MIPME_EWALD_STEP_VERSION, who);
+  if (rc) return rc;
+  // everything the arguments alone decide, before anything touches a device
+  MIPME_REQUIRE(a.dtype == MIPME_F32 || a.dtype == MIPME_F64, "%s: invalid dtype %d", who, int(a.dtype));
+  MIPME_REQUIRE(a.pot != nullptr, "%s: potential descriptor is NULL", who);
+  MIPME_REQUIRE(a.pot->smearing > 0,
+                "%s: the potential has no smearing (`smearing` is %g): the Ewald sum needs a range-separated potential", who,
+                a.pot->smearing);
+  MIPME_REQUIRE(!(a.pot->exclusion_radius > 0) || a.pot->exclusion_degree >= 1, "%s: exclusion_degree must be >= 1, got %d", who,
+                int(a.pot->exclusion_degree));
+  MIPME_REQUIRE(a.n_k >= 0 && a.n_k <= kEsMaxK, "%s: n_k must be >= 0, got %lld", who, (long long)a.n_k);
+  if ((rc = check_step_rows(a.shift_format, a.n_atoms, who))) return rc;
+  MIPME_REQUIRE(std::isfinite(a.lr_wavelength) && a.lr_wavelength > 0 && a.ns[0] >= 1 && a.ns[1] >= 1 && a.ns[2] >= 1,
+                "%s: lr_wavelength must be positive and ns >= 1 (the grid `status` compares with), got %g and (%d, %d, %d)", who,
+                a.lr_wavelength, int(a.ns[0]), int(a.ns[1]), int(a.ns[2]));
+  MIPME_REQUIRE(!a.cell_gradient || a.grad_cell, "%s: cell_gradient needs grad_cell", who);
+  MIPME_REQUIRE(!a.cell_gradient || a.n_k == 0 || a.dG, "%s: cell_gradient needs dG (n_k reals of scratch)", who);
+  MIPME_REQUIRE(a.positions && a.charges && a.cell && a.row_ptr && a.entries && a.records && a.energy && a.forces && a.grad_charges &&
+                    a.status && a.work &&
+                    (a.n_k == 0 || (a.frequencies && a.multiplicities && a.kvectors && a.G && a.s_cos && a.s_sin)),
+                "%s: NULL required buffer", who);
+  KPot kp;
+  SRPot sp;
+  if ((rc = make_kpot(a.pot, kp)) || (rc = make_srpot(a.pot, sp))) return rc;
+  DT_SWITCH(a.dtype, ewald_step_t<float>(a, kp, sp), ewald_step_t<double>(a, kp, sp));
+}
+
+}  // extern "C"

@@ -1171,3 +1171,162 @@ class GraphedDipoleStep(_ExplicitListStep):
         if self.cell_gradient:
             out += (self.cell_grad,)
         return out
+
+
+class GraphedEwaldStep(_ExplicitListStep):
+    """``E, F, dE_dq = step(positions, charges, cell)`` for an :class:`~torchpme_amd.EwaldCalculator`, replayed from one HIP
+    graph: the MD form of the eager call for a fixed neighbour list -- and a cell that may change from call to call (NPT runs,
+    cell relaxations, strain scans).
+
+    With ``V`` what the eager calculator returns for ``pair_distances(positions, pairs, cell, shifts)`` and the current cell,
+    ``E = sum_a q_a V_a`` (0-dim), ``F = -dE/dpositions`` (N, 3), ``dE_dq = dE/dcharges`` (N, 1; the total derivative: ``2 V`` for
+    a half list, ``V`` plus the transposed pair half for a full one) and, with ``cell_gradient``, ``dE_dcell`` (3, 3) at fixed
+    Cartesian positions (the convention of the other steps).  All outputs are buffers of the object, overwritten by every call.
+
+    A call copies whichever of ``positions``, ``charges`` and ``cell`` are given into the object's buffers and replays one graph:
+    no host reads, nothing re-captured.  Everything that depends on the cell's values -- k-vectors, G(k), dG/dk^2, the inverse
+    cell, 1/V, the Cartesian shift vectors of the pair rows -- is rebuilt on the device inside the replay from the nine values of
+    the cell buffer (``mipme_ewald_step``, csrc/ewald_step.hip).  Every sum has a fixed order (no floating-point atomics), so
+    equal inputs give equal bits.
+
+    The SET of k-vectors is fixed when the object is built: the integer frequencies the eager call chooses for the construction
+    cell, ``ns_d = ceil(|a_d| / lr_wavelength)`` per axis (:attr:`ns`), one of every pair +-k (:attr:`n_k` vectors).  The eager
+    call would choose another grid as soon as some ``ns_d`` changes; the step keeps its grid, so the energy stays a smooth
+    function of the cell, and says so: :attr:`status` is a device ``int32`` tensor every replay writes -- bit 0: the eager call
+    would use another k grid for this cell; bit 1: ``det(cell)`` is zero or not finite (the energy is NaN then) -- and
+    :meth:`kgrid_matches` is the same comparison on the host.  The skin of the list under a changing cell is the caller's
+    business; a new list needs :meth:`recapture`.
+
+    :param calculator: an :class:`EwaldCalculator` whose potential is exactly a :class:`CoulombPotential` or an
+        :class:`InversePowerLawPotential` (exponent 1..6), with or without exclusion radius, any ``prefactor``; half or full list
+        from ``calculator.full_neighbor_list``
+    :param charges: (N, 1)
+    :param cell: (3, 3), rows are the lattice vectors
+    :param positions: (N, 3)
+    :param neighbor_indices, neighbor_shifts: an explicit list (P, 2) with integer cell shifts (P, 3) in [-3, 3]; at most 2^22 atoms
+    :param cell_gradient: also return ``dE/dcell``
+    :param warmup: eager runs before the capture
+    """
+
+    def __init__(self, calculator, charges, cell, positions, neighbor_indices, neighbor_shifts, cell_gradient: bool = False,
+                 warmup: int = 3):
+        from .calculators import EwaldCalculator, _integer_frequencies
+        from .potentials import CoulombPotential, InversePowerLawPotential
+
+        if not isinstance(calculator, EwaldCalculator):
+            raise TypeError(f"GraphedEwaldStep serves an EwaldCalculator, got a {type(calculator).__name__}: use GraphedEnergyForces "
+                            "for the mesh calculators")
+        pot = calculator.potential
+        if type(pot) not in (CoulombPotential, InversePowerLawPotential):
+            raise TypeError(f"GraphedEwaldStep: the kernels know exactly CoulombPotential and InversePowerLawPotential, got a "
+                            f"{type(pot).__name__}; call the calculator eagerly")
+        if charges.dim() != 2 or charges.shape[1] != 1:
+            raise ValueError(f"GraphedEwaldStep handles a single charge channel, `charges` of shape [n_atoms, 1], got tensor with "
+                             f"shape {list(charges.shape)}")
+        if positions.dim() != 2 or positions.shape[1] != 3 or positions.shape[0] != charges.shape[0]:
+            raise ValueError(f"`positions` must be a tensor with shape [n_atoms, 3] with n_atoms = {charges.shape[0]} (the charges), "
+                             f"got tensor with shape {list(positions.shape)}")
+        if tuple(cell.shape) != (3, 3):
+            raise ValueError(f"`cell` must be a tensor with shape [3, 3], got tensor with shape {list(cell.shape)}")
+        if not (positions.dtype == charges.dtype == cell.dtype) or positions.dtype not in (torch.float32, torch.float64):
+            raise ValueError(f"`positions`, `charges` and `cell` must share one dtype, float32 or float64, got {positions.dtype}, "
+                             f"{charges.dtype} and {cell.dtype}")
+        if positions.shape[0] < 1 or positions.shape[0] > (1 << 22):
+            raise ValueError(f"GraphedEwaldStep handles 1 to 2^22 atoms (the 4-byte pair entries of the row kernel), got "
+                             f"{positions.shape[0]}")
+        self._check_list(neighbor_indices, neighbor_shifts)
+        self.lr_wavelength = float(calculator.lr_wavelength)
+        # (raises ValueError for a singular cell; the frequencies as the eager call forms them)
+        freq, _ = _integer_frequencies(cell.detach(), self.lr_wavelength, None)
+        for t, name in ((positions, "positions"), (charges, "charges"), (cell, "cell"), (neighbor_indices, "neighbor_indices"),
+                        (neighbor_shifts, "neighbor_shifts")):
+            _lib.require_device(t, name)
+        self.calc = calculator
+        self.cell_gradient = bool(cell_gradient)
+        self.full = bool(calculator.full_neighbor_list)
+        lib = self._lib = _lib.load()
+        device, dtype = positions.device, positions.dtype
+        self.device, self.dtype, self._dt = device, dtype, _lib.dtype_code(dtype)
+        N = self.n_atoms = positions.shape[0]
+        self._desc = pot._descriptor()
+        new = lambda *shape, dt=dtype: torch.empty(shape, dtype=dt, device=device)  # noqa: E731
+        self.cell = cell.detach().clone().contiguous()
+        self.ns = self._ns_of(cell, self.lr_wavelength)
+        f = freq.cpu().numpy()
+        rows, weight = _compact_kvectors(f, self.ns)
+        K = self.n_k = int(len(rows))
+        self._freq = torch.tensor(np.rint(f[rows]).astype(np.int32).reshape(K, 3), device=device)
+        self._mult = torch.tensor(weight.astype(np.int32), device=device)
+        self._kvec, self._G, self._Sc, self._Ss = new(max(K, 1), 3), new(max(K, 1)), new(max(K, 1)), new(max(K, 1))
+        self._dG = new(max(K, 1)) if self.cell_gradient else None
+        self.pos = positions.detach().clone().contiguous()
+        self.q = charges.detach().clone().contiguous()
+        self._rec = new(N, 4)
+        self.energy, self.forces, self.charge_grad = new(), new(N, 3), new(N, 1)
+        self.cell_grad = new(3, 3) if self.cell_gradient else None
+        self.status = torch.zeros(1, dtype=torch.int32, device=device)
+        self._work = new(max(1, int(lib.mipme_ewald_step_work(N, K, int(self.cell_gradient)))), dt=torch.float64)
+        self._warmup = max(1, int(warmup))
+        self._capture(neighbor_indices, neighbor_shifts)
+
+    @staticmethod
+    def _ns_of(cell, lr_wavelength):
+        cell_host = cell.detach().to("cpu", torch.float64).numpy()
+        return tuple(int(n) for n in np.ceil(np.linalg.norm(cell_host, axis=1) / lr_wavelength))
+
+    def kgrid_matches(self, cell) -> bool:
+        """Whether the eager calculator would sum the step's k grid for ``cell``: every ``ceil(|a_d| / lr_wavelength)`` equals
+        the one of the construction cell (bit 0 of :attr:`status` clear), decided on the host."""
+        return self._ns_of(cell, self.lr_wavelength) == self.ns
+
+    @staticmethod
+    def _check_list(neighbor_indices, neighbor_shifts):
+        if neighbor_indices.dim() != 2 or neighbor_indices.shape[1] != 2:
+            raise ValueError(f"`neighbor_indices` must be a tensor with shape [n_pairs, 2], got tensor with shape "
+                             f"{list(neighbor_indices.shape)}")
+        if neighbor_shifts.dim() != 2 or tuple(neighbor_shifts.shape) != (neighbor_indices.shape[0], 3):
+            raise ValueError(f"`neighbor_shifts` must be a tensor with shape [n_pairs, 3] with n_pairs = {neighbor_indices.shape[0]}, "
+                             f"got tensor with shape {list(neighbor_shifts.shape)}")
+        if neighbor_shifts.numel() > 0:
+            s = neighbor_shifts.detach()
+            if bool((s != s.round()).any()) or float(s.abs().max()) > 3:
+                raise ValueError("GraphedEwaldStep: the cell shifts must be integers in [-3, 3] (the 4-byte pair entries of the row "
+                                 "kernel); wrap the positions into the cell or use a shorter cutoff")
+
+    def _launch(self):
+        with _lib.on_device(self.device):
+            a = _lib.EwaldStepArgs(
+                stream=_lib.current_stream(self.device), dtype=self._dt, full_list=int(self.full), pot=C.pointer(self._desc),
+                n_atoms=self.n_atoms, n_k=self.n_k, lr_wavelength=self.lr_wavelength, ns=(C.c_int32 * 3)(*self.ns),
+                cell_gradient=int(self.cell_gradient), positions=self.pos.data_ptr(), charges=self.q.data_ptr(),
+                cell=self.cell.data_ptr(), frequencies=self._freq.data_ptr(), multiplicities=self._mult.data_ptr(),
+                row_ptr=self._row_ptr.data_ptr(), entries=self._ent32.data_ptr(), shift_format=2, records=self._rec.data_ptr(),
+                kvectors=self._kvec.data_ptr(), G=self._G.data_ptr(), dG=_lib.ptr(self._dG), s_cos=self._Sc.data_ptr(),
+                s_sin=self._Ss.data_ptr(), energy=self.energy.data_ptr(), forces=self.forces.data_ptr(),
+                grad_charges=self.charge_grad.data_ptr(), grad_cell=_lib.ptr(self.cell_grad), status=self.status.data_ptr(),
+                work=self._work.data_ptr())
+            _lib.check(self._lib.mipme_ewald_step(C.byref(a)))
+
+    def recapture(self, neighbor_indices, neighbor_shifts, positions: torch.Tensor | None = None,
+                  charges: torch.Tensor | None = None, cell: torch.Tensor | None = None) -> None:
+        """New neighbour list: rebuild the pair topology and capture the step again; the k grid and every buffer are kept.  The
+        list is validated before anything of the object changes."""
+        self._check_list(neighbor_indices, neighbor_shifts)
+        self._capture(neighbor_indices, neighbor_shifts, [(self.pos, positions), (self.q, charges), (self.cell, cell)])
+
+    def __call__(self, positions: torch.Tensor | None = None, charges: torch.Tensor | None = None,
+                 cell: torch.Tensor | None = None):
+        """``E, F, dE_dq`` (+ ``dE_dcell`` with ``cell_gradient``) of the current -- or the given -- positions, charges and cell:
+        up to three small copies and one graph replay."""
+        with torch.no_grad():
+            if positions is not None:
+                self.pos.copy_(positions)
+            if charges is not None:
+                self.q.copy_(charges)
+            if cell is not None:
+                self.cell.copy_(cell)
+        self.graph.replay()
+        out = (self.energy, self.forces, self.charge_grad)
+        if self.cell_gradient:
+            out += (self.cell_grad,)
+        return out
