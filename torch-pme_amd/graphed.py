@@ -1330,3 +1330,264 @@ class GraphedEwaldStep(_ExplicitListStep):
         if self.cell_gradient:
             out += (self.cell_grad,)
         return out
+
+
+class GraphedEwaldBatch:
+    """``energies, forces, dE_dq = batch(positions, charges, cells)`` for MANY small systems and one
+    :class:`~torchpme_amd.EwaldCalculator`, replayed from one HIP graph: the data-set form of :class:`GraphedEwaldStep` --
+    hundreds to thousands of structures of 10 to 500 atoms, each with its own cell, its own atom count and its own k grid, whose
+    energies, forces, charge gradients and stress labels are wanted together.  A :class:`GraphedEwaldStep` replay at these sizes
+    is seven launches of a few dozen workgroups: latency, not work.  The batch runs the same seven launches ONCE for all frames
+    (``mipme_ewald_batch``, csrc/ewald_batch.hip; a table maps every workgroup to its frame, no workgroup straddles two).
+
+    For frame f, ``energies[f]``, ``forces[f]``, ``dE_dq[f]`` and -- with ``cell_gradient`` -- ``dE_dcell[f]`` mean word for word
+    what ``E``, ``F``, ``dE_dq`` and ``dE_dcell`` of a :class:`GraphedEwaldStep` of that frame mean: total derivatives, the cell
+    gradient at fixed Cartesian positions.  ``energies`` is (F,); ``forces`` and ``dE_dq`` are lists of per-frame views into one
+    flat buffer each, (sum N, 3) and (sum N, 1), also exposed as :attr:`forces_flat` and :attr:`charge_grads_flat`; ``dE_dcell``
+    is one (F, 3, 3) tensor.  All outputs are buffers of the object, overwritten by every call.
+
+    A call copies whichever of ``positions``, ``charges`` and ``cells`` are given into the object's buffers -- each either one
+    flat tensor in frame order or a list of F per-frame tensors, which goes in through ONE ``torch.cat(..., out=buffer)`` -- and
+    replays one graph: no host reads, nothing re-captured, and nothing launched depends on any cell having the values it had at
+    construction.  Every sum has a fixed order, and a frame is computed from its own inputs alone: the bits it gets do not depend
+    on its index, on F or on the other frames of the batch.
+
+    The k grid of every frame is frozen at construction, as in the single step: :attr:`ns` ``[f]``, :attr:`n_k` ``[f]`` (one of
+    every pair +-k).  :attr:`status` is a device ``int32`` (F,) tensor every replay writes, with the single step's two bits per
+    frame -- bit 0: the eager call would use another k grid for this cell; bit 1: ``det(cell)`` is zero or not finite (that
+    frame's energy is NaN, no other frame is touched) -- and :meth:`kgrid_matches` is the comparison of bit 0 on the host.
+    :attr:`atom_ptr` holds the F + 1 host offsets of the frames in the flat buffers.  Frames whose cell is shorter than
+    ``lr_wavelength`` along every axis have the grid (1, 1, 1) and ``n_k == 0``; they are served, as are frames with an empty list
+    or a single atom.
+
+    Not served: the slab term, several charge channels, ``neighbors=`` streams, frames with different potentials.
+
+    :param calculator: one :class:`EwaldCalculator` for all frames, under the rules of :class:`GraphedEwaldStep`: the potential
+        exactly a :class:`CoulombPotential` or an :class:`InversePowerLawPotential` (exponent 1..6), with or without exclusion
+        radius, any ``prefactor``; half or full lists from ``calculator.full_neighbor_list``
+    :param frames: sequence of ``(charges (N_f, 1), cell (3, 3), positions (N_f, 3), neighbor_indices (P_f, 2), neighbor_shifts
+        (P_f, 3))``, one dtype (float32 or float64) and one device throughout; integer cell shifts in [-3, 3]
+    :param cell_gradient: also return ``dE/dcell`` of every frame
+    :param warmup: eager runs before the capture
+    """
+
+    MAX_FRAMES = 1 << 20
+
+    def __init__(self, calculator, frames, cell_gradient: bool = False, warmup: int = 3):
+        from .calculators import EwaldCalculator, _integer_frequencies
+        from .potentials import CoulombPotential, InversePowerLawPotential
+
+        who = "GraphedEwaldBatch"
+        if not isinstance(calculator, EwaldCalculator):
+            raise TypeError(f"{who} serves an EwaldCalculator, got a {type(calculator).__name__}: use GraphedFrameBatch for the mesh "
+                            "calculators")
+        pot = calculator.potential
+        if type(pot) not in (CoulombPotential, InversePowerLawPotential):
+            raise TypeError(f"{who}: the kernels know exactly CoulombPotential and InversePowerLawPotential, got a "
+                            f"{type(pot).__name__}; call the calculator eagerly")
+        frames = [tuple(fr) for fr in frames]
+        F = self.n_frames = len(frames)
+        if F == 0:
+            raise ValueError(f"{who}: `frames` is empty")
+        if F > self.MAX_FRAMES:
+            raise ValueError(f"{who} handles at most 2^20 frames, got {F}")
+        self.lr_wavelength = float(calculator.lr_wavelength)
+        first = frames[0][2] if len(frames[0]) == 5 else None
+        freqs = []
+        for f, fr in enumerate(frames):
+            if len(fr) != 5:
+                raise ValueError(f"{who}: frame {f} must be (charges, cell, positions, neighbor_indices, neighbor_shifts), got "
+                                 f"{len(fr)} items")
+            charges, cell, positions, idx, shifts = fr
+            if charges.dim() != 2 or charges.shape[1] != 1:
+                raise ValueError(f"{who}: frame {f}: a single charge channel, `charges` of shape [n_atoms, 1], got tensor with shape "
+                                 f"{list(charges.shape)}")
+            if positions.dim() != 2 or positions.shape[1] != 3 or positions.shape[0] != charges.shape[0]:
+                raise ValueError(f"{who}: frame {f}: `positions` must be a tensor with shape [n_atoms, 3] with n_atoms = "
+                                 f"{charges.shape[0]} (the charges), got tensor with shape {list(positions.shape)}")
+            if tuple(cell.shape) != (3, 3):
+                raise ValueError(f"{who}: frame {f}: `cell` must be a tensor with shape [3, 3], got tensor with shape "
+                                 f"{list(cell.shape)}")
+            if not (positions.dtype == charges.dtype == cell.dtype == first.dtype) or positions.dtype not in (torch.float32,
+                                                                                                              torch.float64):
+                raise ValueError(f"{who}: frame {f}: `positions`, `charges` and `cell` of all frames must share one dtype, float32 or "
+                                 f"float64, got {positions.dtype}, {charges.dtype} and {cell.dtype} (frame 0: {first.dtype})")
+            if positions.shape[0] < 1 or positions.shape[0] > (1 << 22):
+                raise ValueError(f"{who}: frame {f}: a frame holds 1 to 2^22 atoms (the 4-byte pair entries of the row kernel), got "
+                                 f"{positions.shape[0]}")
+            self._check_list(f, idx, shifts)
+            for t in (charges, cell, idx, shifts, positions):
+                if t.device != first.device:
+                    raise ValueError(f"{who}: frame {f}: all tensors of all frames must be on one device, got {t.device} and "
+                                     f"{first.device}")
+            try:  # (raises ValueError for a singular cell; the frequencies as the eager call forms them)
+                freqs.append(_integer_frequencies(cell.detach(), self.lr_wavelength, None)[0])
+            except ValueError as e:
+                raise ValueError(f"{who}: frame {f}: {e}") from None
+        for f, fr in enumerate(frames):
+            for t, name in zip(fr, ("charges", "cell", "positions", "neighbor_indices", "neighbor_shifts")):
+                _lib.require_device(t, f"{name} of frame {f}")
+        self.calc = calculator
+        self.cell_gradient = bool(cell_gradient)
+        self.full = bool(calculator.full_neighbor_list)
+        lib = self._lib = _lib.load()
+        device, dtype = first.device, first.dtype
+        self.device, self.dtype, self._dt = device, dtype, _lib.dtype_code(dtype)
+        self._desc = pot._descriptor()
+        counts = [fr[2].shape[0] for fr in frames]
+        self._atom_ptr = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+        self.atom_ptr = [int(v) for v in self._atom_ptr]
+        self.ns, self.n_k, f_all, m_all = [], [], [], []
+        for fr, freq in zip(frames, freqs):
+            ns = GraphedEwaldStep._ns_of(fr[1], self.lr_wavelength)
+            fq = freq.cpu().numpy()
+            rows, weight = _compact_kvectors(fq, ns)
+            self.ns.append(ns)
+            self.n_k.append(int(len(rows)))
+            f_all.append(np.rint(fq[rows]).astype(np.int32).reshape(-1, 3))
+            m_all.append(weight.astype(np.int32))
+        self._k_ptr = np.concatenate([[0], np.cumsum(self.n_k)]).astype(np.int64)
+        self._ns = np.ascontiguousarray(np.asarray(self.ns, dtype=np.int32).reshape(F, 3))
+        n_work = int(lib.mipme_ewald_batch_work(F, self._atom_ptr.ctypes.data, self._k_ptr.ctypes.data, int(self.cell_gradient)))
+        if n_work == 0:
+            raise ValueError(f"{who}: the batch is beyond the limits of the frame table: the sums of the atoms ({self.atom_ptr[-1]}) "
+                             f"and of the k-vectors ({int(self._k_ptr[-1])}) must stay below 2^31 and every launch below 2^24 "
+                             "workgroups (the atom launch has sum_f N_f x slices_f)")
+        SN, SK = self.atom_ptr[-1], int(self._k_ptr[-1])
+        new = lambda *shape, dt=dtype: torch.empty(shape, dtype=dt, device=device)  # noqa: E731
+        self._freq = self._mult = self._kvec = self._G = self._Sc = self._Ss = self._dG = None
+        if SK > 0:
+            self._freq = torch.tensor(np.concatenate(f_all), device=device)
+            self._mult = torch.tensor(np.concatenate(m_all), device=device)
+            self._kvec, self._G, self._Sc, self._Ss = new(SK, 3), new(SK), new(SK), new(SK)
+            self._dG = new(SK) if self.cell_gradient else None
+        with torch.no_grad():
+            self.pos = torch.cat([fr[2].detach() for fr in frames]).contiguous()
+            self.q = torch.cat([fr[0].detach() for fr in frames]).contiguous()
+            self.cells = torch.stack([fr[1].detach() for fr in frames]).contiguous()
+        self._rec = new(SN, 4)
+        self.energies, self.forces_flat, self.charge_grads_flat = new(F), new(SN, 3), new(SN, 1)
+        self.cell_grads = new(F, 3, 3) if self.cell_gradient else None
+        self.status = torch.zeros(F, dtype=torch.int32, device=device)
+        self._work = new(max(1, n_work), dt=torch.float64)
+        cut = lambda t: [t[a:b] for a, b in zip(self.atom_ptr[:-1], self.atom_ptr[1:])]  # noqa: E731
+        self.forces, self.charge_grads = cut(self.forces_flat), cut(self.charge_grads_flat)
+        self._warmup = max(1, int(warmup))
+        self._install(self._pack([(fr[3], fr[4]) for fr in frames]))
+
+    @staticmethod
+    def _check_list(f, neighbor_indices, neighbor_shifts):
+        who = f"GraphedEwaldBatch: frame {f}"
+        if neighbor_indices.dim() != 2 or neighbor_indices.shape[1] != 2:
+            raise ValueError(f"{who}: `neighbor_indices` must be a tensor with shape [n_pairs, 2], got tensor with shape "
+                             f"{list(neighbor_indices.shape)}")
+        if neighbor_shifts.dim() != 2 or tuple(neighbor_shifts.shape) != (neighbor_indices.shape[0], 3):
+            raise ValueError(f"{who}: `neighbor_shifts` must be a tensor with shape [n_pairs, 3] with n_pairs = "
+                             f"{neighbor_indices.shape[0]}, got tensor with shape {list(neighbor_shifts.shape)}")
+        if neighbor_shifts.numel() > 0:
+            s = neighbor_shifts.detach()
+            if bool((s != s.round()).any()) or float(s.abs().max()) > 3:
+                raise ValueError(f"{who}: the cell shifts must be integers in [-3, 3] (the 4-byte pair entries of the row kernel); "
+                                 "wrap the positions into the cell or use a shorter cutoff")
+
+    def _pack(self, lists):
+        """Validate and pack F ``(neighbor_indices, neighbor_shifts)`` into the concatenated row pointers and 4-byte entries and
+        build the frame table for them.  Nothing of the object changes: what is returned goes to :meth:`_install`."""
+        who = "GraphedEwaldBatch"
+        lists = [tuple(ls) for ls in lists]
+        if len(lists) != self.n_frames:
+            raise ValueError(f"{who}: {self.n_frames} lists wanted, one (neighbor_indices, neighbor_shifts) per frame, got {len(lists)}")
+        for f, ls in enumerate(lists):
+            if len(ls) != 2:
+                raise ValueError(f"{who}: frame {f}: a list is (neighbor_indices, neighbor_shifts), got {len(ls)} items")
+            self._check_list(f, *ls)
+            for t, name in zip(ls, ("neighbor_indices", "neighbor_shifts")):
+                _lib.require_device(t, f"{name} of frame {f}")
+        rows, ents, keep = [], [], []
+        for f, (idx, shifts) in enumerate(lists):
+            sh = shifts.to(self.dtype).contiguous()
+            topo = ops.get_topology(idx, self.atom_ptr[f + 1] - self.atom_ptr[f])
+            ent32 = topo.compact_entries(sh, shifts)
+            if ent32 is None:
+                raise ValueError(f"{who}: frame {f}: the cell shifts must be integers in [-3, 3] (the 4-byte pair entries of the row "
+                                 "kernel) and the frame at most 2^22 atoms")
+            rows.append(topo.row_ptr)
+            ents.append(ent32)
+            keep.append(topo)
+        entry_ptr = np.concatenate([[0], np.cumsum([e.shape[0] for e in ents])]).astype(np.int64)
+        if int(entry_ptr[-1]) >= (1 << 31):
+            raise ValueError(f"{who}: the lists hold {int(entry_ptr[-1])} entry words, the frame table 2^31 - 1 at most")
+        lib, F, cg = self._lib, self.n_frames, int(self.cell_gradient)
+        n_bytes = int(lib.mipme_ewald_batch_table_bytes(F, self._atom_ptr.ctypes.data, self._k_ptr.ctypes.data, cg))
+        host = np.zeros(n_bytes, dtype=np.uint8)
+        _lib.check(lib.mipme_ewald_batch_table_build(F, self._atom_ptr.ctypes.data, self._k_ptr.ctypes.data, entry_ptr.ctypes.data,
+                                                     self._ns.ctypes.data, cg, host.ctypes.data, n_bytes))
+        with torch.no_grad():
+            row_ptr = torch.cat(rows).to(torch.int32).contiguous()
+            ent32 = torch.cat(ents).contiguous()
+        table = torch.from_numpy(host).to(self.device)  # one upload per capture
+        return [ls[0] for ls in lists], row_ptr, ent32, entry_ptr, table
+
+    def _install(self, packed):
+        self.pairs, self._row_ptr, self._ent32, self._entry_ptr, self._table = packed
+        self.graph = _capture_graph(self.device, self._warm_up, self._launch)
+
+    def _warm_up(self):
+        for _ in range(self._warmup):
+            self._launch()
+
+    def _launch(self):
+        with _lib.on_device(self.device):
+            a = _lib.EwaldBatchArgs(
+                stream=_lib.current_stream(self.device), dtype=self._dt, full_list=int(self.full), pot=C.pointer(self._desc),
+                n_frames=self.n_frames, cell_gradient=int(self.cell_gradient), lr_wavelength=self.lr_wavelength,
+                atom_ptr=self._atom_ptr.ctypes.data, k_ptr=self._k_ptr.ctypes.data, entry_ptr=self._entry_ptr.ctypes.data,
+                device_table=self._table.data_ptr(), positions=self.pos.data_ptr(), charges=self.q.data_ptr(),
+                cells=self.cells.data_ptr(), frequencies=_lib.ptr(self._freq), multiplicities=_lib.ptr(self._mult),
+                row_ptr=self._row_ptr.data_ptr(), entries=self._ent32.data_ptr(), shift_format=2, records=self._rec.data_ptr(),
+                kvectors=_lib.ptr(self._kvec), G=_lib.ptr(self._G), dG=_lib.ptr(self._dG), s_cos=_lib.ptr(self._Sc),
+                s_sin=_lib.ptr(self._Ss), energies=self.energies.data_ptr(), forces=self.forces_flat.data_ptr(),
+                grad_charges=self.charge_grads_flat.data_ptr(), grad_cells=_lib.ptr(self.cell_grads), status=self.status.data_ptr(),
+                work=self._work.data_ptr())
+            _lib.check(self._lib.mipme_ewald_batch(C.byref(a)))
+
+    def _load(self, positions=None, charges=None, cells=None):
+        """Each input given, a flat tensor or a list of F per-frame tensors, into the object's buffer: one copy each."""
+        with torch.no_grad():
+            for buf, new in ((self.pos, positions), (self.q, charges), (self.cells.view(-1, 3), cells)):
+                if new is None:
+                    continue
+                if isinstance(new, (list, tuple)):
+                    if len(new) != self.n_frames:
+                        raise ValueError(f"GraphedEwaldBatch: a list of {self.n_frames} per-frame tensors wanted, got {len(new)}")
+                    if sum(int(t.shape[0]) for t in new) != buf.shape[0]:
+                        raise ValueError(f"GraphedEwaldBatch: the per-frame tensors hold {sum(int(t.shape[0]) for t in new)} rows, the "
+                                         f"buffer {buf.shape[0]}")
+                    torch.cat([t.detach() for t in new], out=buf)
+                else:
+                    buf.copy_(new.detach().reshape(buf.shape))
+
+    def kgrid_matches(self, cells) -> list:
+        """Per frame, whether the eager calculator would sum the frame's k grid for its cell in ``cells`` ((F, 3, 3) or a list):
+        bit 0 of :attr:`status` clear, decided on the host."""
+        if len(cells) != self.n_frames:
+            raise ValueError(f"GraphedEwaldBatch: {self.n_frames} cells wanted, got {len(cells)}")
+        return [GraphedEwaldStep._ns_of(c, self.lr_wavelength) == ns for c, ns in zip(cells, self.ns)]
+
+    def recapture(self, lists, positions=None, charges=None, cells=None) -> None:
+        """New neighbour lists, a sequence of F ``(neighbor_indices, neighbor_shifts)``: pack them, build the frame table again
+        and capture the step again; the k grids and every buffer are kept.  Every list is validated and packed before anything of
+        the object changes: a refused call leaves the object replaying what it replayed."""
+        packed = self._pack(lists)
+        self._load(positions, charges, cells)
+        self._install(packed)
+
+    def __call__(self, positions=None, charges=None, cells=None):
+        """``energies, forces, dE_dq`` (+ ``dE_dcell`` with ``cell_gradient``) of the current -- or the given -- positions, charges
+        and cells of all frames: up to three copies and one graph replay."""
+        self._load(positions, charges, cells)
+        self.graph.replay()
+        out = (self.energies, self.forces, self.charge_grads)
+        if self.cell_gradient:
+            out += (self.cell_grads,)
+        return out
