@@ -430,6 +430,50 @@ typedef struct {
 } mipme_frames_slab_step_args_t;
 int mipme_frames_slab_step(const mipme_frames_slab_step_args_t* args);
 
+/* The cells of a frame batch as a replay input (NPT, cell relaxation, strain scans): ONE launch ahead of the step derives from
+ * the (n_frames, 3, 3) cells the caller wrote on the device everything the step's kernels read of a cell, so that a captured step
+ * follows the cells without a host read and without a new capture.  The mesh dimensions stay what the table was built with.
+ *   mipme_frames_table_cells patches a HOST table (after mipme_frames_table_contract / _slab / _energy_log, before the upload):
+ *     the gather tail of frame f reads status[f] and writes the frame's energy as NaN when bit 1 is set.  status: int32[n_frames]
+ *     on the device; NULL takes the hook off again.  Refused: a frame without use_tail.
+ *   mipme_frames_cells makes the launch, grid (ceil(Mh / 256), n_frames), Mh = nx ny (nz/2 + 1).  Per frame it inverts the cell in
+ *     float64 and writes status[f]: bit 0 = the mesh rule 2^ceil(log2(2 |a_d| / mesh_spacing + 1)) would give another mesh than the
+ *     frozen one (the step still runs, at the frozen mesh); bit 1 = the cell is bad: its determinant is zero (to within the rounding error of
+ *     its evaluation, 32 eps |a||b||c|: two equal rows) or not finite, or a
+ *     value the launch would store (the cell, its inverse, 1 / |det| in the batch's dtype, the volume, the row norms) is not finite.
+ *     A bad cell changes NOTHING else: table, cells_valid and the filter tables keep the last valid cell, the frame's energy comes
+ *     out as NaN and its other outputs are those of that last valid geometry (invalid).  A good cell patches the uploaded table --
+ *     the inverse cell of the binning and spread records, 1 / V, the mesh (cell, inverse, volume) of the cell-gradient record, the
+ *     slab term's 4 pi prefactor / V and |a_axis| -- writes the frame's slice of cells_valid (mipme_frame_t.cell must point there:
+ *     the pair rows never read the input buffer) and rebuilds the frame's slices of G and, if given, G_deriv with the device
+ *     functions of mipme_kfilter_build / mipme_kfilter_build_deriv.  G_stride >= Mh and G_deriv_stride >= 4 Mh: no shared tables.
+ *     Refused with MIPME_EINVAL before the launch: a wrong size or version, NULL buffers, what mipme_frames_step refuses of the
+ *     frames, a frame without use_tail or whose cell does not point into cells_valid, a mesh_spacing that is not positive.
+ *   mipme_frames_cell_geometry is the launch's inversion, validity and bit-0 rule for ONE cell on the host (no device): cell as
+ *     float64, rounded to float first for MIPME_F32; inv_out (row-major inverse) and inv_vol_out are nullable. */
+int mipme_frames_table_cells(int dtype, int n_frames, const mipme_frame_t* frames, void* host_table, int64_t host_table_bytes,
+                             void* status);
+#define MIPME_FRAMES_CELLS_VERSION 1
+typedef struct mipme_frames_cells_args {
+  uint32_t size, version;   /* sizeof(mipme_frames_cells_args_t), MIPME_FRAMES_CELLS_VERSION */
+  void* stream;
+  int32_t dtype, n_frames;
+  const mipme_frame_t* frames;
+  const mipme_potential_t* pot;
+  void* device_table;       /* the uploaded table: the launch patches it */
+  const void* cells;        /* (n_frames, 3, 3) in the working dtype: the input, read by this launch alone */
+  void* cells_valid;        /* (n_frames, 3, 3): the last valid cell of every frame */
+  void* G;                  /* n_frames filter tables, G_stride reals apart */
+  int64_t G_stride;
+  void* G_deriv;            /* nullable (with its stride): n_frames derivative tables, G_deriv_stride reals apart */
+  int64_t G_deriv_stride;
+  double mesh_spacing;      /* of the mesh rule (status bit 0) */
+  void* status;             /* int32[n_frames] */
+} mipme_frames_cells_args_t;
+int mipme_frames_cells(const mipme_frames_cells_args_t* args);
+int mipme_frames_cell_geometry(const double cell[9], int dtype, const int32_t ns[3], double mesh_spacing, double inv_out[9],
+                               double* inv_vol_out, int32_t* status_out);
+
 int mipme_fft_plan_xfused(const mipme_fft_plan* plan);
 
 /* Adjoint of mipme_kspace_forward for an upstream gradient g = dL/d(out_lr), shape (N,C).

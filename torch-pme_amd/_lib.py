@@ -36,6 +36,7 @@ EXPORTS = (
     "mipme_frames_table_bytes", "mipme_frames_table_build", "mipme_frames_forward", "mipme_frames_backward",
     "mipme_frames_cell_work", "mipme_frames_table_contract", "mipme_frames_step",
     "mipme_frames_slab_work", "mipme_frames_table_slab", "mipme_frames_slab_step",
+    "mipme_frames_table_cells", "mipme_frames_cells", "mipme_frames_cell_geometry",
     "mipme_scaled_match", "mipme_scaled_match_work", "mipme_scaled_match_wide", "mipme_md_supported", "mipme_md_lists_ints", "mipme_md_rebin", "mipme_md_step", "mipme_set_skip_flag", "mipme_energy_select", "mipme_energy_select_sum", "mipme_energy_select_contract",
     "mipme_kfilter_build_deriv", "mipme_cell_tail_work", "mipme_values_equal", "mipme_checksum", "mipme_checksum_words",
     "mipme_spread_jet", "mipme_gather_jet", "mipme_gather_jet3", "mipme_pair_sum", "mipme_pair_sum_rows", "mipme_pair_dot", "mipme_pair_diff", "mipme_pair_scatter",
@@ -280,6 +281,28 @@ class FramesStepArgs(_VersionedArgs):
         C.Structure.__init__(self, size=C.sizeof(type(self)), version=FRAMES_STEP_VERSION, **fields)
 
 
+FRAMES_CELLS_VERSION = 1
+
+
+class FramesCellsArgs(_VersionedArgs):
+    """``mipme_frames_cells_args_t`` (version ``MIPME_FRAMES_CELLS_VERSION``): the launch that turns the cells of a frame batch, as
+    they stand on the device, into the geometry of its table, its filter tables and the validated copy of the cells"""
+
+    _fields_ = [
+        ("size", C.c_uint32), ("version", C.c_uint32),
+        ("stream", C.c_void_p), ("dtype", C.c_int32), ("n_frames", C.c_int32),
+        ("frames", C.POINTER(Frame)), ("pot", C.POINTER(PotentialDesc)), ("device_table", C.c_void_p),
+        ("cells", C.c_void_p), ("cells_valid", C.c_void_p), ("G", C.c_void_p), ("G_stride", C.c_int64),
+        ("G_deriv", C.c_void_p), ("G_deriv_stride", C.c_int64), ("mesh_spacing", C.c_double), ("status", C.c_void_p),
+    ]
+
+    def __init__(self, **fields):
+        unknown = set(fields) - {name for name, _ in self._fields_}
+        if unknown:
+            raise TypeError(f"{type(self).__name__}: unknown field(s) {sorted(unknown)}")
+        C.Structure.__init__(self, size=C.sizeof(type(self)), version=FRAMES_CELLS_VERSION, **fields)
+
+
 FRAMES_SLAB_STEP_VERSION = 1
 
 
@@ -491,6 +514,10 @@ def _declare(lib):
         "mipme_frames_step": [C.POINTER(FramesStepArgs)],
         "mipme_frames_table_slab": [ci, ci, C.POINTER(Frame), PP, vp, i64, C.POINTER(C.c_int32), vp, i64],
         "mipme_frames_slab_step": [C.POINTER(FramesSlabStepArgs)],
+        "mipme_frames_table_cells": [ci, ci, C.POINTER(Frame), vp, i64, vp],
+        "mipme_frames_cells": [C.POINTER(FramesCellsArgs)],
+        "mipme_frames_cell_geometry": [C.POINTER(dbl), ci, C.POINTER(C.c_int32), dbl, C.POINTER(dbl), C.POINTER(dbl),
+                                       C.POINTER(C.c_int32)],
         "mipme_scaled_match": [vp, ci, i64, vp, vp, vp, vp],
         "mipme_scaled_match_work": [i64],
         "mipme_scaled_match_wide": [vp, ci, i64, vp, vp, vp, vp, vp],

@@ -1,11 +1,12 @@
 // What the Ewald step (ewald_step.hip) and its batched form (ewald_batch.hip) share: the block shapes, the slice rule of the atom
-// kernel, the layout of the float64 work area of ONE system, the fixed-order strided sum and the float64 cell inversion.  The
+// kernel, the layout of the float64 work area of ONE system, the fixed-order strided sum and the float64 cell inversion (cell_invert.h).  The
 // batch lays the work areas of its frames one behind the other, each exactly as the single step lays out its own.
 #pragma once
 
 #include <algorithm>
 #include <cstdint>
 
+#include "cell_invert.h"  // es_invert_cell: the float64 cell inversion
 #include "host.h"
 #include "rows_body.h"
 
@@ -68,31 +69,6 @@ __device__ __forceinline__ double es_strided_sum(const double* __restrict__ p, i
   double s = 0.0;
   for (int64_t b = threadIdx.x; b < n; b += kEsBlock) s += p[b * stride + off];
   return block_sum<kEsWaves>(s, red);
-}
-
-// A^-T (rows b x c / det, c x a / det, a x b / det), 1 / |det| and "det is zero or not finite" of the cell, in float64
-struct EsCell {
-  double recip[9], inv_vol;
-  bool bad;
-};
-template <typename T>
-__device__ __forceinline__ EsCell es_invert_cell(const T* __restrict__ cell, double (&A)[9]) {
-#pragma unroll
-  for (int k = 0; k < 9; ++k) A[k] = double(cell[k]);
-  EsCell g;
-  const double* a = A;
-  const double* b = A + 3;
-  const double* c = A + 6;
-  g.recip[0] = b[1] * c[2] - b[2] * c[1], g.recip[1] = b[2] * c[0] - b[0] * c[2], g.recip[2] = b[0] * c[1] - b[1] * c[0];
-  g.recip[3] = c[1] * a[2] - c[2] * a[1], g.recip[4] = c[2] * a[0] - c[0] * a[2], g.recip[5] = c[0] * a[1] - c[1] * a[0];
-  g.recip[6] = a[1] * b[2] - a[2] * b[1], g.recip[7] = a[2] * b[0] - a[0] * b[2], g.recip[8] = a[0] * b[1] - a[1] * b[0];
-  const double det = a[0] * g.recip[0] + a[1] * g.recip[1] + a[2] * g.recip[2];
-  g.bad = !(det != 0.0) || !isfinite(det);
-  const double inv_det = 1.0 / det;
-#pragma unroll
-  for (int k = 0; k < 9; ++k) g.recip[k] *= inv_det;
-  g.inv_vol = fabs(inv_det);
-  return g;
 }
 
 }  // namespace mipme

@@ -125,7 +125,7 @@ static bool frame_plane_lists(const mipme_frame_t& f, int dtype) {
 }
 int64_t frames_counter_ints(const mipme_mesh_t* m, int64_t n_atoms, int dtype) { return frame_counter_ints(m, n_atoms, dtype); }
 
-static int frames_check(int dtype, int n_frames, const mipme_frame_t* fr) {
+int frames_check(int dtype, int n_frames, const mipme_frame_t* fr) {  // (frames_device.h: frames_cells.hip's entry point calls it too)
   MIPME_REQUIRE(n_frames > 0 && fr, "no frames");
   MIPME_REQUIRE(dtype == MIPME_F32 || dtype == MIPME_F64, "invalid dtype %d", dtype);
   const mipme_mesh_t& m0 = fr[0].mesh;
@@ -235,13 +235,6 @@ static int frames_table_build_t(int n_frames, const mipme_frame_t* fr, const mip
     out[k] = d;
   }
   return MIPME_OK;
-}
-
-// the frames table: n_frames FrameDev<T>, then n_frames FrameCellRec (filled by mipme_frames_table_contract, zero otherwise)
-template <typename T>
-static FrameCellRec* frames_cell_recs(const void* table, int n_frames) {
-  static_assert(sizeof(FrameDev<T>) % 8 == 0, "the cell records follow the frame records");
-  return (FrameCellRec*)((char*)const_cast<void*>(table) + size_t(n_frames) * sizeof(FrameDev<T>));
 }
 
 // cell_work (nullable): the batch's cell gradient -- the CELL instantiations of the pair sum, the x stage's store of w, and behind
@@ -630,6 +623,50 @@ int mipme_frames_forward(mipme_fft_plan* plan, void* stream, int dtype, int n_fr
   a.device_table = device_table, a.G = G, a.G_stride = G_stride;
   a.rho_mesh_all = rho_mesh_all, a.hat_work_all = hat_work_all, a.phi_mesh_all = phi_mesh_all, a.dc_all = dc_all;
   return frames_launch("mipme_frames_forward", a, nullptr, false, [] { return int(MIPME_OK); });
+}
+
+int mipme_frames_table_cells(int dtype, int n_frames, const mipme_frame_t* frames, void* host_table, int64_t host_table_bytes,
+                             void* status) {
+  int rc = frames_check(dtype, n_frames, frames);
+  if (rc) return rc;
+  MIPME_REQUIRE(host_table && host_table_bytes >= mipme_frames_table_bytes(dtype, n_frames),
+                "invalid arguments to mipme_frames_table_cells");
+  for (int k = 0; k < n_frames && status; ++k)
+    MIPME_REQUIRE(frames[k].use_tail, "frame %d: the status of a cell rides on the gather tail (mipme_frame_t.use_tail)", k);
+  DT_SWITCH(dtype, frames_table_cells_t<float>(n_frames, host_table, status), frames_table_cells_t<double>(n_frames, host_table, status));
+}
+
+int mipme_frames_cells(const mipme_frames_cells_args_t* a) {
+  MIPME_REQUIRE(a, "NULL argument struct passed to mipme_frames_cells");
+  MIPME_REQUIRE(a->size == sizeof(mipme_frames_cells_args_t), "mipme_frames_cells_args_t: size %u, this library expects %zu", a->size,
+                sizeof(mipme_frames_cells_args_t));
+  MIPME_REQUIRE(a->version == MIPME_FRAMES_CELLS_VERSION, "mipme_frames_cells_args_t: version %u, this library expects %d", a->version,
+                MIPME_FRAMES_CELLS_VERSION);
+  int rc = frames_check(a->dtype, a->n_frames, a->frames);
+  if (rc) return rc;
+  MIPME_REQUIRE(a->pot && a->device_table && a->cells && a->cells_valid && a->G && a->status, "NULL buffer passed to mipme_frames_cells");
+  MIPME_REQUIRE(a->mesh_spacing > 0 && std::isfinite(a->mesh_spacing), "mipme_frames_cells: mesh_spacing must be positive, got %g",
+                a->mesh_spacing);
+  const mipme_mesh_t* m = &a->frames[0].mesh;
+  const int64_t Mh = int64_t(m->nx) * m->ny * (m->nz / 2 + 1);
+  // every frame writes its own slice of the tables: a shared table (stride 0) cannot follow several cells
+  MIPME_REQUIRE(a->G_stride >= Mh, "mipme_frames_cells: G_stride = %lld is below the half grid's %lld points", (long long)a->G_stride,
+                (long long)Mh);
+  MIPME_REQUIRE(!a->G_deriv || a->G_deriv_stride >= 4 * Mh, "mipme_frames_cells: G_deriv_stride = %lld is below 4 x %lld",
+                (long long)a->G_deriv_stride, (long long)Mh);
+  const size_t real = a->dtype == MIPME_F32 ? 4 : 8;
+  for (int k = 0; k < a->n_frames; ++k) {
+    MIPME_REQUIRE(a->frames[k].use_tail, "frame %d: the status of a cell rides on the gather tail (mipme_frame_t.use_tail)", k);
+    // the pair rows read the validated copy, never the input buffer
+    MIPME_REQUIRE(a->frames[k].cell == (const char*)a->cells_valid + size_t(k) * 9 * real,
+                  "frame %d: mipme_frame_t.cell must point at the frame's slice of cells_valid", k);
+  }
+  hipStream_t st = (hipStream_t)a->stream;
+  DT_SWITCH(a->dtype,
+            frames_cells_launch<float>(st, a->n_frames, m, a->pot, a->device_table, a->cells, a->cells_valid, a->G, a->G_stride, a->G_deriv,
+                                       a->G_deriv_stride, a->mesh_spacing, a->status),
+            frames_cells_launch<double>(st, a->n_frames, m, a->pot, a->device_table, a->cells, a->cells_valid, a->G, a->G_stride, a->G_deriv,
+                                        a->G_deriv_stride, a->mesh_spacing, a->status));
 }
 
 int64_t mipme_frames_counter_ints(const mipme_mesh_t* mesh, int64_t n_atoms, int dtype) {

@@ -38,6 +38,23 @@ struct FrameDev {
   bool use_tail;
 };
 
+// the frames table: n_frames FrameDev<T>, then n_frames FrameCellRec (filled by mipme_frames_table_contract, zero otherwise)
+template <typename T>
+inline FrameCellRec* frames_cell_recs(const void* table, int n_frames) {
+  static_assert(sizeof(FrameDev<T>) % 8 == 0, "the cell records follow the frame records");
+  return (FrameCellRec*)((char*)const_cast<void*>(table) + size_t(n_frames) * sizeof(FrameDev<T>));
+}
+
+// frames.hip: what every entry point of the frame batches refuses of its frames before anything else
+int frames_check(int dtype, int n_frames, const mipme_frame_t* fr);
+
+// frames_cells.hip: the cells of a batch as a replay input -- the status word of every frame on its gather tail (host table), and
+// the ONE launch that turns the cells on the device into the table's geometry fields, the filter tables and the validated copy
+template <typename T> int frames_table_cells_t(int n_frames, void* host_table, void* status);
+template <typename T> int frames_cells_launch(hipStream_t st, int n_frames, const mipme_mesh_t* m, const mipme_potential_t* pot,
+                                              void* device_table, const void* cells_in, void* cells_valid, void* G, int64_t G_stride,
+                                              void* G_deriv, int64_t G_deriv_stride, double mesh_spacing, void* status);
+
 // frames_cell.hip: the co-scheduled launches of a batch whose pair sum also forms the cell sums (FusedRowsArgs::cpart of every
 // frame; 4-byte entries, 1/r or 1/r^6: rows_cell_supported) -- the plane route and the brick route
 template <typename T> int frames_cell_plane_rows(hipStream_t st, int scheme, int order, int pfast, dim3 grid, size_t lds,

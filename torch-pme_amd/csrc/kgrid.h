@@ -86,4 +86,67 @@ __device__ inline double kgrid_point(const KGeom& g, int64_t p, double& inv_u2, 
   return k2;
 }
 
+struct KPoint {
+  double k[3];
+  int f[3];
+  double G, dGdk[3], dGdh[3];
+  // dG/dk_c = alpha k_c - beta_c h_c,  dG/dh_c = -beta_c k_c: the four values per k-point the derivative table keeps
+  double alpha, beta[3];
+};
+
+// Filter value and derivatives at the k-point (ix, iy, iz): the cell gradient's k-grid sums and the derivative table.  (The
+// table G itself needs none of the derivatives: kfilter_kernel, from kgrid_point of kgrid.h.)
+__device__ inline void eval_point(const KGeom& g, const KPot& kp, int ix, int iy, int iz, KPoint& o) {
+  o.f[0] = fft_freq(ix, g.nx);
+  o.f[1] = fft_freq(iy, g.ny);
+  o.f[2] = iz;
+  const double k2 = kvector_dev(g.inv, o.f, o.k);
+  double v, dv;
+  lr_kernel_dev(kp, k2, v, dv);
+  if (g.scheme == MIPME_LAGRANGE) {
+    o.G = v;
+    o.alpha = 2.0 * dv;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      o.dGdk[c] = 2.0 * o.k[c] * dv;
+      o.dGdh[c] = 0.0;
+      o.beta[c] = 0.0;
+    }
+    return;
+  }
+  // the sinc product of p3m_inv_u2 (kgrid.h) with ONE sincos per axis, the cosine being wanted too: the double-precision sin / cos
+  // of libm are ~250 instructions each, and the cell-gradient sums of the x stage evaluate this for every k-point of the half
+  // grid -- most of that kernel's extra 19 us
+  double s = 1.0, t[3], sn[3], cs[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    t[c] = 0.5 * o.k[c] * g.h[c];
+    sincos(t[c], &sn[c], &cs[c]);
+    s *= (t[c] == 0.0) ? 1.0 : sn[c] / t[c];
+  }
+  double U2 = 1.0;
+  const double s2 = s * s;
+  for (int i = 0; i < g.order; ++i) U2 *= s2;
+  if (U2 == 0.0) {
+    o.G = 0.0;
+    o.alpha = 0.0;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) o.dGdk[c] = o.dGdh[c] = o.beta[c] = 0.0;
+    return;
+  }
+  const double inv = 1.0 / U2;
+  o.G = v * inv;
+  o.alpha = 2.0 * dv * inv;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const double tc = t[c];
+    // d/dt ln(sin t / t) = cot t - 1/t
+    const double L = fabs(tc) < 1e-4 ? (-tc / 3.0 - tc * tc * tc / 45.0) : (cs[c] / sn[c] - 1.0 / tc);
+    const double w = o.G * double(2 * g.order) * L;
+    o.dGdk[c] = 2.0 * o.k[c] * dv * inv - w * 0.5 * g.h[c];
+    o.dGdh[c] = -w * 0.5 * o.k[c];
+    o.beta[c] = 0.5 * w;
+  }
+}
+
 }  // namespace mipme

@@ -587,10 +587,23 @@ class GraphedFrameBatch:
         must be 1/r with a smearing.  The batch takes explicit pair lists, so ``periodic`` has no list to shape: it is refused
         without ``slab_correction=True``.  A batch whose frames are all fully periodic is built and launched as without the
         keywords
+    :param follow_cells: the cells become a replay input (NPT, cell relaxation, strain scans, finite-difference stress): the batch
+        owns ``self.cells`` (F, 3, 3) -- the input buffer --, a private validated copy that the pair rows read, and ``self.status``
+        (F,) int32.  ``batch(positions, cells=...)`` copies the cells in, makes ONE launch (``mipme_frames_cells``: it inverts
+        every cell in float64, patches the geometry of the device-resident table and rebuilds every frame's G(k) and derivative
+        table) and replays the unchanged graph: no host read, nothing captured again.  ``update_cells()`` makes the launch alone,
+        for callers whose own kernel (a barostat) wrote into ``self.cells``.  The mesh dimensions stay those of the construction
+        (``self.ns``): ``dE/dcell`` is "at fixed Cartesian positions, at the frozen mesh", which is what makes E a smooth function
+        of the cell.  ``status[f]`` bit 0: the mesh rule would give frame f another mesh at its present cell (results are still
+        those of the frozen mesh; build a new batch when the accuracy matters; :meth:`mesh_matches` decides the same on the host).
+        Bit 1: the cell is singular or not finite -- the frame keeps the geometry of its last valid cell, its energy comes out as
+        NaN and its other outputs are invalid; the next valid cell recovers it.  The neighbour lists stay the caller's business
+        (their skin has to cover the strain).  A batch of one frame is the variable-cell form of :class:`GraphedEnergyForces`
     """
 
     def __init__(self, calculator, frames, warmup: int = 2, store_distances: bool = False, energy_log=None, epilogue=None,
-                 charge_gradient: bool = False, cell_gradient: bool = False, periodic=None, slab_correction: bool = False):
+                 charge_gradient: bool = False, cell_gradient: bool = False, periodic=None, slab_correction: bool = False,
+                 follow_cells: bool = False):
         _refuse_spline(calculator, "GraphedFrameBatch")
         frames = list(frames)
         slab = self._slab_codes(calculator, len(frames), periodic, slab_correction)
@@ -634,12 +647,19 @@ class GraphedFrameBatch:
         self._frames = (_lib.Frame * F)()
         self._minus_one = torch.full((F,), -1.0, dtype=dtype, device=device)
         self._grad_pos, self.distances = [], []
+        self.follow_cells = bool(follow_cells)
+        self.cells = self.status = self._cells_valid = None
+        if self.follow_cells:
+            #: (F, 3, 3): the cells the next ``update_cells()`` / ``batch(cells=...)`` evaluates; ``status``: (F,) int32, see the class
+            self.cells = torch.stack([cell.detach().to(dtype).reshape(3, 3) for _, cell, _, _, _ in frames]).contiguous()
+            self._cells_valid = self.cells.clone()  # what the pair rows read: written by the cells launch, for valid cells only
+            self.status = torch.zeros((F,), dtype=torch.int32, device=device)
         compact_ok, ent_streams = True, []
         for k, (q, cell, pos, pairs, shifts) in enumerate(frames):
             N, P = pos.shape[0], pairs.shape[0]
             p = pos.detach().clone().contiguous().requires_grad_(True)
             qc = q.detach().reshape(-1).contiguous()
-            cl = cell.detach().to(dtype).contiguous()
+            cl = self._cells_valid[k] if self.follow_cells else cell.detach().to(dtype).contiguous()
             sh = shifts.to(dtype).contiguous()
             topo = ops.get_topology(pairs, N)
             ent_sh, fmt = topo.entries_with_shifts(sh, shifts, table=True)
@@ -727,7 +747,11 @@ class GraphedFrameBatch:
         if self.energy_log is not None:  # every frame's gather tail also writes its slot of the log (no extra launch)
             _lib.check(lib.mipme_frames_table_energy_log(dt, F, host.ctypes.data, nbytes, self.energy_log.values.data_ptr(),
                                                          self.energy_log.cursor.data_ptr(), self.energy_log.capacity))
+        if self.follow_cells:  # the status word of every frame on its gather tail (bit 1: the energy becomes NaN)
+            _lib.check(lib.mipme_frames_table_cells(dt, F, self._frames, host.ctypes.data, nbytes, self.status.data_ptr()))
         self._table = torch.from_numpy(host).to(device)
+        if self.follow_cells:  # from the first replay on the tables are a function of `self.cells` alone
+            self.update_cells()
 
         def warm_up():  # (plans, lazy module loads)
             for _ in range(max(1, warmup)):
@@ -804,11 +828,68 @@ class GraphedFrameBatch:
         E.backward(self._minus_one)  # seeded with -1: positions.grad are the forces
         return E
 
-    def __call__(self, positions=None):
+    def _need_follow_cells(self, what):
+        if not self.follow_cells:
+            raise ValueError(f"GraphedFrameBatch: {what} needs a batch built with follow_cells=True (this one keeps the cells it was "
+                             f"built with)")
+
+    def _checked_cells(self, cells):
+        """``cells`` as the (F, 3, 3) tensor or the list of F (3, 3) tensors ``torch.stack(..., out=self.cells)`` takes; refused by
+        ``ValueError`` before anything changes."""
+        F = self.n_frames
+        seq = [cells] if torch.is_tensor(cells) else list(cells)
+        if not torch.is_tensor(cells) and len(seq) != F:
+            raise ValueError(f"GraphedFrameBatch: `cells` must hold one (3, 3) tensor per frame ({F}), got {len(seq)}")
+        want = (F, 3, 3) if torch.is_tensor(cells) else (3, 3)
+        for c in seq:
+            if not torch.is_tensor(c) or tuple(c.shape) != want or c.dtype != self.dtype or c.device != self.cells.device:
+                got = (tuple(c.shape), c.dtype, str(c.device)) if torch.is_tensor(c) else type(c).__name__
+                raise ValueError(f"GraphedFrameBatch: `cells` must be a {(F, 3, 3)} tensor or {F} tensors of shape (3, 3), dtype "
+                                 f"{self.dtype} on {self.cells.device}; got {got}")
+        return cells if torch.is_tensor(cells) else seq
+
+    def update_cells(self) -> None:
+        """Make the tables of the batch those of ``self.cells`` as it stands on the device (one launch on the current stream; no
+        host read).  ``batch(cells=...)`` calls it; call it yourself after writing into ``self.cells`` in place."""
+        self._need_follow_cells("update_cells()")
+        a = self.__dict__.get("_cells_args")
+        if a is None:  # (every pointer in it is a buffer of the object: built once, only the stream is per call)
+            G_deriv = self._G_deriv if self.cell_gradient else None
+            a = self._cells_args = _lib.FramesCellsArgs(
+                dtype=self._dt, n_frames=self.n_frames, frames=self._frames, pot=C.pointer(self._pot),
+                device_table=self._table.data_ptr(), cells=self.cells.data_ptr(), cells_valid=self._cells_valid.data_ptr(),
+                G=self._G.data_ptr(), G_stride=self._G.shape[1], G_deriv=_lib.ptr(G_deriv),
+                G_deriv_stride=0 if G_deriv is None else G_deriv.shape[1], mesh_spacing=float(self.calc.mesh_spacing),
+                status=self.status.data_ptr())
+        with _lib.on_device(self.device):
+            a.stream = _lib.current_stream(self.device)
+            _lib.check(_lib.load().mipme_frames_cells(C.byref(a)))
+
+    def mesh_matches(self, cells=None) -> list:
+        """Per frame: would the mesh rule give the frozen mesh ``self.ns`` at these cells (default: ``self.cells``)?  Decided on
+        the host (this reads the cells back); ``status`` bit 0 says the same on the device."""
+        if cells is None:
+            self._need_follow_cells("mesh_matches() without `cells`")
+            cells = self.cells
+        host = [torch.as_tensor(c).detach().to("cpu", torch.float64).numpy() for c in cells]
+        if len(host) != self.n_frames:
+            raise ValueError(f"GraphedFrameBatch: `cells` must hold one cell per frame ({self.n_frames}), got {len(host)}")
+        return [tuple(ops.ns_mesh_from_cell(c, self.calc.mesh_spacing)) == tuple(self.ns) for c in host]
+
+    def __call__(self, positions=None, cells=None):
+        if cells is not None:
+            self._need_follow_cells("`cells=`")
+            cells = self._checked_cells(cells)
         if positions is not None:
             with torch.no_grad():
                 for buf, new in zip(self.pos, positions):
                     buf.copy_(new)
+        if cells is not None:
+            if torch.is_tensor(cells):
+                self.cells.copy_(cells)
+            else:
+                torch.stack(cells, out=self.cells)
+            self.update_cells()
         self.calc.check()  # a NaN a previous replay met (pinned word, no synchronisation)
         self.graph.replay()
         out = (self.energies, self.forces)
