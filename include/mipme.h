@@ -553,6 +553,10 @@ const char* mipme_last_cosched_kernel(void);
 int mipme_last_slot_fill(void);
 /* Cell-gradient rider workgroups on that same launch (0: none, or no deferred slot fill in the last forward call). */
 int mipme_last_cell_riders(void);
+/* Whether the last gather launch of the calling thread -- or the last one captured into a graph -- took a brick's atoms in
+ * rounds of two per lane group (1: gather + energy + forces launches of orders up to 5 on dense bricks, at most two workgroups
+ * per CU in fp32; MIPME_GATHER_PAIRS, docs/SWITCHES.md) or one by one (0: every other gather).  Same numbers either way. */
+int mipme_last_gather_pairs(void);
 /* Workgroups per x plane of the PLANE SPREAD that mipme_kspace_forward uses for this mesh / system when the caller sets
  * MIPME_FWD_RHO_MESH_UNUSED and rho_hat == NULL (0: the owner-computes bricks + the forward plane launch): single channel,
  * power-of-two nx, ny, nz, planes whose accumulation tile fits a workgroup's LDS, dense bricks, not MIPME_DETERMINISTIC.  For

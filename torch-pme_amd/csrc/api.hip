@@ -20,6 +20,8 @@ static thread_local int g_last_slot_fill = 0;
 void note_slot_fill(int rider_atoms) { g_last_slot_fill = rider_atoms; }
 static thread_local int g_last_cell_riders = 0;
 void note_cell_riders(int n) { g_last_cell_riders = n; }
+static thread_local int g_last_gather_pairs = 0;
+void note_gather_pairs(int paired) { g_last_gather_pairs = paired; }
 void set_error(const char* fmt, ...) {
   va_list ap;
   va_start(ap, fmt);
@@ -997,6 +999,7 @@ extern "C" {
 const char* mipme_last_error(void) { return g_error; }
 const char* mipme_last_cosched_kernel(void) { return g_last_cosched; }
 int mipme_last_slot_fill(void) { return g_last_slot_fill; }
+int mipme_last_gather_pairs(void) { return g_last_gather_pairs; }
 int mipme_last_cell_riders(void) { return g_last_cell_riders; }
 int mipme_version(void) { return MIPME_VERSION; }
 

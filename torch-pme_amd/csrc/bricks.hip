@@ -353,11 +353,25 @@ bool sr_job_fusable(const mipme_sr_job_t* job) {
   return pfast == 1 || pfast == 6;
 }
 
+// MIPME_GATHER_PAIRS (default 1; 0: the gather tail's loop of one atom per lane group everywhere; read once per process)
+static bool gather_pairs_setting() {
+  static const bool on = env_flag("MIPME_GATHER_PAIRS", true);
+  return on;
+}
+// ... and the launch has room for the paired build's registers: in fp32 it is held to 128 = the two workgroups per CU of the loop
+// build (and gather_pairs_fit keeps it to launches of at most 512 bricks); in fp64 it takes 160-198 = ONE workgroup per CU where
+// the loop build of order 4 has two, so only launches that are one generation at that residency take it (the ionic presets: 64)
+template <typename T>
+static bool gather_pairs_room(int nb) {
+  return sizeof(T) == 4 || nb <= 256;
+}
+
 // tail (nullable): energy + force assembly in the same launch (needs field, accumulate, a single channel)
 template <typename T>
 int gather_bricks(hipStream_t st, const mipme_mesh_t* m, int64_t N, void* bins, const void* mesh, const void* q,
                   const void* qsum, double self_c, double bg_c, void* out, void* raw, int accumulate, void* field,
                   const GatherTailHost* th, void* nan_flag, int* live) {
+  note_gather_pairs(0);
   if (N == 0) return MIPME_OK;
   const int dtype = dtype_of<T>();
   const Geom g = make_geom(m);
@@ -379,10 +393,22 @@ int gather_bricks(hipStream_t st, const mipme_mesh_t* m, int64_t N, void* bins, 
     // the slab term: the same kernels compiled with it (SLAB), so that the launches without it carry no branch for it
     const bool slab = th->slab != 0;
     MIPME_REQUIRE(!slab || (tail.rec4 && tail.slab_mom), "the slab term of the gather needs the atom records and the moments");
-#define MIPME_GATHER_TAIL_LAUNCH(THREADS_V, DENSE_V, SLAB_V)                                                                       \
-  gather_tail_kernel<N, T, THREADS_V, DENSE_V, SLAB_V><<<brick_grid(bg), THREADS_V, 0, st>>>(                                       \
+#define MIPME_GATHER_TAIL_LAUNCH_P(THREADS_V, DENSE_V, SLAB_V, PAIRED_V)                                                           \
+  gather_tail_kernel<N, T, THREADS_V, DENSE_V, SLAB_V, PAIRED_V><<<brick_grid(bg), THREADS_V, 0, st>>>(                             \
       g, bg, v.idx, v.rec, (const T*)v.wts, (const T*)mesh, (const T*)q, (const T*)qsum, T(1.0 / m->volume), T(self_c), T(bg_c), \
       (T*)out, (T*)raw, (T*)field, tail, (int*)nan_flag)
+    // rounds of two atoms per lane group where the instantiation has them (gather_pairs_fit) and MIPME_GATHER_PAIRS allows
+#define MIPME_GATHER_TAIL_LAUNCH(THREADS_V, DENSE_V, SLAB_V)                          \
+  do {                                                                                \
+    if constexpr (gather_pairs_fit<N, T, THREADS_V, DENSE_V>()) {                     \
+      if (gather_pairs_setting() && gather_pairs_room<T>(bg.nb)) {                    \
+        MIPME_GATHER_TAIL_LAUNCH_P(THREADS_V, DENSE_V, SLAB_V, true);                 \
+        note_gather_pairs(1);                                                         \
+        break;                                                                        \
+      }                                                                               \
+    }                                                                                 \
+    MIPME_GATHER_TAIL_LAUNCH_P(THREADS_V, DENSE_V, SLAB_V, false);                    \
+  } while (0)
     if (sparse_bricks(N, bg.nb))
       MIPME_DISPATCH_STENCIL_B(m->scheme, m->order, ((void)S, [&] {
         if (slab)
@@ -408,6 +434,7 @@ int gather_bricks(hipStream_t st, const mipme_mesh_t* m, int64_t N, void* bins, 
           MIPME_GATHER_TAIL_LAUNCH(GATHER_THREADS, false, false);
       }()));
 #undef MIPME_GATHER_TAIL_LAUNCH
+#undef MIPME_GATHER_TAIL_LAUNCH_P
     MIPME_LAUNCH_CHECK();
     return MIPME_OK;
   }

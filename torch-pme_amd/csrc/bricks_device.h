@@ -1758,12 +1758,36 @@ static inline bool sparse_bricks(int64_t n_atoms, int nb) {
   return force || (n_atoms <= int64_t(kSparseBrickAtoms) * nb && nb >= kSparseMinBricks);
 }
 
-template <int N, int NT, typename T, int THREADS = GATHER_THREADS>
+// BATCH (one tile, at most 4 elements per thread): every load of the thread is issued before the first LDS store.  The loop
+// below waits for each element before it stores it (s_waitcnt vmcnt(0) per turn: the turns are not unrolled), which makes the
+// staging of a 12^3 tile by 512 threads FOUR memory trips in a row where one will do -- the mesh was written by other XCDs in
+// the launch before: every one of them goes to the Infinity Cache (profiles/gather_pairs.txt).  Same elements, same places.
+template <int N, int NT, typename T, int THREADS = GATHER_THREADS, bool BATCH = false>
 __device__ __forceinline__ void load_tiles(const Geom& g, int ox, int oy, int oz, const T* __restrict__ m0,
                                            const T* __restrict__ m1, T* tile) {
   constexpr int TL = BRICK + N - 1;
   constexpr int s0 = stencil_start<N>();
   const int64_t plane = int64_t(g.ny) * g.nz;
+  constexpr int TURNS = (TL * TL * TL + THREADS - 1) / THREADS;
+  if constexpr (BATCH && NT == 1 && TURNS <= 4) {
+    T v[TURNS];
+#pragma unroll
+    for (int i = 0; i < TURNS; ++i) {
+      const int k = int(threadIdx.x) + i * THREADS;
+      v[i] = T(0);
+      if (k < TL * TL * TL) {
+        const int tx = k / (TL * TL), ty = (k / TL) % TL, tz = k % TL;
+        const int gx = wrap1(ox + s0 + tx, g.nx), gy = wrap1(oy + s0 + ty, g.ny), gz = wrap1(oz + s0 + tz, g.nz);
+        v[i] = m0[gx * plane + int64_t(gy) * g.nz + gz];
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < TURNS; ++i) {
+      const int k = int(threadIdx.x) + i * THREADS;
+      if (k < TL * TL * TL) tile[k] = v[i];
+    }
+    return;
+  }
   for (int k = threadIdx.x; k < TL * TL * TL; k += THREADS) {
     const int tx = k / (TL * TL), ty = (k / TL) % TL, tz = k % TL;
     // (o + s0 + t lies in (-n, 2n): bricks_supported guarantees n > 2 BRICK >= BRICK + N; one conditional add / subtract
@@ -1928,7 +1952,157 @@ __device__ __forceinline__ void tail_energy(const GatherTail<T>& tail, const T* 
   }
 }
 
-template <int N, bool FIELD, typename T, bool TAIL = false, int THREADS = GATHER_THREADS, bool SLAB = false>
+// ---- one atom of a gather pass: its loads, and everything behind them -----------------------------------------------------
+// The loop of gather_brick_body and its rounds of two atoms (PAIRED) are built from the same three pieces, so that the two forms
+// cannot differ in what they load or in a single operation of the arithmetic.
+
+// the 1-D weights of slot `id`: x and y rows (and their derivatives) for every lane, the lane's own z entry
+template <int N, bool FIELD, typename T>
+__device__ __forceinline__ void gather_load_weights(const T* __restrict__ wts, int id, bool lane_active, int tz, T (&wx)[N],
+                                                    T (&wy)[N], T (&dwx)[FIELD ? N : 1], T (&dwy)[FIELD ? N : 1], T& wzv,
+                                                    T& dwzv) {
+  const T* wr = wts + int64_t(id) * wts_stride<N, T>();
+#pragma unroll
+  for (int t = 0; t < N; ++t) {
+    wx[t] = wr[t];
+    wy[t] = wr[N + t];
+    if constexpr (FIELD) {
+      dwx[t] = wr[3 * N + t];
+      dwy[t] = wr[4 * N + t];
+    }
+  }
+  wzv = lane_active ? wr[2 * N + tz] : T(0);
+  dwzv = (FIELD && lane_active) ? wr[5 * N + tz] : T(0);
+}
+
+// what the record's atom index `w` addresses: charge, potential so far (accumulate), and for the tail the lane's component of the
+// pair force sum (lanes 0..2: x, y, z) and the atom's (position, charge) record
+template <typename T, bool TAIL, bool SLAB>
+__device__ __forceinline__ void gather_load_atom(int w, int C, int c, int l, const T* __restrict__ q, bool accumulate,
+                                                 const T* __restrict__ out, const GatherTail<T>* tail, T& q_early, T& out_early,
+                                                 T& f_early, AtomRecord<T>& r_early) {
+  const int64_t o_early = int64_t(w) * C + c;
+  q_early = T(0);
+  out_early = T(0);
+  if (q) {
+    q_early = q[o_early];
+    if (accumulate) out_early = out[o_early];
+  }
+  f_early = T(0);
+  r_early = AtomRecord<T>{T(0), T(0), T(0), T(0)};
+  if constexpr (TAIL) {
+    f_early = tail->force[3 * int64_t(w) + (l < 3 ? l : 0)];
+    if (SLAB || tail->rpart) r_early = tail->rec4[w];
+  }
+}
+
+// what gather_atom_finish needs that is the same for every atom of a workgroup
+template <typename T>
+struct GatherAtomArgs {
+  const Geom& g;
+  const T* tile;  // the brick's halo tile in LDS
+  int ox, oy, oz, tz, l, C;
+  const T* __restrict__ q;
+  const T* __restrict__ qsum;
+  T inv_vol, self_c, bg_c;
+  bool accumulate;
+  T* __restrict__ out;
+  T* __restrict__ raw;
+  T* __restrict__ field;
+  const GatherTail<T>* tail;
+  int* __restrict__ nan_flag;
+  T seed, seed_aux;
+  T fA, fB, pA, pB, pK;  // SLAB: see gather_brick_body
+};
+
+// Everything of an atom behind its loads: the stencil sums of the lane's z column, the reductions over the atom's lanes, field
+// and gradient, potential, dE/dq, the slab term, the NaN flag, the stores -- and (r3) the lane's share of the cell sums.
+template <int N, bool FIELD, typename T, bool TAIL, bool SLAB>
+__device__ __forceinline__ void gather_atom_finish(const GatherAtomArgs<T>& u, int c, bool valid, const int4& a,
+                                                   const T (&wx)[N], const T (&wy)[N], const T (&dwx)[FIELD ? N : 1],
+                                                   const T (&dwy)[FIELD ? N : 1], T wzv, T dwzv, T q_early, T out_early,
+                                                   T f_early, const AtomRecord<T>& r_early, double (&r3)[3]) {
+  constexpr int LANES = kGatherLanes;
+  constexpr int TL = BRICK + N - 1;
+  const Geom& g = u.g;
+  const GatherTail<T>* tail = u.tail;
+  const int l = u.l;
+  const T inv_vol = u.inv_vol;
+  const int rx = a.x - u.ox, ry = a.y - u.oy, rz = a.z - u.oz;
+  const T* tp = u.tile + ry * TL + (rz + u.tz);
+  T sA = T(0), sB = T(0), sC = T(0);  // sum wx wy M,  sum dwx wy M,  sum wx dwy M   over (t_x, t_y) of this z column
+#pragma unroll
+  for (int ty = 0; ty < N; ++ty) {
+    T sx = T(0), sdx = T(0);
+#pragma unroll
+    for (int tx = 0; tx < N; ++tx) {
+      const T v = tp[(rx + tx) * TL * TL + ty * TL];
+      sx += v * wx[tx];
+      if constexpr (FIELD) sdx += v * dwx[tx];
+    }
+    sA += sx * wy[ty];
+    if constexpr (FIELD) {
+      sB += sdx * wy[ty];
+      sC += sx * dwy[ty];
+    }
+  }
+  T acc = sA * wzv;
+  if constexpr (FIELD) {
+    const T fx = group_sum_b<LANES, T>(sB * wzv) * T(g.nx) * inv_vol;
+    const T fy = group_sum_b<LANES, T>(sC * wzv) * T(g.ny) * inv_vol;
+    const T fz = group_sum_b<LANES, T>(sA * dwzv) * T(g.nz) * inv_vol;
+    if constexpr (TAIL) {
+      // lanes 0..2 own one Cartesian component each: field (kept for other consumers) and the assembled gradient
+      const int k3 = l < 3 ? l : 0;
+      const T fc = T(g.inv[3 * k3]) * fx + T(g.inv[3 * k3 + 1]) * fy + T(g.inv[3 * k3 + 2]) * fz;
+      T fs = fc;  // SLAB: + the term's field along its axis (the cell sums below take the mesh part alone)
+      if constexpr (SLAB) {
+        if (l == tail->slab_axis) fs += u.fA - u.fB * slab_coord(r_early, tail->slab_axis);
+      }
+      if (l < 3 && valid) {
+        const int64_t o = int64_t(a.w);
+        u.field[3 * o + l] = fs;
+        tail->grad_pos[3 * o + l] = u.seed * q_early * (tail->force_scale * f_early + fs);
+        if (tail->rpart) {
+          const double gp = double(u.seed_aux * q_early * fc);
+          r3[0] += double(r_early.x) * gp;
+          r3[1] += double(r_early.y) * gp;
+          r3[2] += double(r_early.z) * gp;
+        }
+      }
+    } else if (l == 0 && valid) {
+      const int64_t o = int64_t(a.w);
+      u.field[3 * o + 0] = T(g.inv[0]) * fx + T(g.inv[1]) * fy + T(g.inv[2]) * fz;
+      u.field[3 * o + 1] = T(g.inv[3]) * fx + T(g.inv[4]) * fy + T(g.inv[5]) * fz;
+      u.field[3 * o + 2] = T(g.inv[6]) * fx + T(g.inv[7]) * fy + T(g.inv[8]) * fz;
+    }
+  }
+  acc = group_sum_b<LANES, T>(acc);
+  if (l == 0 && valid) {
+    const int64_t o = int64_t(a.w) * u.C + c;
+    if (u.q) {
+      const T phi = acc * inv_vol;
+      T lr = T(0.5) * (phi - u.self_c * q_early - T(2) * u.bg_c * inv_vol * u.qsum[c]);
+      if constexpr (SLAB) {
+        const T z = slab_coord(r_early, tail->slab_axis);
+        lr += z * (u.pA - u.pB * z) + u.pK;
+      }
+      const T v_final = u.accumulate ? out_early + lr : lr;
+      u.out[o] = v_final;
+      if constexpr (TAIL) {
+        if (tail->grad_q) tail->grad_q[o] = T(2) * u.seed_aux * v_final;
+      }
+      if (u.nan_flag && lr != lr) *u.nan_flag = 1;  // NaN guard of kspace_filter.py:189-195 (see mipme.h, nan_flag)
+      if (u.raw) u.raw[o] = phi;
+    } else {
+      u.out[o] = acc;
+    }
+  }
+}
+
+// PAIRED: rounds of two atoms per lane group instead of the loop of one (see the loop); the tail kernels' choice
+template <int N, bool FIELD, typename T, bool TAIL = false, int THREADS = GATHER_THREADS, bool SLAB = false,
+          bool PAIRED = false>
 __device__ __forceinline__ void gather_brick_body(const Geom& g, const BrickGeom& bg, int C, const BinIndex& bins,
                                                   const int4* __restrict__ rec, const T* __restrict__ wts,
                                                   const T* __restrict__ mesh, const T* __restrict__ q,
@@ -1939,6 +2113,7 @@ __device__ __forceinline__ void gather_brick_body(const Geom& g, const BrickGeom
   static_assert(N <= kGatherLanes, "one lane per z point of the stencil");
   static_assert(!TAIL || FIELD, "the tail needs the mesh field");
   static_assert(!SLAB || TAIL, "the slab term rides in the tail");
+  static_assert(!PAIRED || TAIL, "rounds of two atoms are a form of the tail kernels");
   constexpr int LANES = kGatherLanes;
   constexpr int GROUPS = THREADS / LANES;
   constexpr int TL = BRICK + N - 1;
@@ -1985,6 +2160,8 @@ __device__ __forceinline__ void gather_brick_body(const Geom& g, const BrickGeom
   const int l = threadIdx.x % LANES, grp = threadIdx.x / LANES;
   const bool lane_active = l < N;
   const int tz = lane_active ? l : 0;
+  const GatherAtomArgs<T> ga{g,   tile, ox,  oy,    oz,     tz,   l,     C,        q,    qsum,     inv_vol, self_c, bg_c, accumulate,
+                            out, raw,  field, tail, nan_flag, seed, seed_aux, fA,   fB,       pA,      pB,     pK};
   for (int c = 0; c < C; ++c) {
     if (c > 0) __syncthreads();
     // The loads of a pass are issued in the order of their dependencies and BEFORE the tile is staged, so that the kernel is
@@ -1992,120 +2169,88 @@ __device__ __forceinline__ void gather_brick_body(const Geom& g, const BrickGeom
     // the third overlaps the stencil arithmetic -- not five in series (each is a trip to the Infinity Cache: the inputs
     // were written by other XCDs in the previous kernels).
     bool staged = false;
-    for (int it = 0; it < main_iters + over_iters; ++it) {
-      bool valid;
-      int id;
-      if (it < main_iters) {
-        const int idx = beg + it * GROUPS + grp;
-        valid = idx < end;
-        id = valid ? idx : beg;
-      } else {
-        const int k = (it - main_iters) * GROUPS + grp;
-        valid = k < n_over && bins.over_brick[k < n_over ? k : 0] == int(block);
-        id = int(bins.over_base) + (k < n_over ? k : 0);
-      }
-      int4 a = rec[id];
-      if (!valid) a = make_int4(ox, oy, oz, 0);  // a slot that may never have been written: keep every index derived from it in range
-      const T* wr = wts + int64_t(id) * wts_stride<N, T>();
-      T wx[N], wy[N], dwx[FIELD ? N : 1], dwy[FIELD ? N : 1];
-#pragma unroll
-      for (int t = 0; t < N; ++t) {
-        wx[t] = wr[t];
-        wy[t] = wr[N + t];
-        if constexpr (FIELD) {
-          dwx[t] = wr[3 * N + t];
-          dwy[t] = wr[4 * N + t];
-        }
-      }
-      const T wzv = lane_active ? wr[2 * N + tz] : T(0);
-      const T dwzv = (FIELD && lane_active) ? wr[5 * N + tz] : T(0);
-      if (!staged) {
-        load_tiles<N, 1, T, THREADS>(g, ox, oy, oz, mesh + c * M, nullptr, tile);
-        staged = true;
-      }
-      // the atom's charge and (accumulate) its potential so far: needed only at the end of the pass
-      const int64_t o_early = int64_t(a.w) * C + c;
-      T q_early = T(0), out_early = T(0);
-      if (q) {
-        q_early = q[o_early];
-        if (accumulate) out_early = out[o_early];
-      }
-      T f_early = T(0);  // TAIL: lanes 0..2 hold the x, y, z components of the atom's pair force sum
-      AtomRecord<T> r_early{T(0), T(0), T(0), T(0)};
-      if constexpr (TAIL) {
-        f_early = tail->force[3 * int64_t(a.w) + (l < 3 ? l : 0)];
-        if (SLAB || tail->rpart) r_early = tail->rec4[a.w];
-      }
-      if (it == 0) __syncthreads();  // tile staged (uniform: every thread runs the first pass)
-      const int rx = a.x - ox, ry = a.y - oy, rz = a.z - oz;
-      const T* tp = tile + ry * TL + (rz + tz);
-      T sA = T(0), sB = T(0), sC = T(0);  // sum wx wy M,  sum dwx wy M,  sum wx dwy M   over (t_x, t_y) of this z column
-#pragma unroll
-      for (int ty = 0; ty < N; ++ty) {
-        T sx = T(0), sdx = T(0);
-#pragma unroll
-        for (int tx = 0; tx < N; ++tx) {
-          const T v = tp[(rx + tx) * TL * TL + ty * TL];
-          sx += v * wx[tx];
-          if constexpr (FIELD) sdx += v * dwx[tx];
-        }
-        sA += sx * wy[ty];
-        if constexpr (FIELD) {
-          sB += sdx * wy[ty];
-          sC += sx * dwy[ty];
-        }
-      }
-      T acc = sA * wzv;
-      if constexpr (FIELD) {
-        const T fx = group_sum_b<LANES, T>(sB * wzv) * T(g.nx) * inv_vol;
-        const T fy = group_sum_b<LANES, T>(sC * wzv) * T(g.ny) * inv_vol;
-        const T fz = group_sum_b<LANES, T>(sA * dwzv) * T(g.nz) * inv_vol;
-        if constexpr (TAIL) {
-          // lanes 0..2 own one Cartesian component each: field (kept for other consumers) and the assembled gradient
-          const int k3 = l < 3 ? l : 0;
-          const T fc = T(g.inv[3 * k3]) * fx + T(g.inv[3 * k3 + 1]) * fy + T(g.inv[3 * k3 + 2]) * fz;
-          T fs = fc;  // SLAB: + the term's field along its axis (the cell sums below take the mesh part alone)
-          if constexpr (SLAB) {
-            if (l == tail->slab_axis) fs += fA - fB * slab_coord(r_early, tail->slab_axis);
-          }
-          if (l < 3 && valid) {
-            const int64_t o = int64_t(a.w);
-            field[3 * o + l] = fs;
-            tail->grad_pos[3 * o + l] = seed * q_early * (tail->force_scale * f_early + fs);
-            if (tail->rpart) {
-              const double gp = double(seed_aux * q_early * fc);
-              r3[0] += double(r_early.x) * gp;
-              r3[1] += double(r_early.y) * gp;
-              r3[2] += double(r_early.z) * gp;
-            }
-          }
-        } else if (l == 0 && valid) {
-          const int64_t o = int64_t(a.w);
-          field[3 * o + 0] = T(g.inv[0]) * fx + T(g.inv[1]) * fy + T(g.inv[2]) * fz;
-          field[3 * o + 1] = T(g.inv[3]) * fx + T(g.inv[4]) * fy + T(g.inv[5]) * fz;
-          field[3 * o + 2] = T(g.inv[6]) * fx + T(g.inv[7]) * fy + T(g.inv[8]) * fz;
-        }
-      }
-      acc = group_sum_b<LANES, T>(acc);
-      if (l == 0 && valid) {
-        const int64_t o = int64_t(a.w) * C + c;
-        if (q) {
-          const T phi = acc * inv_vol;
-          T lr = T(0.5) * (phi - self_c * q_early - T(2) * bg_c * inv_vol * qsum[c]);
-          if constexpr (SLAB) {
-            const T z = slab_coord(r_early, tail->slab_axis);
-            lr += z * (pA - pB * z) + pK;
-          }
-          const T v_final = accumulate ? out_early + lr : lr;
-          out[o] = v_final;
-          if constexpr (TAIL) {
-            if (tail->grad_q) tail->grad_q[o] = T(2) * seed_aux * v_final;
-          }
-          if (nan_flag && lr != lr) *nan_flag = 1;  // NaN guard of kspace_filter.py:189-195 (see mipme.h, nan_flag)
-          if (raw) raw[o] = phi;
+    if constexpr (PAIRED) {
+      // Rounds of two passes: a lane group takes the atoms of pass `it` (A) and of pass `it + 1` (B) of the sequence below --
+      // own slots, then the overflow candidates -- and issues both atoms' loads of each trip together, so that a brick of up
+      // to 2 * GROUPS atoms is the same three trips (the loop below starts the trips of its second pass after the
+      // arithmetic of the first: five).  Arithmetic and stores are gather_atom_finish for A, then B: the order of the loop.
+      const int iters = main_iters + over_iters;
+      // slot of this lane group in pass `it`; a pass beyond the last one yields the brick's first slot, not valid
+      auto slot_of = [&](int it, bool& valid, int& id) {
+        if (it < main_iters) {
+          const int idx = beg + it * GROUPS + grp;
+          valid = idx < end;
+          id = valid ? idx : beg;
+        } else if (it < iters) {
+          const int k = (it - main_iters) * GROUPS + grp;
+          valid = k < n_over && bins.over_brick[k < n_over ? k : 0] == int(block);
+          id = int(bins.over_base) + (k < n_over ? k : 0);
         } else {
-          out[o] = acc;
+          valid = false;
+          id = beg;
         }
+      };
+      for (int it = 0; it < iters; it += 2) {
+        bool validA, validB;
+        int idA, idB;
+        slot_of(it, validA, idA);
+        slot_of(it + 1, validB, idB);
+        // B's loads only in the lane groups that have a second atom: the others would all fetch the brick's first slot and then
+        // atom 0's charge, potential and force -- lines that atom 0's own workgroup is writing at that moment, asked for by
+        // every lane group of every brick of <= GROUPS atoms (measured: +0.6 us on each of those workgroups)
+        int4 aA = rec[idA], aB = make_int4(ox, oy, oz, 0);
+        T wxA[N], wyA[N], dwxA[FIELD ? N : 1], dwyA[FIELD ? N : 1], wzvA, dwzvA;
+        T wxB[N] = {}, wyB[N] = {}, dwxB[FIELD ? N : 1] = {}, dwyB[FIELD ? N : 1] = {}, wzvB = T(0), dwzvB = T(0);
+        gather_load_weights<N, FIELD, T>(wts, idA, lane_active, tz, wxA, wyA, dwxA, dwyA, wzvA, dwzvA);
+        if (validB) {
+          aB = rec[idB];
+          gather_load_weights<N, FIELD, T>(wts, idB, lane_active, tz, wxB, wyB, dwxB, dwyB, wzvB, dwzvB);
+        }
+        // a slot that may never have been written: keep every index derived from it in range
+        if (!validA) aA = make_int4(ox, oy, oz, 0);
+        if (!staged) {
+          load_tiles<N, 1, T, THREADS, true>(g, ox, oy, oz, mesh + c * M, nullptr, tile);
+          staged = true;
+        }
+        // what the records' atom indices address, of both atoms: needed only at the end of each atom's arithmetic
+        T qA, outA, fAe, qB = T(0), outB = T(0), fBe = T(0);
+        AtomRecord<T> rA, rB{T(0), T(0), T(0), T(0)};
+        gather_load_atom<T, TAIL, SLAB>(aA.w, C, c, l, q, accumulate, out, tail, qA, outA, fAe, rA);
+        if (validB) gather_load_atom<T, TAIL, SLAB>(aB.w, C, c, l, q, accumulate, out, tail, qB, outB, fBe, rB);
+        if (it == 0) __syncthreads();  // tile staged (uniform: every thread runs the first round)
+        gather_atom_finish<N, FIELD, T, TAIL, SLAB>(ga, c, validA, aA, wxA, wyA, dwxA, dwyA, wzvA, dwzvA, qA, outA, fAe, rA, r3);
+        // a wavefront none of whose lane groups has a second atom (every one of a brick of <= GROUPS atoms) skips B: uniform
+        if (__any(validB))
+          gather_atom_finish<N, FIELD, T, TAIL, SLAB>(ga, c, validB, aB, wxB, wyB, dwxB, dwyB, wzvB, dwzvB, qB, outB, fBe, rB, r3);
+      }
+    } else {
+      for (int it = 0; it < main_iters + over_iters; ++it) {
+        bool valid;
+        int id;
+        if (it < main_iters) {
+          const int idx = beg + it * GROUPS + grp;
+          valid = idx < end;
+          id = valid ? idx : beg;
+        } else {
+          const int k = (it - main_iters) * GROUPS + grp;
+          valid = k < n_over && bins.over_brick[k < n_over ? k : 0] == int(block);
+          id = int(bins.over_base) + (k < n_over ? k : 0);
+        }
+        int4 a = rec[id];
+        if (!valid) a = make_int4(ox, oy, oz, 0);  // a slot that may never have been written: keep every index derived from it in range
+        T wx[N], wy[N], dwx[FIELD ? N : 1], dwy[FIELD ? N : 1], wzv, dwzv;
+        gather_load_weights<N, FIELD, T>(wts, id, lane_active, tz, wx, wy, dwx, dwy, wzv, dwzv);
+        if (!staged) {
+          load_tiles<N, 1, T, THREADS>(g, ox, oy, oz, mesh + c * M, nullptr, tile);
+          staged = true;
+        }
+        // the atom's charge and (accumulate) its potential so far: needed only at the end of the pass
+        T q_early, out_early, f_early;  // TAIL: lanes 0..2 hold the x, y, z components of the atom's pair force sum
+        AtomRecord<T> r_early;
+        gather_load_atom<T, TAIL, SLAB>(a.w, C, c, l, q, accumulate, out, tail, q_early, out_early, f_early, r_early);
+        if (it == 0) __syncthreads();  // tile staged (uniform: every thread runs the first pass)
+        gather_atom_finish<N, FIELD, T, TAIL, SLAB>(ga, c, valid, a, wx, wy, dwx, dwy, wzv, dwzv, q_early, out_early, f_early,
+                                                    r_early, r3);
       }
     }
   }
@@ -2140,8 +2285,17 @@ __global__ __launch_bounds__(GATHER_THREADS) void gather_brick_kernel(Geom g, Br
 #ifndef MIPME_GATHER_TAIL_WAVES
 #define MIPME_GATHER_TAIL_WAVES 6
 #endif
-template <int N, typename T, int THREADS = GATHER_THREADS, bool DENSE = false, bool SLAB = false>
-__global__ __launch_bounds__(THREADS, DENSE ? MIPME_GATHER_TAIL_WAVES : 1) void gather_tail_kernel(Geom g, BrickGeom bg, BinIndex bins,
+// PAIRED (rounds of two atoms per lane group, gather_brick_body): a brick of 65..128 atoms -- 39 % of cfg3's, every one of the
+// ionic boxes' -- is three dependent memory trips like a brick of up to 64, not five.  Two atoms' weights are in registers at
+// once: the fp32 build is told to stay within 128 (4 waves per SIMD = the two workgroups per CU that hold cfg3's 512 bricks at
+// once), the fp64 build of a single-frame launch may take what it likes (64 bricks on 256 CUs).  See gather_pairs_fit.
+template <typename T>
+static constexpr int gather_pairs_waves() { return sizeof(T) == 4 ? 4 : 1; }
+// the instantiations that have the paired form: orders up to 5, 512 threads, not DENSE (held to 80 registers)
+template <int N, typename T, int THREADS, bool DENSE>
+static constexpr bool gather_pairs_fit() { return N <= 5 && THREADS == GATHER_THREADS && !DENSE; }
+template <int N, typename T, int THREADS = GATHER_THREADS, bool DENSE = false, bool SLAB = false, bool PAIRED = false>
+__global__ __launch_bounds__(THREADS, DENSE ? MIPME_GATHER_TAIL_WAVES : (PAIRED ? gather_pairs_waves<T>() : 1)) void gather_tail_kernel(Geom g, BrickGeom bg, BinIndex bins,
                                                              const int4* __restrict__ rec, const T* __restrict__ wts,
                                                              const T* __restrict__ mesh, const T* __restrict__ q,
                                                              const T* __restrict__ qsum, T inv_vol, T self_c, T bg_c,
@@ -2150,8 +2304,8 @@ __global__ __launch_bounds__(THREADS, DENSE ? MIPME_GATHER_TAIL_WAVES : 1) void 
   MIPME_WG_STAMP_GATHER(0);
   const unsigned b = brick_of(bg, blockIdx.x);
   if (b < unsigned(bg.nb))
-    gather_brick_body<N, true, T, true, THREADS, SLAB>(g, bg, 1, bins, rec, wts, mesh, q, qsum, inv_vol, self_c, bg_c, true, out,
-                                                       raw, field, b, &tail, nan_flag);
+    gather_brick_body<N, true, T, true, THREADS, SLAB, PAIRED>(g, bg, 1, bins, rec, wts, mesh, q, qsum, inv_vol, self_c, bg_c, true,
+                                                               out, raw, field, b, &tail, nan_flag);
 #if MIPME_WG_TIMELINE_GATHER
   __syncthreads();
 #endif

@@ -19,6 +19,8 @@ void note_cosched_kernel(const char* name);
 void note_slot_fill(int rider_atoms);
 // (mipme_last_cell_riders: cell riders on the inverse plane launch that carried the slot riders)
 void note_cell_riders(int n);
+// (mipme_last_gather_pairs: 1 = the last gather launch took its atoms in rounds of two per lane group, 0 = one by one)
+void note_gather_pairs(int paired);
 
 #define MIPME_CHECK_HIP(expr)                                                                 \
   do {                                                                                        \

@@ -320,6 +320,7 @@ static int frames_forward_t(mipme_fft_plan* plan, hipStream_t st, int n_frames, 
     MIPME_DISPATCH_STENCIL_B(m->scheme, m->order,
                              ((void)S, frames_spread_rows_kernel<N, T, 6, false><<<dim3(grid_x, F), SPREAD_THREADS, lds, st>>>(tb)));
   MIPME_LAUNCH_CHECK();
+  note_gather_pairs(0);  // (the batches' gathers take one atom per lane group and pass)
   bool all_tail = true;
   for (int k = 0; k < n_frames; ++k) all_tail = all_tail && fr[k].use_tail != 0;
   const int64_t n_k = xconv_blocks(plan) / n_frames;  // blocks of the x stage per batch entry

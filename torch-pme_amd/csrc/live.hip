@@ -671,6 +671,7 @@ int live_gather(hipStream_t st, const mipme_mesh_t* m, int64_t N, const void* re
   const BrickGeom bg = make_brick_geom(m);
   const BinsView v = bins_view(m, N, dtype, bins);
   const LiveLists ll = live_view(m, N, lists, nullptr);
+  note_gather_pairs(0);  // (a body of its own: one atom per lane group and pass)
   MIPME_REQUIRE(th && th->force && th->grad_pos && th->energy && th->epart_k && out && qsum, "NULL buffer passed to the live gather");
   // (the pair kernel's energy partial sums: pre-reduced by the x stage of the convolution)
   const GatherTail<T> tail =
