@@ -309,6 +309,53 @@ def test_python_refusals():
                                                full_neighbor_list=True))
 
 
+def test_shared_checks_word_for_word():
+    """The step, the dipole step and the batch raise through the same helpers of graphed.py: both forms of every sentence."""
+    from torchpme_amd.graphed import _check_ewald_system, _check_explicit_list, _ewald_kgrid
+
+    z = lambda *s, dt=F64: torch.zeros(*s, dtype=dt)  # noqa: E731
+    idx, far = torch.tensor([[0, 1]]), torch.tensor([[0.0, 4.0, 0.0]], dtype=F64)
+    shifts = ("the cell shifts must be integers in [-3, 3] (the 4-byte pair entries of the row kernel); wrap the positions into the "
+              "cell or use a shorter cutoff")
+    cases = [
+        (lambda: _check_explicit_list("GraphedEwaldStep", idx, far), "GraphedEwaldStep: " + shifts),
+        (lambda: _check_explicit_list("GraphedDipoleStep", idx, far), "GraphedDipoleStep: " + shifts),
+        (lambda: _check_explicit_list("GraphedEwaldBatch", idx, far, frame=7), "GraphedEwaldBatch: frame 7: " + shifts),
+        (lambda: _check_explicit_list("GraphedEwaldStep", idx[0], far),
+         "`neighbor_indices` must be a tensor with shape [n_pairs, 2], got tensor with shape [2]"),
+        (lambda: _check_explicit_list("GraphedEwaldBatch", idx, z(2, 3), frame=1),
+         "GraphedEwaldBatch: frame 1: `neighbor_shifts` must be a tensor with shape [n_pairs, 3] with n_pairs = 1, got tensor with "
+         "shape [2, 3]"),
+        (lambda: _check_ewald_system("GraphedEwaldStep", z(2, 2), z(3, 3), z(2, 3)),
+         "GraphedEwaldStep handles a single charge channel, `charges` of shape [n_atoms, 1], got tensor with shape [2, 2]"),
+        (lambda: _check_ewald_system("GraphedEwaldBatch", z(2, 2), z(3, 3), z(2, 3), frame=0, first=z(1)),
+         "GraphedEwaldBatch: frame 0: a single charge channel, `charges` of shape [n_atoms, 1], got tensor with shape [2, 2]"),
+        (lambda: _check_ewald_system("GraphedEwaldStep", z(2, 1), z(3, 3), z(3, 3)),
+         "`positions` must be a tensor with shape [n_atoms, 3] with n_atoms = 2 (the charges), got tensor with shape [3, 3]"),
+        (lambda: _check_ewald_system("GraphedEwaldBatch", z(2, 1), z(3), z(2, 3), frame=3, first=z(1)),
+         "GraphedEwaldBatch: frame 3: `cell` must be a tensor with shape [3, 3], got tensor with shape [3]"),
+        (lambda: _check_ewald_system("GraphedEwaldStep", z(2, 1), z(3, 3, dt=torch.float32), z(2, 3)),
+         "`positions`, `charges` and `cell` must share one dtype, float32 or float64, got torch.float64, torch.float64 and "
+         "torch.float32"),
+        (lambda: _check_ewald_system("GraphedEwaldBatch", z(2, 1), z(3, 3), z(2, 3), frame=1, first=z(1, dt=torch.float32)),
+         "GraphedEwaldBatch: frame 1: `positions`, `charges` and `cell` of all frames must share one dtype, float32 or float64, got "
+         "torch.float64, torch.float64 and torch.float64 (frame 0: torch.float32)"),
+        (lambda: _check_ewald_system("GraphedEwaldStep", z(0, 1), z(3, 3), z(0, 3)),
+         "GraphedEwaldStep handles 1 to 2^22 atoms (the 4-byte pair entries of the row kernel), got 0"),
+        (lambda: _check_ewald_system("GraphedEwaldBatch", z(0, 1), z(3, 3), z(0, 3), frame=2, first=z(1)),
+         "GraphedEwaldBatch: frame 2: a frame holds 1 to 2^22 atoms (the 4-byte pair entries of the row kernel), got 0"),
+    ]
+    for call, text in cases:
+        with pytest.raises(ValueError) as e:
+            call()
+        assert str(e.value) == text
+    # the frozen k grid: ns of the cell, one of every pair +-k without k = 0, int32 throughout
+    ns, freq, mult = _ewald_kgrid(torch.eye(3, dtype=F64) * 5.0, 2.0)
+    assert ns == (3, 3, 3) and freq.dtype == mult.dtype == np.int32 and freq.shape == (13, 3) and mult.tolist() == [2] * 13
+    ns, freq, mult = _ewald_kgrid(torch.eye(3, dtype=F64), 2.0)
+    assert ns == (1, 1, 1) and freq.shape == (0, 3) and mult.shape == (0,)
+
+
 def test_kgrid_matches_is_decided_per_frame_on_the_host():
     from torchpme_amd.graphed import GraphedEwaldBatch
 

@@ -191,6 +191,27 @@ def test_independence_to_the_bit(cname, dtype):
         assert _same(first[n], alone[0]), f"frame {n} alone"
 
 
+# ---- the batch of one frame and the single step of that frame run the same bodies (csrc/ewald_step_bodies.h) --------------------
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("cname", ["C1", "C2"])
+@pytest.mark.parametrize("n", ALL)
+def test_a_batch_of_one_frame_equals_the_single_step_to_the_bit(n, cname, dtype):
+    """E, F, dE/dq, dE/dcell and status, at the construction cell and -- from the same two graphs -- at the strained cell with
+    the strained positions."""
+    step, batch = _single(cname, dtype, n), _batch(cname, dtype, which=(n,))
+    graphs = (step.graph, batch.graph)
+    _, p, c, _, _ = _system(n, CALCS[cname][1])
+    for ctag, m in (("c0", np.eye(3)), ("c1", STRAIN)):
+        pos, cell = _t(p @ m, dtype), _t(c @ m, dtype)
+        one = [o.clone() for o in step(positions=pos, cell=cell)] + [step.status[0].clone()]
+        got = _bits(batch, positions=[pos], cells=[cell])[0]
+        torch.cuda.synchronize()
+        for key, a, b in zip(("E", "F", "gq", "gcell", "status"), one, got):
+            assert a.shape == b.shape and torch.equal(a, b), f"{cname} f{n} {ctag} {dtype}: {key} of the step and of the batch differ"
+        assert int(got[4]) == 0
+    assert (step.graph, batch.graph) == graphs
+
+
 # ---- what happens to one frame happens to that frame alone ----------------------------------------------------------------
 @pytest.mark.parametrize("dtype", DTYPES)
 def test_isolation(dtype):

@@ -13,19 +13,17 @@
 // A frame's record holds where its slices of the concatenated buffers begin and where its work area lies; the work area of a frame
 // is laid out exactly as the single step lays out its own (es_work_layout), the areas one behind the other in frame order.
 //
-// Inside its blocks a frame is computed as the single step computes it, with LOCAL indices (partner atoms, row pointers and
-// k-vectors count from the start of the frame): the slice count of the atom kernel is es_slices(N_f, K_f), every cross-block sum
-// is float64 block partials of that frame added in index order by a later launch, and nothing a block reads belongs to another
-// frame.  So the bits a frame gets depend on its own inputs alone -- not on its index, on F or on its neighbours in the batch.
+// Inside its blocks a frame is computed as the single step computes it -- by the same bodies (ewald_step_bodies.h), which see
+// one system and nothing of the table -- with LOCAL indices (partner atoms, row pointers and k-vectors count from the start of
+// the frame): the slice count of the atom kernel is es_slices(N_f, K_f), every cross-block sum is float64 block partials of that
+// frame added in index order by a later launch, and nothing a block reads belongs to another frame.  So the bits a frame gets depend on its own inputs alone -- not on its index, on F or on its neighbours in the batch.
 // No atomics, no workgroup waits for another.  A singular cell gives ITS frame a zero k table, E = NaN, dE/dcell = NaN and
 // status bit 1, and no other frame anything.
 #include <cmath>
 
-#include "dipole_device.h"
+#include "ewald_step_bodies.h"
 #include "ewald_step_device.h"
 #include "host.h"
-#include "kpot.h"
-#include "rows_body.h"
 
 namespace mipme {
 
@@ -109,7 +107,9 @@ static bool eb_layout(int F, const int64_t* atom_ptr, const int64_t* k_ptr, cons
   return true;
 }
 
-// ---- 1. prep: per frame the k table and geometry (local blocks < n_table_blocks), records and charge partials (behind them) --
+// ---- the kernels: the bodies of ewald_step_bodies.h with the sizes, the slices and the local block index of the block's frame ----
+// blk and everything read from the frame's record is uniform per block.  Partner atoms, row pointers and k-vectors are local to
+// the frame: a body that gets the frame's slices computes what the single step computes.
 template <typename T>
 __global__ __launch_bounds__(kEsBlock) void ewald_batch_prep_kernel(KPot kp, const EbFrame* __restrict__ frames,
                                                                    const EbBlock* __restrict__ blocks, const T* __restrict__ cells,
@@ -119,153 +119,41 @@ __global__ __launch_bounds__(kEsBlock) void ewald_batch_prep_kernel(KPot kp, con
                                                                    T* __restrict__ G_all, T* __restrict__ dG_all,
                                                                    AtomRecord<T>* __restrict__ rec_all, double* __restrict__ work,
                                                                    int* __restrict__ status) {
-  __shared__ double red[kEsWaves];
-  const EbBlock blk = blocks[blockIdx.x];  // (uniform per block, like everything read from the frame's record)
+  const EbBlock blk = blocks[blockIdx.x];
   const EbFrame& fr = frames[blk.frame];
-  const int64_t N = fr.n_atoms, K = fr.n_k;
-  const int n_table_blocks = fr.n_table_blocks;
-  if (blk.local >= n_table_blocks) {
-    const int64_t a = int64_t(blk.local - n_table_blocks) * kEsBlock + threadIdx.x;
-    double qa = 0.0;
-    if (a < N) {
-      const int64_t ga = fr.atom0 + a;
-      const T qv = q_all[ga];
-      rec_all[ga] = AtomRecord<T>{pos_all[3 * ga], pos_all[3 * ga + 1], pos_all[3 * ga + 2], qv};
-      qa = double(qv);
-    }
-    const double s = block_sum<kEsWaves>(qa, red);
-    if (threadIdx.x == 0) work[fr.q_part + (blk.local - n_table_blocks)] = s;
-    return;
-  }
-  double A[9];
-  const EsCell g = es_invert_cell(cells + 9 * int64_t(blk.frame), A);
-  if (blk.local == 0 && threadIdx.x == 0) {
-    double* __restrict__ geom = work + fr.geom;
-    // A^-1 = (A^-T)^T, row-major
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-      for (int c = 0; c < 3; ++c) geom[3 * r + c] = g.recip[3 * c + r];
-    geom[9] = g.inv_vol;
-    geom[10] = g.bad ? 1.0 : 0.0;
-    // bit 0: the eager call would choose another k grid for this cell, ns_d = ceil(|a_d| / lr_wavelength)
-    const int ns[3] = {fr.ns[0], fr.ns[1], fr.ns[2]};
-    int st = g.bad ? 2 : 0;
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-      const double norm = sqrt(A[3 * d] * A[3 * d] + A[3 * d + 1] * A[3 * d + 1] + A[3 * d + 2] * A[3 * d + 2]);
-      if (!(ceil(norm / lr_wavelength) == double(ns[d]))) st |= 1;
-    }
-    status[blk.frame] = st;
-  }
-  const int64_t k = int64_t(blk.local) * kEsBlock + threadIdx.x;
-  if (k >= K) return;
-  const int* __restrict__ freq = freq_all + 3 * fr.k0;
-  double kv[3] = {0.0, 0.0, 0.0}, v = 0.0, dv = 0.0;
-  if (!g.bad) {  // (a singular cell: a table of zeros, and the final launch writes NaN as the energy)
-    const double f0 = double(freq[3 * k]), f1 = double(freq[3 * k + 1]), f2 = double(freq[3 * k + 2]);
-#pragma unroll
-    for (int n = 0; n < 3; ++n) kv[n] = (2.0 * kPi) * (f0 * g.recip[n] + f1 * g.recip[3 + n] + f2 * g.recip[6 + n]);
-    lr_kernel_dev(kp, kv[0] * kv[0] + kv[1] * kv[1] + kv[2] * kv[2], v, dv);
-    const double m = double(mult_all[fr.k0 + k]);
-    v *= m;
-    dv *= m;
-  }
-  T* __restrict__ kvec = kvec_all + 3 * fr.k0;
-  kvec[3 * k] = T(kv[0]), kvec[3 * k + 1] = T(kv[1]), kvec[3 * k + 2] = T(kv[2]);
-  G_all[fr.k0 + k] = T(v);
-  if (dG_all) dG_all[fr.k0 + k] = T(dv);
+  es_prep_body<T>(kp, fr.n_atoms, fr.n_k, fr.n_table_blocks, blk.local, cells + 9 * int64_t(blk.frame), freq_all + 3 * fr.k0,
+                  mult_all + fr.k0, fr.ns[0], fr.ns[1], fr.ns[2], lr_wavelength, pos_all + 3 * fr.atom0, q_all + fr.atom0,
+                  kvec_all + 3 * fr.k0, G_all + fr.k0, dG_all ? dG_all + fr.k0 : nullptr, rec_all + fr.atom0, work + fr.q_part,
+                  work + fr.geom, status + blk.frame);
 }
 
-// ---- 2. structure factors: 32 lanes per k-vector, the frame's records streamed through LDS ------------------------------------
-// (the phase function of the atom and cell kernels: see ewald_step_structure_kernel)
 template <typename T>
 __global__ __launch_bounds__(kEsBlock) void ewald_batch_structure_kernel(const EbFrame* __restrict__ frames,
                                                                         const EbBlock* __restrict__ blocks,
                                                                         const AtomRecord<T>* __restrict__ rec_all,
                                                                         const T* __restrict__ kvec_all, T* __restrict__ Sc_all,
                                                                         T* __restrict__ Ss_all) {
-  __shared__ AtomRecord<T> sr[kEsTile];
   const EbBlock blk = blocks[blockIdx.x];
   const EbFrame& fr = frames[blk.frame];
-  const int64_t N = fr.n_atoms, K = fr.n_k;
-  const AtomRecord<T>* __restrict__ rec = rec_all + fr.atom0;
-  const T* __restrict__ kvec = kvec_all + 3 * fr.k0;
-  const int al = threadIdx.x % kEsKLanes;
-  const int64_t k = int64_t(blk.local) * kEsKPerBlock + threadIdx.x / kEsKLanes;
-  const bool valid = k < K;
-  const int64_t kc = valid ? k : 0;
-  const T kx = kvec[3 * kc], ky = kvec[3 * kc + 1], kz = kvec[3 * kc + 2];
-  T ac = T(0), as = T(0);
-  for (int64_t base = 0; base < N; base += kEsTile) {
-    const int n = int(min<int64_t>(kEsTile, N - base));
-    __syncthreads();
-    for (int t = threadIdx.x; t < n; t += kEsBlock) sr[t] = rec[base + t];
-    __syncthreads();
-    for (int i = al; i < n; i += kEsKLanes) {
-      const AtomRecord<T> r = sr[i];
-      T s, c;
-      dipole_phase3(kx, ky, kz, r.x, r.y, r.z, s, c);
-      ac += r.w * c;
-      as += r.w * s;
-    }
-  }
-#pragma unroll
-  for (int off = kEsKLanes / 2; off > 0; off >>= 1) {
-    ac += __shfl_xor(ac, off, kEsKLanes);
-    as += __shfl_xor(as, off, kEsKLanes);
-  }
-  if (valid && al == 0) Sc_all[fr.k0 + k] = ac, Ss_all[fr.k0 + k] = as;
+  es_structure_body<T>(fr.n_atoms, fr.n_k, int64_t(blk.local), rec_all + fr.atom0, kvec_all + 3 * fr.k0, Sc_all + fr.k0,
+                       Ss_all + fr.k0);
 }
 
-// ---- 3. fused atom kernel: local block = slice * N + i, atom i against the k-vectors [slice * chunk, (slice + 1) * chunk) ----
-// part[(slice N + i) 4 + c] of the frame: c = 0 the potential sum_k G (c S_c + s S_s), c >= 1 the bracket sum_k G k (c S_s - s S_c)
+// local block = slice * N + i
 template <typename T>
 __global__ __launch_bounds__(kEsBlock) void ewald_batch_atom_kernel(const EbFrame* __restrict__ frames, const EbBlock* __restrict__ blocks,
                                                                    const AtomRecord<T>* __restrict__ rec_all,
                                                                    const T* __restrict__ kvec_all, const T* __restrict__ G_all,
                                                                    const T* __restrict__ Sc_all, const T* __restrict__ Ss_all,
                                                                    double* __restrict__ work) {
-  __shared__ T red[kEsWaves][4];
   const EbBlock blk = blocks[blockIdx.x];
   const EbFrame& fr = frames[blk.frame];
-  const int64_t N = fr.n_atoms, K = fr.n_k, chunk = fr.chunk;
-  const int64_t i = blk.local % N, slice = blk.local / N;
-  const T* __restrict__ kvec = kvec_all + 3 * fr.k0;
-  const T* __restrict__ G = G_all + fr.k0;
-  const T* __restrict__ Sc = Sc_all + fr.k0;
-  const T* __restrict__ Ss = Ss_all + fr.k0;
-  T* __restrict__ part = (T*)(work + fr.slice_part);
-  const int64_t k0 = slice * chunk, k1 = min<int64_t>(K, k0 + chunk);
-  const AtomRecord<T> p = rec_all[fr.atom0 + i];
-  T phi = T(0), bx = T(0), by = T(0), bz = T(0);
-  for (int64_t k = k0 + threadIdx.x; k < k1; k += kEsBlock) {
-    const T gk = G[k];
-    if (gk == T(0)) continue;  // exact: the term is G(k) times a finite sum
-    const T kx = kvec[3 * k], ky = kvec[3 * k + 1], kz = kvec[3 * k + 2];
-    const T sc = Sc[k], ss = Ss[k];
-    T s, c;
-    dipole_phase3(kx, ky, kz, p.x, p.y, p.z, s, c);
-    phi += gk * (c * sc + s * ss);
-    const T b = gk * (c * ss - s * sc);
-    bx += b * kx;
-    by += b * ky;
-    bz += b * kz;
-  }
-  phi = wave_sum(phi), bx = wave_sum(bx), by = wave_sum(by), bz = wave_sum(bz);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) red[wave][0] = phi, red[wave][1] = bx, red[wave][2] = by, red[wave][3] = bz;
-  __syncthreads();
-  if (threadIdx.x < 4) {
-    T s = T(0);
-#pragma unroll
-    for (int w = 0; w < kEsWaves; ++w) s += red[w][threadIdx.x];
-    part[(slice * N + i) * 4 + threadIdx.x] = s;
-  }
+  const int64_t N = fr.n_atoms;
+  es_atom_body<T>(blk.local % N, blk.local / N, N, fr.n_k, fr.chunk, rec_all + fr.atom0, kvec_all + 3 * fr.k0, G_all + fr.k0,
+                  Sc_all + fr.k0, Ss_all + fr.k0, (T*)(work + fr.slice_part));
 }
 
-// ---- 4. pair rows: 16 lanes per atom row, the 7^3 shift table of the block's frame in LDS ------------------------------------
-// (ewald_step_rows_kernel with the frame's slices: the partners and the row pointers are local to the frame)
+// one shift table per row block: the table of the block's frame
 template <typename T, int PFAST, bool CELL>
 __global__ __launch_bounds__(kEsBlock) void ewald_batch_rows_kernel(SRPot sp, FastRS cf, const EbFrame* __restrict__ frames,
                                                                    const EbBlock* __restrict__ blocks,
@@ -273,274 +161,48 @@ __global__ __launch_bounds__(kEsBlock) void ewald_batch_rows_kernel(SRPot sp, Fa
                                                                    const int* __restrict__ ent32_all,
                                                                    const AtomRecord<T>* __restrict__ rec_all,
                                                                    const T* __restrict__ cells, T scale, double* __restrict__ work) {
-  __shared__ AtomRecord<T> shift_tab[kShiftTableSize];
-  __shared__ double red[kEsWaves][9];
-  const int tid = threadIdx.x;
   const EbBlock blk = blocks[blockIdx.x];
   const EbFrame& fr = frames[blk.frame];
-  const int64_t N = fr.n_atoms;
-  const int* __restrict__ row_ptr = row_ptr_all + fr.rp0;
-  const int* __restrict__ ent32 = ent32_all + fr.ent0;
-  const AtomRecord<T>* __restrict__ rec = rec_all + fr.atom0;
-  T* __restrict__ row_out = (T*)(work + fr.row_out);
-  {
-    const T* __restrict__ cell = cells + 9 * int64_t(blk.frame);
-    T A[9];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) A[k] = cell[k];
-    fill_shift_table<T, kEsBlock>(shift_tab, A);
-  }
-  __syncthreads();
-  const T c_inv2s2 = T(cf.inv_2s2), c1 = T(cf.c1), cpref = T(cf.pref);
-  const int sub = tid % 16;
-  int64_t a = int64_t(blk.local) * kEsRowsPerBlock + tid / 16;
-  const bool valid = a < N;
-  if (!valid) a = N - 1;
-  const int* __restrict__ rp = row_ptr + 2 * a;
-  const int beg = rp[0], mid = rp[1], end = valid ? rp[2] : beg;
-  const AtomRecord<T> pa = rec[a];
-  const unsigned last_atom = unsigned(N - 1);
-  T pot = T(0), fx = T(0), fy = T(0), fz = T(0);
-  T w00 = T(0), w01 = T(0), w02 = T(0), w10 = T(0), w11 = T(0), w12 = T(0), w20 = T(0), w21 = T(0), w22 = T(0);
-  for (int base = beg; base < end; base += 16) {
-    const int e = base + sub;
-    const bool ok = e < end;
-    const unsigned word = unsigned(ent32[ok ? e : beg]);  // (beg < end here: a real entry, left out of the sums)
-    // (a valid stream never needs the two clamps; they keep a damaged one inside the frame's records and the table)
-    const unsigned o = min(word & unsigned(kCompactMaxAtoms - 1), last_atom);
-    const unsigned code = min(word >> kCompactAtomBits, unsigned(kShiftTableSize - 1));
-    const AtomRecord<T> po = rec[o];
-    const AtomRecord<T> sh = shift_tab[code];
-    const T vx = (po.x - pa.x) + sh.x, vy = (po.y - pa.y) + sh.y, vz = (po.z - pa.z) + sh.z;
-    const T d2 = vx * vx + vy * vy + vz * vz;
-    T v, dvd;  // v_SR(d) and v_SR'(d) / d
-    if constexpr (PFAST > 0) {
-      fast_rs_eval<PFAST, true, T>(c_inv2s2, c1, cpref, d2, v, dvd, cf.cheb);
-    } else {
-      const T d = fsqrt(d2);
-      T dv;
-      sr_eval<T, true>(sp, d, v, dv);
-      dvd = dv / d;
-    }
-    if (ok) {
-      pot += po.w * v;
-      const T w = po.w * dvd;
-      const T ex = w * vx, ey = w * vy, ez = w * vz;
-      fx += ex;
-      fy += ey;
-      fz += ez;
-      if (CELL && e < mid) {  // role i: the listed pair, its own shift
-        const int ic = int(code);
-        const T sx = T(ic % kShiftTableBase - kShiftTableRange), sy = T((ic / kShiftTableBase) % kShiftTableBase - kShiftTableRange),
-                sz = T(ic / (kShiftTableBase * kShiftTableBase) - kShiftTableRange);
-        w00 += sx * ex, w01 += sx * ey, w02 += sx * ez;
-        w10 += sy * ex, w11 += sy * ey, w12 += sy * ez;
-        w20 += sz * ex, w21 += sz * ey, w22 += sz * ez;
-      }
-    }
-  }
-  pot = row_sum(pot), fx = row_sum(fx), fy = row_sum(fy), fz = row_sum(fz);
-  if (sub == 0 && valid) {
-    T* o = row_out + 4 * a;
-    const T sq = scale * pa.w;
-    o[0] = scale * pot, o[1] = sq * fx, o[2] = sq * fy, o[3] = sq * fz;
-  }
-  if (CELL) {
-    const int lane = tid & 63, wave = tid >> 6;
-    const double qa = double(pa.w);  // (the rows of a wavefront belong to different atoms: q_a goes in before the wave sum)
-    const double s0 = wave_sum(qa * double(w00)), s1 = wave_sum(qa * double(w01)), s2 = wave_sum(qa * double(w02));
-    const double s3 = wave_sum(qa * double(w10)), s4 = wave_sum(qa * double(w11)), s5 = wave_sum(qa * double(w12));
-    const double s6 = wave_sum(qa * double(w20)), s7 = wave_sum(qa * double(w21)), s8 = wave_sum(qa * double(w22));
-    if (lane == 0) {
-      red[wave][0] = s0, red[wave][1] = s1, red[wave][2] = s2;
-      red[wave][3] = s3, red[wave][4] = s4, red[wave][5] = s5;
-      red[wave][6] = s6, red[wave][7] = s7, red[wave][8] = s8;
-    }
-    __syncthreads();
-    if (tid < 9) {
-      double s = 0.0;
-#pragma unroll
-      for (int w = 0; w < kEsWaves; ++w) s += red[w][tid];
-      work[fr.row_cell + 9 * int64_t(blk.local) + tid] = double(scale) * s;
-    }
-  }
+  es_rows_body<T, PFAST, CELL>(sp, cf, fr.n_atoms, int64_t(blk.local), row_ptr_all + fr.rp0, ent32_all + fr.ent0, rec_all + fr.atom0,
+                               cells + 9 * int64_t(blk.frame), scale, (T*)(work + fr.row_out), work + fr.row_cell);
 }
 
-// ---- 5. per-k cell gradient: 32 lanes per k-vector, the frame's records streamed through LDS -------------------------------
-// (ewald_step_cellk_kernel: k_part[10 b + 3 a + n] = sum over the k-vectors of local block b of gk_a k_n, [10 b + 9] = sum 1/2 G |S|^2)
 template <typename T>
 __global__ __launch_bounds__(kEsBlock) void ewald_batch_cellk_kernel(const EbFrame* __restrict__ frames, const EbBlock* __restrict__ blocks,
                                                                     const AtomRecord<T>* __restrict__ rec_all,
                                                                     const T* __restrict__ kvec_all, const T* __restrict__ G_all,
                                                                     const T* __restrict__ dG_all, const T* __restrict__ Sc_all,
                                                                     const T* __restrict__ Ss_all, double* __restrict__ work) {
-  __shared__ AtomRecord<T> sr[kEsTile];
-  __shared__ double red[kEsKPerBlock][kEsCellK];
   const EbBlock blk = blocks[blockIdx.x];
   const EbFrame& fr = frames[blk.frame];
-  const int64_t N = fr.n_atoms, K = fr.n_k;
-  const AtomRecord<T>* __restrict__ rec = rec_all + fr.atom0;
-  const T* __restrict__ kvec = kvec_all + 3 * fr.k0;
-  const T* __restrict__ G = G_all + fr.k0;
-  const T* __restrict__ dG = dG_all + fr.k0;
-  const T* __restrict__ Sc = Sc_all + fr.k0;
-  const T* __restrict__ Ss = Ss_all + fr.k0;
-  const int al = threadIdx.x % kEsKLanes, kl = threadIdx.x / kEsKLanes;
-  const int64_t k = int64_t(blk.local) * kEsKPerBlock + kl;
-  const bool live = k < K && (G[k] != T(0) || dG[k] != T(0));
-  const int64_t kc = k < K ? k : 0;
-  const T kx = kvec[3 * kc], ky = kvec[3 * kc + 1], kz = kvec[3 * kc + 2];
-  const T lSc = Sc[kc], lSs = Ss[kc];
-  T ax = T(0), ay = T(0), az = T(0);
-  for (int64_t base = 0; base < N; base += kEsTile) {
-    const int n = int(min<int64_t>(kEsTile, N - base));
-    __syncthreads();
-    for (int t = threadIdx.x; t < n; t += kEsBlock) sr[t] = rec[base + t];
-    __syncthreads();
-    if (live)
-      for (int i = al; i < n; i += kEsKLanes) {
-        const AtomRecord<T> r = sr[i];
-        T s, c;
-        dipole_phase3(kx, ky, kz, r.x, r.y, r.z, s, c);
-        const T b = r.w * (c * lSs - s * lSc);
-        ax += b * r.x;
-        ay += b * r.y;
-        az += b * r.z;
-      }
-  }
-#pragma unroll
-  for (int off = kEsKLanes / 2; off > 0; off >>= 1) {
-    ax += __shfl_xor(ax, off, kEsKLanes);
-    ay += __shfl_xor(ay, off, kEsKLanes);
-    az += __shfl_xor(az, off, kEsKLanes);
-  }
-  if (al == 0) {
-    double g[3] = {0.0, 0.0, 0.0}, e = 0.0;
-    const double kd[3] = {double(kx), double(ky), double(kz)};
-    if (live) {
-      const double gk = double(G[kc]), s2 = double(lSc) * double(lSc) + double(lSs) * double(lSs), d = double(dG[kc]) * s2;
-      g[0] = gk * double(ax) + d * kd[0];
-      g[1] = gk * double(ay) + d * kd[1];
-      g[2] = gk * double(az) + d * kd[2];
-      e = 0.5 * gk * s2;
-    }
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-      for (int n = 0; n < 3; ++n) red[kl][3 * a + n] = g[a] * kd[n];
-    red[kl][9] = e;
-  }
-  __syncthreads();
-  if (threadIdx.x < kEsCellK) {
-    double s = 0.0;
-#pragma unroll
-    for (int q = 0; q < kEsKPerBlock; ++q) s += red[q][threadIdx.x];
-    work[fr.k_cell + kEsCellK * int64_t(blk.local) + threadIdx.x] = s;
-  }
+  es_cellk_body<T>(fr.n_atoms, fr.n_k, int64_t(blk.local), rec_all + fr.atom0, kvec_all + 3 * fr.k0, G_all + fr.k0, dG_all + fr.k0,
+                   Sc_all + fr.k0, Ss_all + fr.k0, work + fr.k_cell);
 }
 
-// ---- 6. finish: 16 lanes per atom over the frame's slices (ewald_step_finish_kernel) ----------------------------------------
 template <typename T>
 __global__ __launch_bounds__(kEsBlock) void ewald_batch_finish_kernel(const EbFrame* __restrict__ frames, const EbBlock* __restrict__ blocks,
                                                                      T self_c, double two_bg, const AtomRecord<T>* __restrict__ rec_all,
                                                                      T* __restrict__ forces_all, T* __restrict__ grad_q_all,
                                                                      double* __restrict__ work) {
-  __shared__ double red[kEsWaves];
   const EbBlock blk = blocks[blockIdx.x];
   const EbFrame& fr = frames[blk.frame];
-  const int64_t N = fr.n_atoms;
-  const int n_slices = fr.n_slices;
-  const double* __restrict__ geom = work + fr.geom;
-  const T* __restrict__ part = (const T*)(work + fr.slice_part);
-  const T* __restrict__ row_out = (const T*)(work + fr.row_out);
-  const AtomRecord<T>* __restrict__ rec = rec_all + fr.atom0;
-  T* __restrict__ forces = forces_all + 3 * fr.atom0;
-  T* __restrict__ grad_q = grad_q_all + fr.atom0;
-  const double inv_vol_d = geom[9];
-  double Q = 0.0;
-  if (two_bg != 0.0) Q = es_strided_sum(work + fr.q_part, fr.n_atom_blocks, 1, 0, red);  // (uniform) the same fixed order in every block
-  const T inv_vol = T(inv_vol_d), bg_term = T(two_bg * Q * inv_vol_d);
-  const int sub = threadIdx.x % 16;
-  const int64_t a = int64_t(blk.local) * kEsRowsPerBlock + threadIdx.x / 16;
-  const bool valid = a < N;
-  T phi = T(0), b0 = T(0), b1 = T(0), b2 = T(0);
-  if (valid)
-    for (int s = sub; s < n_slices; s += 16) {
-      const T* __restrict__ p = part + (int64_t(s) * N + a) * 4;
-      phi += p[0], b0 += p[1], b1 += p[2], b2 += p[3];
-    }
-  phi = row_sum(phi), b0 = row_sum(b0), b1 = row_sum(b1), b2 = row_sum(b2);
-  double e = 0.0;
-  if (valid && sub == 0) {
-    const T qa = rec[a].w;
-    const T* __restrict__ r = row_out + 4 * a;
-    const T d = ((inv_vol * phi - self_c * qa) - bg_term) + r[0];
-    grad_q[a] = d;
-    const T qv = qa * inv_vol;
-    forces[3 * a] = r[1] - qv * b0;
-    forces[3 * a + 1] = r[2] - qv * b1;
-    forces[3 * a + 2] = r[3] - qv * b2;
-    e = 0.5 * double(qa) * double(d);
-  }
-  e = block_sum<kEsWaves>(e, red);
-  if (threadIdx.x == 0) work[fr.e_part + blk.local] = e;
+  es_finish_body<T>(fr.n_atoms, fr.n_slices, int64_t(blk.local), self_c, two_bg, work + fr.geom, rec_all + fr.atom0,
+                    (const T*)(work + fr.slice_part), (const T*)(work + fr.row_out), work + fr.q_part, fr.n_atom_blocks,
+                    forces_all + 3 * fr.atom0, grad_q_all + fr.atom0, work + fr.e_part);
 }
 
-// ---- 7. final: one block per frame (ewald_step_final_kernel) ----------------------------------------------------------------
+// one block per frame: no block table
 template <typename T, bool CELL>
 __global__ __launch_bounds__(kEsBlock) void ewald_batch_final_kernel(const EbFrame* __restrict__ frames, double bg,
                                                                     const double* __restrict__ work, T* __restrict__ energies,
                                                                     T* __restrict__ grad_cells) {
-  __shared__ double red[kEsWaves];
-  __shared__ double tot[9 + kEsCellK + 1];
   const int64_t f = blockIdx.x;
   const EbFrame& fr = frames[f];
-  const double* __restrict__ geom = work + fr.geom;
-  const bool bad = geom[10] != 0.0;
-  const double E = es_strided_sum(work + fr.e_part, fr.n_fin_blocks, 1, 0, red);
-  if (threadIdx.x == 0) energies[f] = bad ? T(NAN) : T(E);
-  if (CELL) {
-    for (int j = 0; j < 9; ++j) {
-      const double s = es_strided_sum(work + fr.row_cell, fr.n_row_blocks, 9, j, red);
-      if (threadIdx.x == 0) tot[j] = s;
-    }
-    for (int j = 0; j < kEsCellK; ++j) {
-      const double s = es_strided_sum(work + fr.k_cell, fr.n_k_blocks, kEsCellK, j, red);
-      if (threadIdx.x == 0) tot[9 + j] = s;
-    }
-    {
-      const double s = es_strided_sum(work + fr.q_part, fr.n_atom_blocks, 1, 0, red);
-      if (threadIdx.x == 0) tot[9 + kEsCellK] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < 9) {
-      const int m = threadIdx.x / 3, n = threadIdx.x % 3;
-      const double* Wr = tot;
-      const double* Wk = tot + 9;
-      const double Ek = tot[9 + 9], Q = tot[9 + kEsCellK], inv_vol = geom[9];
-      const double e_v = inv_vol * (Ek - bg * Q * Q);  // what scales with 1/V
-      double chain = 0.0;
-      for (int a = 0; a < 3; ++a) chain += geom[3 * a + m] * Wk[3 * a + n];
-      grad_cells[9 * f + 3 * m + n] = bad ? T(NAN) : T(Wr[3 * m + n] - inv_vol * chain - e_v * geom[3 * n + m]);
-    }
-  }
+  es_final_body<T, CELL>(fr.n_fin_blocks, work + fr.e_part, energies + f, fr.n_row_blocks, work + fr.row_cell, fr.n_k_blocks,
+                         work + fr.k_cell, fr.n_atom_blocks, work + fr.q_part, bg, work + fr.geom, CELL ? grad_cells + 9 * f : nullptr);
 }
 
 // ---- host --------------------------------------------------------------------------------------------------------------------
-template <typename T, int PFAST>
-static void ewald_batch_rows_launch(hipStream_t st, const mipme_ewald_batch_args_t& a, const SRPot& sp, const FastRS& cf, unsigned n_blocks,
-                                    const EbFrame* frames, const EbBlock* blocks) {
-  const T scale = T(a.full_list ? 0.5 : 1.0);
-  if (a.cell_gradient)
-    ewald_batch_rows_kernel<T, PFAST, true><<<n_blocks, kEsBlock, 0, st>>>(sp, cf, frames, blocks, (const int*)a.row_ptr,
-                                                                          (const int*)a.entries, (const AtomRecord<T>*)a.records,
-                                                                          (const T*)a.cells, scale, (double*)a.work);
-  else
-    ewald_batch_rows_kernel<T, PFAST, false><<<n_blocks, kEsBlock, 0, st>>>(sp, cf, frames, blocks, (const int*)a.row_ptr,
-                                                                           (const int*)a.entries, (const AtomRecord<T>*)a.records,
-                                                                           (const T*)a.cells, scale, (double*)a.work);
-}
-
 template <typename T>
 static int ewald_batch_t(const mipme_ewald_batch_args_t& a, const EbLayout& L, const KPot& kp, const SRPot& sp) {
   hipStream_t st = (hipStream_t)a.stream;
@@ -552,10 +214,7 @@ static int ewald_batch_t(const mipme_ewald_batch_args_t& a, const EbLayout& L, c
   const EbBlock* b_row = b_atom + L.n_atomblk;
   AtomRecord<T>* rec = (AtomRecord<T>*)a.records;
   double* work = (double*)a.work;
-  const FastRS cf = make_fast_rs(sp);
-  double self_c, bg_c;
-  correction_terms(a.pot, self_c, bg_c);
-  const double bg = bg_c - 0.5 * kp.k0;  // (the k = 0 term of the eager sum: v_LR(0) Q / V per atom, non-zero for p > 3)
+  const EsTerms t = es_terms(a.pot, kp, sp);
   ewald_batch_prep_kernel<T><<<unsigned(L.n_prep), kEsBlock, 0, st>>>(
       kp, frames, b_prep, (const T*)a.cells, (const int*)a.frequencies, (const int*)a.multiplicities, a.lr_wavelength,
       (const T*)a.positions, (const T*)a.charges, (T*)a.kvectors, (T*)a.G, cell ? (T*)a.dG : nullptr, rec, work, (int*)a.status);
@@ -568,24 +227,23 @@ static int ewald_batch_t(const mipme_ewald_batch_args_t& a, const EbLayout& L, c
                                                                           (const T*)a.s_cos, (const T*)a.s_sin, work);
     MIPME_LAUNCH_CHECK();
   }
-  switch (fast_rs_exponent(sp)) {
-    case 1: ewald_batch_rows_launch<T, 1>(st, a, sp, cf, unsigned(L.n_rowblk), frames, b_row); break;
-    case 6: ewald_batch_rows_launch<T, 6>(st, a, sp, cf, unsigned(L.n_rowblk), frames, b_row); break;
-    default: ewald_batch_rows_launch<T, 0>(st, a, sp, cf, unsigned(L.n_rowblk), frames, b_row); break;
-  }
+  es_rows_dispatch(sp, cell, [&](auto pfast, auto with_cell) {
+    ewald_batch_rows_kernel<T, pfast(), with_cell()><<<unsigned(L.n_rowblk), kEsBlock, 0, st>>>(
+        sp, t.cf, frames, b_row, (const int*)a.row_ptr, (const int*)a.entries, rec, (const T*)a.cells, T(a.full_list ? 0.5 : 1.0), work);
+  });
   MIPME_LAUNCH_CHECK();
   if (cell && L.n_kblk > 0) {
     ewald_batch_cellk_kernel<T><<<unsigned(L.n_kblk), kEsBlock, 0, st>>>(frames, b_k, rec, (const T*)a.kvectors, (const T*)a.G,
                                                                         (const T*)a.dG, (const T*)a.s_cos, (const T*)a.s_sin, work);
     MIPME_LAUNCH_CHECK();
   }
-  ewald_batch_finish_kernel<T><<<unsigned(L.n_rowblk), kEsBlock, 0, st>>>(frames, b_row, T(self_c), 2.0 * bg, rec, (T*)a.forces,
+  ewald_batch_finish_kernel<T><<<unsigned(L.n_rowblk), kEsBlock, 0, st>>>(frames, b_row, T(t.self_c), 2.0 * t.bg, rec, (T*)a.forces,
                                                                          (T*)a.grad_charges, work);
   MIPME_LAUNCH_CHECK();
   if (cell)
-    ewald_batch_final_kernel<T, true><<<unsigned(a.n_frames), kEsBlock, 0, st>>>(frames, bg, work, (T*)a.energies, (T*)a.grad_cells);
+    ewald_batch_final_kernel<T, true><<<unsigned(a.n_frames), kEsBlock, 0, st>>>(frames, t.bg, work, (T*)a.energies, (T*)a.grad_cells);
   else
-    ewald_batch_final_kernel<T, false><<<unsigned(a.n_frames), kEsBlock, 0, st>>>(frames, bg, work, (T*)a.energies, nullptr);
+    ewald_batch_final_kernel<T, false><<<unsigned(a.n_frames), kEsBlock, 0, st>>>(frames, t.bg, work, (T*)a.energies, nullptr);
   MIPME_LAUNCH_CHECK();
   return MIPME_OK;
 }
@@ -633,13 +291,7 @@ int mipme_ewald_batch(const mipme_ewald_batch_args_t* in) {
   int rc = load_args(in, a, MIPME_EWALD_BATCH_VERSION, who);
   if (rc) return rc;
   // everything the arguments alone decide, before anything touches a device
-  MIPME_REQUIRE(a.dtype == MIPME_F32 || a.dtype == MIPME_F64, "%s: invalid dtype %d", who, int(a.dtype));
-  MIPME_REQUIRE(a.pot != nullptr, "%s: potential descriptor is NULL", who);
-  MIPME_REQUIRE(a.pot->smearing > 0,
-                "%s: the potential has no smearing (`smearing` is %g): the Ewald sum needs a range-separated potential", who,
-                a.pot->smearing);
-  MIPME_REQUIRE(!(a.pot->exclusion_radius > 0) || a.pot->exclusion_degree >= 1, "%s: exclusion_degree must be >= 1, got %d", who,
-                int(a.pot->exclusion_degree));
+  if ((rc = check_ewald_pot(a.dtype, a.pot, who))) return rc;
   MIPME_REQUIRE((a.shift_format & 0xff) == 2 && !(a.shift_format & MIPME_ROWS_PADDED),
                 "%s: the rows are read as 4-byte entries, other | code << 22 (shift_format 2), got shift_format %d", who,
                 int(a.shift_format));

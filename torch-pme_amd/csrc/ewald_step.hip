@@ -26,17 +26,19 @@
 // bg = background term minus half the k = 0 limit of v_LR (non-zero for p > 3, where the eager sum keeps its k = 0 term): both
 // are a constant times Q / V per atom.  No atomics and no workgroup that waits for another: every cross-block sum is float64
 // block partials added in index order by a later launch, so equal inputs give equal bits, in fp32 too.
+//
+// Each of the seven computations is written once, as a body in ewald_step_bodies.h (es_prep_body ... es_final_body); the kernels
+// below hand their body the arguments of the one system and the block index of the grid, those of ewald_batch.hip the slices of
+// a frame and its local block index.
 #include <cmath>
 
-#include "dipole_device.h"
+#include "ewald_step_bodies.h"
 #include "ewald_step_device.h"
 #include "host.h"
-#include "kpot.h"
-#include "rows_body.h"
 
 namespace mipme {
 
-// ---- 1. prep: k table and geometry (blocks < n_table_blocks), records and charge partials (the blocks behind them) ---------
+// ---- the kernels: the bodies of ewald_step_bodies.h with the arguments of one system and the block index of the grid -------
 template <typename T>
 __global__ __launch_bounds__(kEsBlock) void ewald_step_prep_kernel(KPot kp, int64_t N, int64_t K, int n_table_blocks,
                                                                   const T* __restrict__ cell, const int* __restrict__ freq,
@@ -46,294 +48,42 @@ __global__ __launch_bounds__(kEsBlock) void ewald_step_prep_kernel(KPot kp, int6
                                                                   T* __restrict__ dG, AtomRecord<T>* __restrict__ rec,
                                                                   double* __restrict__ q_part, double* __restrict__ geom,
                                                                   int* __restrict__ status) {
-  __shared__ double red[kEsWaves];
-  if (int(blockIdx.x) >= n_table_blocks) {  // (uniform per block)
-    const int64_t a = int64_t(int(blockIdx.x) - n_table_blocks) * kEsBlock + threadIdx.x;
-    double qa = 0.0;
-    if (a < N) {
-      const T qv = q[a];
-      rec[a] = AtomRecord<T>{pos[3 * a], pos[3 * a + 1], pos[3 * a + 2], qv};
-      qa = double(qv);
-    }
-    const double s = block_sum<kEsWaves>(qa, red);
-    if (threadIdx.x == 0) q_part[int(blockIdx.x) - n_table_blocks] = s;
-    return;
-  }
-  double A[9];
-  const EsCell g = es_invert_cell(cell, A);
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    // A^-1 = (A^-T)^T, row-major
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-      for (int c = 0; c < 3; ++c) geom[3 * r + c] = g.recip[3 * c + r];
-    geom[9] = g.inv_vol;
-    geom[10] = g.bad ? 1.0 : 0.0;
-    // bit 0: the eager call would choose another k grid for this cell, ns_d = ceil(|a_d| / lr_wavelength)
-    const int ns[3] = {ns0, ns1, ns2};
-    int st = g.bad ? 2 : 0;
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-      const double norm = sqrt(A[3 * d] * A[3 * d] + A[3 * d + 1] * A[3 * d + 1] + A[3 * d + 2] * A[3 * d + 2]);
-      if (!(ceil(norm / lr_wavelength) == double(ns[d]))) st |= 1;
-    }
-    status[0] = st;
-  }
-  const int64_t k = int64_t(blockIdx.x) * kEsBlock + threadIdx.x;
-  if (k >= K) return;
-  double kv[3] = {0.0, 0.0, 0.0}, v = 0.0, dv = 0.0;
-  if (!g.bad) {  // (a singular cell: a table of zeros, and the final launch writes NaN as the energy)
-    const double f0 = double(freq[3 * k]), f1 = double(freq[3 * k + 1]), f2 = double(freq[3 * k + 2]);
-#pragma unroll
-    for (int n = 0; n < 3; ++n) kv[n] = (2.0 * kPi) * (f0 * g.recip[n] + f1 * g.recip[3 + n] + f2 * g.recip[6 + n]);
-    lr_kernel_dev(kp, kv[0] * kv[0] + kv[1] * kv[1] + kv[2] * kv[2], v, dv);
-    const double m = double(mult[k]);
-    v *= m;
-    dv *= m;
-  }
-  kvec[3 * k] = T(kv[0]), kvec[3 * k + 1] = T(kv[1]), kvec[3 * k + 2] = T(kv[2]);
-  G[k] = T(v);
-  if (dG) dG[k] = T(dv);
+  es_prep_body<T>(kp, N, K, n_table_blocks, int(blockIdx.x), cell, freq, mult, ns0, ns1, ns2, lr_wavelength, pos, q, kvec, G, dG, rec,
+                  q_part, geom, status);
 }
 
-// ---- 2. structure factors: 32 lanes per k-vector, the records streamed through LDS -------------------------------------------
-// The mapping of ewald_structure_kernel (ewald.hip) for one channel, with the phase of the atom and cell kernels below
-// (dipole_phase3: in float the phase is formed and reduced in double).  That kernel itself rounds a float phase before sincosf,
-// and then S and the (c, s) of the later launches disagree by |k.r| ulps per term: c S_s - s S_c of an atom with its own
-// contribution to S no longer cancels, which is the whole force on a single atom.
 template <typename T>
 __global__ __launch_bounds__(kEsBlock) void ewald_step_structure_kernel(int64_t N, int64_t K, const AtomRecord<T>* __restrict__ rec,
                                                                        const T* __restrict__ kvec, T* __restrict__ Sc,
                                                                        T* __restrict__ Ss) {
-  __shared__ AtomRecord<T> sr[kEsTile];
-  const int al = threadIdx.x % kEsKLanes;
-  const int64_t k = int64_t(blockIdx.x) * kEsKPerBlock + threadIdx.x / kEsKLanes;
-  const bool valid = k < K;
-  const int64_t kc = valid ? k : 0;
-  const T kx = kvec[3 * kc], ky = kvec[3 * kc + 1], kz = kvec[3 * kc + 2];
-  T ac = T(0), as = T(0);
-  for (int64_t base = 0; base < N; base += kEsTile) {
-    const int n = int(min<int64_t>(kEsTile, N - base));
-    __syncthreads();
-    for (int t = threadIdx.x; t < n; t += kEsBlock) sr[t] = rec[base + t];
-    __syncthreads();
-    for (int i = al; i < n; i += kEsKLanes) {
-      const AtomRecord<T> r = sr[i];
-      T s, c;
-      dipole_phase3(kx, ky, kz, r.x, r.y, r.z, s, c);
-      ac += r.w * c;
-      as += r.w * s;
-    }
-  }
-#pragma unroll
-  for (int off = kEsKLanes / 2; off > 0; off >>= 1) {
-    ac += __shfl_xor(ac, off, kEsKLanes);
-    as += __shfl_xor(as, off, kEsKLanes);
-  }
-  if (valid && al == 0) Sc[k] = ac, Ss[k] = as;
+  es_structure_body<T>(N, K, int64_t(blockIdx.x), rec, kvec, Sc, Ss);
 }
 
-// ---- 3. fused atom kernel: block (i, slice), atom i against the k-vectors [slice * chunk, (slice + 1) * chunk) ---------------
-// part[(slice N + i) 4 + c]: c = 0 the potential sum_k G (c S_c + s S_s), c >= 1 the bracket sum_k G k (c S_s - s S_c)
+// block (i, slice) of an N x n_slices grid
 template <typename T>
 __global__ __launch_bounds__(kEsBlock) void ewald_step_atom_kernel(int64_t K, int64_t chunk, const AtomRecord<T>* __restrict__ rec,
                                                                   const T* __restrict__ kvec, const T* __restrict__ G,
                                                                   const T* __restrict__ Sc, const T* __restrict__ Ss,
                                                                   T* __restrict__ part) {
-  __shared__ T red[kEsWaves][4];
-  const int64_t i = blockIdx.x, N = gridDim.x;
-  const int64_t k0 = int64_t(blockIdx.y) * chunk, k1 = min<int64_t>(K, k0 + chunk);
-  const AtomRecord<T> p = rec[i];
-  T phi = T(0), bx = T(0), by = T(0), bz = T(0);
-  for (int64_t k = k0 + threadIdx.x; k < k1; k += kEsBlock) {
-    const T gk = G[k];
-    if (gk == T(0)) continue;  // exact: the term is G(k) times a finite sum
-    const T kx = kvec[3 * k], ky = kvec[3 * k + 1], kz = kvec[3 * k + 2];
-    const T sc = Sc[k], ss = Ss[k];
-    T s, c;
-    dipole_phase3(kx, ky, kz, p.x, p.y, p.z, s, c);
-    phi += gk * (c * sc + s * ss);
-    const T b = gk * (c * ss - s * sc);
-    bx += b * kx;
-    by += b * ky;
-    bz += b * kz;
-  }
-  phi = wave_sum(phi), bx = wave_sum(bx), by = wave_sum(by), bz = wave_sum(bz);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) red[wave][0] = phi, red[wave][1] = bx, red[wave][2] = by, red[wave][3] = bz;
-  __syncthreads();
-  if (threadIdx.x < 4) {
-    T s = T(0);
-#pragma unroll
-    for (int w = 0; w < kEsWaves; ++w) s += red[w][threadIdx.x];
-    part[(int64_t(blockIdx.y) * N + i) * 4 + threadIdx.x] = s;
-  }
+  es_atom_body<T>(int64_t(blockIdx.x), int64_t(blockIdx.y), int64_t(gridDim.x), K, chunk, rec, kvec, G, Sc, Ss, part);
 }
 
-// ---- 4. pair rows ----------------------------------------------------------------------------------------------------------
-// 16 lanes per atom row, 4 rows per wavefront; the 7^3 table of Cartesian shift vectors in LDS, filled from the device cell; per
-// entry one word (other | code << 22) and one 16- or 32-byte record gather (position and charge of the partner).
-//   row_out[4 a]         = scale sum_e q_o v_SR(d_e)                               (scale = 1, or 1/2 for a full list; both roles)
-//   row_out[4 a + 1 + c] = scale q_a sum_e q_o v_SR'(d_e)/d_e (u_e)_c              (= the pair force on a)
-//   cell_part[9 b + 3 m + n] = scale sum over the role-i entries of the rows of block b of S_m q_a q_o v_SR'/d (u_e)_n   (CELL, float64)
-// PFAST: the exponent of fast_rs_eval (range separated, no exclusion: 1 or 6), 0: the general sr_eval
 template <typename T, int PFAST, bool CELL>
 __global__ __launch_bounds__(kEsBlock) void ewald_step_rows_kernel(SRPot sp, FastRS cf, int64_t N, const int* __restrict__ row_ptr,
                                                                   const int* __restrict__ ent32,
                                                                   const AtomRecord<T>* __restrict__ rec, const T* __restrict__ cell,
                                                                   T scale, T* __restrict__ row_out, double* __restrict__ cell_part) {
-  __shared__ AtomRecord<T> shift_tab[kShiftTableSize];
-  __shared__ double red[kEsWaves][9];
-  const int tid = threadIdx.x;
-  {
-    T A[9];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) A[k] = cell[k];
-    fill_shift_table<T, kEsBlock>(shift_tab, A);
-  }
-  __syncthreads();
-  const T c_inv2s2 = T(cf.inv_2s2), c1 = T(cf.c1), cpref = T(cf.pref);
-  const int sub = tid % 16;
-  int64_t a = int64_t(blockIdx.x) * kEsRowsPerBlock + tid / 16;
-  const bool valid = a < N;
-  if (!valid) a = N - 1;
-  const int* __restrict__ rp = row_ptr + 2 * a;
-  const int beg = rp[0], mid = rp[1], end = valid ? rp[2] : beg;
-  const AtomRecord<T> pa = rec[a];
-  const unsigned last_atom = unsigned(N - 1);
-  T pot = T(0), fx = T(0), fy = T(0), fz = T(0);
-  T w00 = T(0), w01 = T(0), w02 = T(0), w10 = T(0), w11 = T(0), w12 = T(0), w20 = T(0), w21 = T(0), w22 = T(0);
-  for (int base = beg; base < end; base += 16) {
-    const int e = base + sub;
-    const bool ok = e < end;
-    const unsigned word = unsigned(ent32[ok ? e : beg]);  // (beg < end here: a real entry, left out of the sums)
-    // (a valid stream never needs the two clamps; they keep a damaged one inside the buffers)
-    const unsigned o = min(word & unsigned(kCompactMaxAtoms - 1), last_atom);
-    const unsigned code = min(word >> kCompactAtomBits, unsigned(kShiftTableSize - 1));
-    const AtomRecord<T> po = rec[o];
-    const AtomRecord<T> sh = shift_tab[code];
-    const T vx = (po.x - pa.x) + sh.x, vy = (po.y - pa.y) + sh.y, vz = (po.z - pa.z) + sh.z;
-    const T d2 = vx * vx + vy * vy + vz * vz;
-    T v, dvd;  // v_SR(d) and v_SR'(d) / d
-    if constexpr (PFAST > 0) {
-      fast_rs_eval<PFAST, true, T>(c_inv2s2, c1, cpref, d2, v, dvd, cf.cheb);
-    } else {
-      const T d = fsqrt(d2);
-      T dv;
-      sr_eval<T, true>(sp, d, v, dv);
-      dvd = dv / d;
-    }
-    if (ok) {
-      pot += po.w * v;
-      const T w = po.w * dvd;
-      const T ex = w * vx, ey = w * vy, ez = w * vz;
-      fx += ex;
-      fy += ey;
-      fz += ez;
-      if (CELL && e < mid) {  // role i: the listed pair, its own shift
-        const int ic = int(code);
-        const T sx = T(ic % kShiftTableBase - kShiftTableRange), sy = T((ic / kShiftTableBase) % kShiftTableBase - kShiftTableRange),
-                sz = T(ic / (kShiftTableBase * kShiftTableBase) - kShiftTableRange);
-        w00 += sx * ex, w01 += sx * ey, w02 += sx * ez;
-        w10 += sy * ex, w11 += sy * ey, w12 += sy * ez;
-        w20 += sz * ex, w21 += sz * ey, w22 += sz * ez;
-      }
-    }
-  }
-  pot = row_sum(pot), fx = row_sum(fx), fy = row_sum(fy), fz = row_sum(fz);
-  if (sub == 0 && valid) {
-    T* o = row_out + 4 * a;
-    const T sq = scale * pa.w;
-    o[0] = scale * pot, o[1] = sq * fx, o[2] = sq * fy, o[3] = sq * fz;
-  }
-  if (CELL) {
-    const int lane = tid & 63, wave = tid >> 6;
-    const double qa = double(pa.w);  // (the rows of a wavefront belong to different atoms: q_a goes in before the wave sum)
-    const double s0 = wave_sum(qa * double(w00)), s1 = wave_sum(qa * double(w01)), s2 = wave_sum(qa * double(w02));
-    const double s3 = wave_sum(qa * double(w10)), s4 = wave_sum(qa * double(w11)), s5 = wave_sum(qa * double(w12));
-    const double s6 = wave_sum(qa * double(w20)), s7 = wave_sum(qa * double(w21)), s8 = wave_sum(qa * double(w22));
-    if (lane == 0) {
-      red[wave][0] = s0, red[wave][1] = s1, red[wave][2] = s2;
-      red[wave][3] = s3, red[wave][4] = s4, red[wave][5] = s5;
-      red[wave][6] = s6, red[wave][7] = s7, red[wave][8] = s8;
-    }
-    __syncthreads();
-    if (tid < 9) {
-      double s = 0.0;
-#pragma unroll
-      for (int w = 0; w < kEsWaves; ++w) s += red[w][tid];
-      cell_part[9 * int64_t(blockIdx.x) + tid] = double(scale) * s;
-    }
-  }
+  es_rows_body<T, PFAST, CELL>(sp, cf, N, int64_t(blockIdx.x), row_ptr, ent32, rec, cell, scale, row_out, cell_part);
 }
 
-// ---- 5. per-k cell gradient: 32 lanes per k-vector, the records streamed through LDS ---------------------------------------
-// gk = dE_raw/dk = dG |S|^2 k + G sum_j q_j r_j (c S_s - s S_c),  E_raw = 1/2 sum G |S|^2  (E_k = E_raw / V).
-//   k_part[10 b + 3 a + n] = sum over the k-vectors of block b of gk_a k_n;   k_part[10 b + 9] = sum 1/2 G |S|^2        (float64)
 template <typename T>
 __global__ __launch_bounds__(kEsBlock) void ewald_step_cellk_kernel(int64_t N, int64_t K, const AtomRecord<T>* __restrict__ rec,
                                                                    const T* __restrict__ kvec, const T* __restrict__ G,
                                                                    const T* __restrict__ dG, const T* __restrict__ Sc,
                                                                    const T* __restrict__ Ss, double* __restrict__ k_part) {
-  __shared__ AtomRecord<T> sr[kEsTile];
-  __shared__ double red[kEsKPerBlock][kEsCellK];
-  const int al = threadIdx.x % kEsKLanes, kl = threadIdx.x / kEsKLanes;
-  const int64_t k = int64_t(blockIdx.x) * kEsKPerBlock + kl;
-  const bool live = k < K && (G[k] != T(0) || dG[k] != T(0));
-  const int64_t kc = k < K ? k : 0;
-  const T kx = kvec[3 * kc], ky = kvec[3 * kc + 1], kz = kvec[3 * kc + 2];
-  const T lSc = Sc[kc], lSs = Ss[kc];
-  T ax = T(0), ay = T(0), az = T(0);
-  for (int64_t base = 0; base < N; base += kEsTile) {
-    const int n = int(min<int64_t>(kEsTile, N - base));
-    __syncthreads();
-    for (int t = threadIdx.x; t < n; t += kEsBlock) sr[t] = rec[base + t];
-    __syncthreads();
-    if (live)
-      for (int i = al; i < n; i += kEsKLanes) {
-        const AtomRecord<T> r = sr[i];
-        T s, c;
-        dipole_phase3(kx, ky, kz, r.x, r.y, r.z, s, c);
-        const T b = r.w * (c * lSs - s * lSc);
-        ax += b * r.x;
-        ay += b * r.y;
-        az += b * r.z;
-      }
-  }
-#pragma unroll
-  for (int off = kEsKLanes / 2; off > 0; off >>= 1) {
-    ax += __shfl_xor(ax, off, kEsKLanes);
-    ay += __shfl_xor(ay, off, kEsKLanes);
-    az += __shfl_xor(az, off, kEsKLanes);
-  }
-  if (al == 0) {
-    double g[3] = {0.0, 0.0, 0.0}, e = 0.0;
-    const double kd[3] = {double(kx), double(ky), double(kz)};
-    if (live) {
-      const double gk = double(G[kc]), s2 = double(lSc) * double(lSc) + double(lSs) * double(lSs), d = double(dG[kc]) * s2;
-      g[0] = gk * double(ax) + d * kd[0];
-      g[1] = gk * double(ay) + d * kd[1];
-      g[2] = gk * double(az) + d * kd[2];
-      e = 0.5 * gk * s2;
-    }
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-      for (int n = 0; n < 3; ++n) red[kl][3 * a + n] = g[a] * kd[n];
-    red[kl][9] = e;
-  }
-  __syncthreads();
-  if (threadIdx.x < kEsCellK) {
-    double s = 0.0;
-#pragma unroll
-    for (int q = 0; q < kEsKPerBlock; ++q) s += red[q][threadIdx.x];
-    k_part[kEsCellK * int64_t(blockIdx.x) + threadIdx.x] = s;
-  }
+  es_cellk_body<T>(N, K, int64_t(blockIdx.x), rec, kvec, G, dG, Sc, Ss, k_part);
 }
 
-// ---- 6. finish -----------------------------------------------------------------------------------------------------------
-// 16 lanes per atom: lane l adds the slices l, l + 16, ... in that order, then the 16 lanes are added by the shuffle tree of the
-// rows (with few atoms there are hundreds of slices: one thread per atom would walk them one dependent load after the other)
 template <typename T>
 __global__ __launch_bounds__(kEsBlock) void ewald_step_finish_kernel(int64_t N, int n_slices, T self_c, double two_bg,
                                                                     const double* __restrict__ geom,
@@ -341,38 +91,11 @@ __global__ __launch_bounds__(kEsBlock) void ewald_step_finish_kernel(int64_t N, 
                                                                     const T* __restrict__ row_out, const double* __restrict__ q_part,
                                                                     int64_t n_q_blocks, T* __restrict__ forces,
                                                                     T* __restrict__ grad_q, double* __restrict__ e_part) {
-  __shared__ double red[kEsWaves];
-  const double inv_vol_d = geom[9];
-  double Q = 0.0;
-  if (two_bg != 0.0) Q = es_strided_sum(q_part, n_q_blocks, 1, 0, red);  // (uniform) the same fixed order in every block
-  const T inv_vol = T(inv_vol_d), bg_term = T(two_bg * Q * inv_vol_d);
-  const int sub = threadIdx.x % 16;
-  const int64_t a = int64_t(blockIdx.x) * kEsRowsPerBlock + threadIdx.x / 16;
-  const bool valid = a < N;
-  T phi = T(0), b0 = T(0), b1 = T(0), b2 = T(0);
-  if (valid)
-    for (int s = sub; s < n_slices; s += 16) {
-      const T* __restrict__ p = part + (int64_t(s) * N + a) * 4;
-      phi += p[0], b0 += p[1], b1 += p[2], b2 += p[3];
-    }
-  phi = row_sum(phi), b0 = row_sum(b0), b1 = row_sum(b1), b2 = row_sum(b2);
-  double e = 0.0;
-  if (valid && sub == 0) {
-    const T qa = rec[a].w;
-    const T* __restrict__ r = row_out + 4 * a;
-    const T d = ((inv_vol * phi - self_c * qa) - bg_term) + r[0];
-    grad_q[a] = d;
-    const T qv = qa * inv_vol;
-    forces[3 * a] = r[1] - qv * b0;
-    forces[3 * a + 1] = r[2] - qv * b1;
-    forces[3 * a + 2] = r[3] - qv * b2;
-    e = 0.5 * double(qa) * double(d);
-  }
-  e = block_sum<kEsWaves>(e, red);
-  if (threadIdx.x == 0) e_part[blockIdx.x] = e;
+  es_finish_body<T>(N, n_slices, int64_t(blockIdx.x), self_c, two_bg, geom, rec, part, row_out, q_part, n_q_blocks, forces, grad_q,
+                    e_part);
 }
 
-// ---- 7. final: one block ----------------------------------------------------------------------------------------------------
+// one block
 template <typename T, bool CELL>
 __global__ __launch_bounds__(kEsBlock) void ewald_step_final_kernel(int64_t n_e_blocks, const double* __restrict__ e_part,
                                                                    T* __restrict__ energy, int64_t n_row_blocks,
@@ -380,52 +103,11 @@ __global__ __launch_bounds__(kEsBlock) void ewald_step_final_kernel(int64_t n_e_
                                                                    const double* __restrict__ k_cell, int64_t n_q_blocks,
                                                                    const double* __restrict__ q_part, double bg,
                                                                    const double* __restrict__ geom, T* __restrict__ grad_cell) {
-  __shared__ double red[kEsWaves];
-  __shared__ double tot[9 + kEsCellK + 1];
-  const bool bad = geom[10] != 0.0;
-  const double E = es_strided_sum(e_part, n_e_blocks, 1, 0, red);
-  if (threadIdx.x == 0) energy[0] = bad ? T(NAN) : T(E);
-  if (CELL) {
-    for (int j = 0; j < 9; ++j) {
-      const double s = es_strided_sum(row_cell, n_row_blocks, 9, j, red);
-      if (threadIdx.x == 0) tot[j] = s;
-    }
-    for (int j = 0; j < kEsCellK; ++j) {
-      const double s = es_strided_sum(k_cell, n_k_blocks, kEsCellK, j, red);
-      if (threadIdx.x == 0) tot[9 + j] = s;
-    }
-    {
-      const double s = es_strided_sum(q_part, n_q_blocks, 1, 0, red);
-      if (threadIdx.x == 0) tot[9 + kEsCellK] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < 9) {
-      const int m = threadIdx.x / 3, n = threadIdx.x % 3;
-      const double* Wr = tot;
-      const double* Wk = tot + 9;
-      const double Ek = tot[9 + 9], Q = tot[9 + kEsCellK], inv_vol = geom[9];
-      const double e_v = inv_vol * (Ek - bg * Q * Q);  // what scales with 1/V
-      double chain = 0.0;
-      for (int a = 0; a < 3; ++a) chain += geom[3 * a + m] * Wk[3 * a + n];
-      grad_cell[3 * m + n] = bad ? T(NAN) : T(Wr[3 * m + n] - inv_vol * chain - e_v * geom[3 * n + m]);
-    }
-  }
+  es_final_body<T, CELL>(n_e_blocks, e_part, energy, n_row_blocks, row_cell, n_k_blocks, k_cell, n_q_blocks, q_part, bg, geom,
+                         grad_cell);
 }
 
 // ---- host --------------------------------------------------------------------------------------------------------------------
-template <typename T, int PFAST>
-static void ewald_step_rows_launch(hipStream_t st, const mipme_ewald_step_args_t& a, const SRPot& sp, const FastRS& cf, const EsWork& w,
-                                   const AtomRecord<T>* rec) {
-  const unsigned blocks = unsigned((a.n_atoms + kEsRowsPerBlock - 1) / kEsRowsPerBlock);
-  const T scale = T(a.full_list ? 0.5 : 1.0);
-  if (a.cell_gradient)
-    ewald_step_rows_kernel<T, PFAST, true><<<blocks, kEsBlock, 0, st>>>(sp, cf, a.n_atoms, (const int*)a.row_ptr, (const int*)a.entries,
-                                                                       rec, (const T*)a.cell, scale, (T*)w.row_out, w.row_cell);
-  else
-    ewald_step_rows_kernel<T, PFAST, false><<<blocks, kEsBlock, 0, st>>>(sp, cf, a.n_atoms, (const int*)a.row_ptr, (const int*)a.entries,
-                                                                        rec, (const T*)a.cell, scale, (T*)w.row_out, nullptr);
-}
-
 template <typename T>
 static int ewald_step_t(const mipme_ewald_step_args_t& a, const KPot& kp, const SRPot& sp) {
   hipStream_t st = (hipStream_t)a.stream;
@@ -433,10 +115,7 @@ static int ewald_step_t(const mipme_ewald_step_args_t& a, const KPot& kp, const 
   const bool cell = a.cell_gradient != 0;
   const EsWork w = es_work_layout(N, K, cell, a.work);
   AtomRecord<T>* rec = (AtomRecord<T>*)a.records;
-  const FastRS cf = make_fast_rs(sp);
-  double self_c, bg_c;
-  correction_terms(a.pot, self_c, bg_c);
-  const double bg = bg_c - 0.5 * kp.k0;  // (the k = 0 term of the eager sum: v_LR(0) Q / V per atom, non-zero for p > 3)
+  const EsTerms t = es_terms(a.pot, kp, sp);
   ewald_step_prep_kernel<T><<<unsigned(w.n_table_blocks + w.n_atom_blocks), kEsBlock, 0, st>>>(
       kp, N, K, int(w.n_table_blocks), (const T*)a.cell, (const int*)a.frequencies, (const int*)a.multiplicities, a.ns[0], a.ns[1],
       a.ns[2], a.lr_wavelength, (const T*)a.positions, (const T*)a.charges, (T*)a.kvectors, (T*)a.G, cell ? (T*)a.dG : nullptr, rec,
@@ -451,11 +130,11 @@ static int ewald_step_t(const mipme_ewald_step_args_t& a, const KPot& kp, const 
         K, chunk, rec, (const T*)a.kvectors, (const T*)a.G, (const T*)a.s_cos, (const T*)a.s_sin, (T*)w.slice_part);
     MIPME_LAUNCH_CHECK();
   }
-  switch (fast_rs_exponent(sp)) {
-    case 1: ewald_step_rows_launch<T, 1>(st, a, sp, cf, w, rec); break;
-    case 6: ewald_step_rows_launch<T, 6>(st, a, sp, cf, w, rec); break;
-    default: ewald_step_rows_launch<T, 0>(st, a, sp, cf, w, rec); break;
-  }
+  es_rows_dispatch(sp, cell, [&](auto pfast, auto with_cell) {
+    ewald_step_rows_kernel<T, pfast(), with_cell()><<<unsigned(w.n_fin_blocks), kEsBlock, 0, st>>>(
+        sp, t.cf, N, (const int*)a.row_ptr, (const int*)a.entries, rec, (const T*)a.cell, T(a.full_list ? 0.5 : 1.0), (T*)w.row_out,
+        with_cell() ? w.row_cell : nullptr);
+  });
   MIPME_LAUNCH_CHECK();
   if (cell && K > 0) {
     ewald_step_cellk_kernel<T><<<unsigned(w.n_k_blocks), kEsBlock, 0, st>>>(N, K, rec, (const T*)a.kvectors, (const T*)a.G,
@@ -463,18 +142,18 @@ static int ewald_step_t(const mipme_ewald_step_args_t& a, const KPot& kp, const 
                                                                            w.k_cell);
     MIPME_LAUNCH_CHECK();
   }
-  ewald_step_finish_kernel<T><<<unsigned(w.n_fin_blocks), kEsBlock, 0, st>>>(N, int(w.n_slices), T(self_c), 2.0 * bg, w.geom, rec,
+  ewald_step_finish_kernel<T><<<unsigned(w.n_fin_blocks), kEsBlock, 0, st>>>(N, int(w.n_slices), T(t.self_c), 2.0 * t.bg, w.geom, rec,
                                                                             (const T*)w.slice_part, (const T*)w.row_out, w.q_part,
                                                                             w.n_atom_blocks, (T*)a.forces, (T*)a.grad_charges,
                                                                             w.e_part);
   MIPME_LAUNCH_CHECK();
   if (cell)
     ewald_step_final_kernel<T, true><<<1, kEsBlock, 0, st>>>(w.n_fin_blocks, w.e_part, (T*)a.energy, w.n_row_blocks, w.row_cell,
-                                                            w.n_k_blocks, w.k_cell, w.n_atom_blocks, w.q_part, bg, w.geom,
+                                                            w.n_k_blocks, w.k_cell, w.n_atom_blocks, w.q_part, t.bg, w.geom,
                                                             (T*)a.grad_cell);
   else
     ewald_step_final_kernel<T, false><<<1, kEsBlock, 0, st>>>(w.n_fin_blocks, w.e_part, (T*)a.energy, 0, nullptr, 0, nullptr, 0, nullptr,
-                                                             bg, w.geom, nullptr);
+                                                             t.bg, w.geom, nullptr);
   MIPME_LAUNCH_CHECK();
   return MIPME_OK;
 }
@@ -496,13 +175,7 @@ int mipme_ewald_step(const mipme_ewald_step_args_t* in) {
   int rc = load_args(in, a, MIPME_EWALD_STEP_VERSION, who);
   if (rc) return rc;
   // everything the arguments alone decide, before anything touches a device
-  MIPME_REQUIRE(a.dtype == MIPME_F32 || a.dtype == MIPME_F64, "%s: invalid dtype %d", who, int(a.dtype));
-  MIPME_REQUIRE(a.pot != nullptr, "%s: potential descriptor is NULL", who);
-  MIPME_REQUIRE(a.pot->smearing > 0,
-                "%s: the potential has no smearing (`smearing` is %g): the Ewald sum needs a range-separated potential", who,
-                a.pot->smearing);
-  MIPME_REQUIRE(!(a.pot->exclusion_radius > 0) || a.pot->exclusion_degree >= 1, "%s: exclusion_degree must be >= 1, got %d", who,
-                int(a.pot->exclusion_degree));
+  if ((rc = check_ewald_pot(a.dtype, a.pot, who))) return rc;
   MIPME_REQUIRE(a.n_k >= 0 && a.n_k <= kEsMaxK, "%s: n_k must be >= 0, got %lld", who, (long long)a.n_k);
   if ((rc = check_step_rows(a.shift_format, a.n_atoms, who))) return rc;
   MIPME_REQUIRE(std::isfinite(a.lr_wavelength) && a.lr_wavelength > 0 && a.ns[0] >= 1 && a.ns[1] >= 1 && a.ns[2] >= 1,

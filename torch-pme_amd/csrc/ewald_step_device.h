@@ -1,13 +1,17 @@
 // What the Ewald step (ewald_step.hip) and its batched form (ewald_batch.hip) share: the block shapes, the slice rule of the atom
-// kernel, the layout of the float64 work area of ONE system, the fixed-order strided sum and the float64 cell inversion (cell_invert.h).  The
-// batch lays the work areas of its frames one behind the other, each exactly as the single step lays out its own.
+// kernel, the layout of the float64 work area of ONE system, the fixed-order strided sum and the float64 cell inversion (cell_invert.h),
+// and on the host the checks of the potential, its constants and the choice of the rows kernel.  The batch lays the work areas
+// of its frames one behind the other, each exactly as the single step lays out its own.  The bodies of the seven kernels are
+// in ewald_step_bodies.h.
 #pragma once
 
 #include <algorithm>
 #include <cstdint>
+#include <type_traits>
 
 #include "cell_invert.h"  // es_invert_cell: the float64 cell inversion
 #include "host.h"
+#include "kpot.h"
 #include "rows_body.h"
 
 namespace mipme {
@@ -62,6 +66,49 @@ static EsWork es_work_layout(int64_t N, int64_t K, bool cell, void* base) {
   w.slice_part = slice_part;
   w.total = kEsGeom + w.n_atom_blocks + w.n_fin_blocks + 9 * w.n_row_blocks + kEsCellK * w.n_k_blocks + 4 * N + 4 * N * w.n_slices;
   return w;
+}
+
+// ---- host: what mipme_ewald_step and mipme_ewald_batch check and prepare alike ------------------------------------------------
+// the first refusals of both entry points, in this order
+inline int check_ewald_pot(int dtype, const mipme_potential_t* pot, const char* who) {
+  MIPME_REQUIRE(dtype == MIPME_F32 || dtype == MIPME_F64, "%s: invalid dtype %d", who, int(dtype));
+  MIPME_REQUIRE(pot != nullptr, "%s: potential descriptor is NULL", who);
+  MIPME_REQUIRE(pot->smearing > 0,
+                "%s: the potential has no smearing (`smearing` is %g): the Ewald sum needs a range-separated potential", who,
+                pot->smearing);
+  MIPME_REQUIRE(!(pot->exclusion_radius > 0) || pot->exclusion_degree >= 1, "%s: exclusion_degree must be >= 1, got %d", who,
+                int(pot->exclusion_degree));
+  return MIPME_OK;
+}
+
+// the constants of the potential in the launches: the fast pair function, the self term and the background term
+struct EsTerms {
+  FastRS cf;
+  double self_c, bg;
+};
+inline EsTerms es_terms(const mipme_potential_t* pot, const KPot& kp, const SRPot& sp) {
+  EsTerms t;
+  t.cf = make_fast_rs(sp);
+  double bg_c;
+  correction_terms(pot, t.self_c, bg_c);
+  t.bg = bg_c - 0.5 * kp.k0;  // (the k = 0 term of the eager sum: v_LR(0) Q / V per atom, non-zero for p > 3)
+  return t;
+}
+
+// launch(PFAST, CELL) with the template arguments of the rows kernel as integral constants
+template <typename Launch>
+void es_rows_dispatch(const SRPot& sp, bool cell, Launch&& launch) {
+  auto with_cell = [&](auto pfast) {
+    if (cell)
+      launch(pfast, std::true_type{});
+    else
+      launch(pfast, std::false_type{});
+  };
+  switch (fast_rs_exponent(sp)) {
+    case 1: with_cell(std::integral_constant<int, 1>{}); break;
+    case 6: with_cell(std::integral_constant<int, 6>{}); break;
+    default: with_cell(std::integral_constant<int, 0>{}); break;
+  }
 }
 
 // sum_b p[b * stride + off], b < n: thread t adds b = t, t + 256, ... in that order, then the threads in a fixed order

@@ -1100,6 +1100,71 @@ def _compact_kvectors(freq: np.ndarray, ns):
     return rows, np.where(unpaired[rows], 1.0, 2.0)
 
 
+def _check_explicit_list(who, neighbor_indices, neighbor_shifts, frame=None):
+    """The list rules of the steps that walk 4-byte pair entries.  ``frame``: the index the messages of a batch carry."""
+    pre = "" if frame is None else f"{who}: frame {frame}: "
+    if neighbor_indices.dim() != 2 or neighbor_indices.shape[1] != 2:
+        raise ValueError(f"{pre}`neighbor_indices` must be a tensor with shape [n_pairs, 2], got tensor with shape "
+                         f"{list(neighbor_indices.shape)}")
+    if neighbor_shifts.dim() != 2 or tuple(neighbor_shifts.shape) != (neighbor_indices.shape[0], 3):
+        raise ValueError(f"{pre}`neighbor_shifts` must be a tensor with shape [n_pairs, 3] with n_pairs = "
+                         f"{neighbor_indices.shape[0]}, got tensor with shape {list(neighbor_shifts.shape)}")
+    if neighbor_shifts.numel() > 0:
+        s = neighbor_shifts.detach()
+        if bool((s != s.round()).any()) or float(s.abs().max()) > 3:
+            raise ValueError(f"{pre or who + ': '}the cell shifts must be integers in [-3, 3] (the 4-byte pair entries of the row "
+                             "kernel); wrap the positions into the cell or use a shorter cutoff")
+
+
+def _check_ewald_calculator(who, calculator, instead):
+    """The calculator and potential the Ewald step kernels serve; ``instead``: the class for the mesh calculators."""
+    from .calculators import EwaldCalculator
+    from .potentials import CoulombPotential, InversePowerLawPotential
+
+    if not isinstance(calculator, EwaldCalculator):
+        raise TypeError(f"{who} serves an EwaldCalculator, got a {type(calculator).__name__}: use {instead} for the mesh "
+                        "calculators")
+    pot = calculator.potential
+    if type(pot) not in (CoulombPotential, InversePowerLawPotential):
+        raise TypeError(f"{who}: the kernels know exactly CoulombPotential and InversePowerLawPotential, got a "
+                        f"{type(pot).__name__}; call the calculator eagerly")
+
+
+def _check_ewald_system(who, charges, cell, positions, frame=None, first=None):
+    """Shapes, dtype and atom count of one system of an Ewald step.  In a batch, ``frame`` is its index and ``first`` the tensor
+    whose dtype all frames share."""
+    batch = frame is not None
+    pre = f"{who}: frame {frame}: " if batch else ""
+    if charges.dim() != 2 or charges.shape[1] != 1:
+        raise ValueError(f"{pre or who + ' handles '}a single charge channel, `charges` of shape [n_atoms, 1], got tensor with "
+                         f"shape {list(charges.shape)}")
+    if positions.dim() != 2 or positions.shape[1] != 3 or positions.shape[0] != charges.shape[0]:
+        raise ValueError(f"{pre}`positions` must be a tensor with shape [n_atoms, 3] with n_atoms = {charges.shape[0]} (the "
+                         f"charges), got tensor with shape {list(positions.shape)}")
+    if tuple(cell.shape) != (3, 3):
+        raise ValueError(f"{pre}`cell` must be a tensor with shape [3, 3], got tensor with shape {list(cell.shape)}")
+    shared = positions.dtype == charges.dtype == cell.dtype and (not batch or cell.dtype == first.dtype)
+    if not shared or positions.dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"{pre}`positions`, `charges` and `cell`{' of all frames' if batch else ''} must share one dtype, float32 "
+                         f"or float64, got {positions.dtype}, {charges.dtype} and {cell.dtype}"
+                         + (f" (frame 0: {first.dtype})" if batch else ""))
+    if positions.shape[0] < 1 or positions.shape[0] > (1 << 22):
+        raise ValueError(f"{pre + 'a frame holds ' if batch else who + ' handles '}1 to 2^22 atoms (the 4-byte pair entries of the "
+                         f"row kernel), got {positions.shape[0]}")
+
+
+def _ewald_kgrid(cell, lr_wavelength):
+    """``(ns, frequencies (K, 3) int32, multiplicities (K,) int32)`` of the k grid an Ewald step freezes for ``cell``: the integer
+    frequencies as the eager call forms them (ValueError for a singular cell), one of every pair +-k."""
+    from .calculators import _integer_frequencies
+
+    freq, _ = _integer_frequencies(cell.detach(), lr_wavelength, None)
+    ns = GraphedEwaldStep._ns_of(cell, lr_wavelength)
+    f = freq.cpu().numpy()
+    rows, weight = _compact_kvectors(f, ns)
+    return ns, np.rint(f[rows]).astype(np.int32).reshape(-1, 3), weight.astype(np.int32)
+
+
 class GraphedDipoleStep(_ExplicitListStep):
     """``E, F, dE_dmu = step(positions, dipoles)`` for a :class:`~torchpme_amd.CalculatorDipole`, replayed from one HIP graph: the
     MD form of the eager call for a fixed neighbour list and cell (dipolar fluids, polarisable models).
@@ -1152,7 +1217,7 @@ class GraphedDipoleStep(_ExplicitListStep):
         if positions.shape[0] < 1 or positions.shape[0] > (1 << 22):
             raise ValueError(f"GraphedDipoleStep handles 1 to 2^22 atoms (the 4-byte pair entries of the row kernel), got "
                              f"{positions.shape[0]}")
-        self._check_list(neighbor_indices, neighbor_shifts)
+        _check_explicit_list("GraphedDipoleStep", neighbor_indices, neighbor_shifts)
         for t, name in ((positions, "positions"), (dipoles, "dipoles"), (cell, "cell"), (neighbor_indices, "neighbor_indices"),
                         (neighbor_shifts, "neighbor_shifts")):
             _lib.require_device(t, name)
@@ -1206,20 +1271,6 @@ class GraphedDipoleStep(_ExplicitListStep):
         self._warmup = max(1, int(warmup))
         self._capture(neighbor_indices, neighbor_shifts)
 
-    @staticmethod
-    def _check_list(neighbor_indices, neighbor_shifts):
-        if neighbor_indices.dim() != 2 or neighbor_indices.shape[1] != 2:
-            raise ValueError(f"`neighbor_indices` must be a tensor with shape [n_pairs, 2], got tensor with shape "
-                             f"{list(neighbor_indices.shape)}")
-        if neighbor_shifts.dim() != 2 or tuple(neighbor_shifts.shape) != (neighbor_indices.shape[0], 3):
-            raise ValueError(f"`neighbor_shifts` must be a tensor with shape [n_pairs, 3] with n_pairs = {neighbor_indices.shape[0]}, "
-                             f"got tensor with shape {list(neighbor_shifts.shape)}")
-        if neighbor_shifts.numel() > 0:
-            s = neighbor_shifts.detach()
-            if bool((s != s.round()).any()) or float(s.abs().max()) > 3:
-                raise ValueError("GraphedDipoleStep: the cell shifts must be integers in [-3, 3] (the 4-byte pair entries of the row "
-                                 "kernel); wrap the positions into the cell or use a shorter cutoff")
-
     def _launch(self):
         with _lib.on_device(self.device):
             a = _lib.DipoleStepArgs(
@@ -1236,7 +1287,7 @@ class GraphedDipoleStep(_ExplicitListStep):
     def recapture(self, neighbor_indices, neighbor_shifts, positions: torch.Tensor | None = None,
                   dipoles: torch.Tensor | None = None) -> None:
         """New neighbour list: rebuild the pair topology and capture the step again; every other buffer is kept."""
-        self._check_list(neighbor_indices, neighbor_shifts)
+        _check_explicit_list("GraphedDipoleStep", neighbor_indices, neighbor_shifts)
         self._capture(neighbor_indices, neighbor_shifts, [(self.pos, positions), (self.mu, dipoles)])
 
     def __call__(self, positions: torch.Tensor | None = None, dipoles: torch.Tensor | None = None):
@@ -1291,34 +1342,12 @@ class GraphedEwaldStep(_ExplicitListStep):
 
     def __init__(self, calculator, charges, cell, positions, neighbor_indices, neighbor_shifts, cell_gradient: bool = False,
                  warmup: int = 3):
-        from .calculators import EwaldCalculator, _integer_frequencies
-        from .potentials import CoulombPotential, InversePowerLawPotential
-
-        if not isinstance(calculator, EwaldCalculator):
-            raise TypeError(f"GraphedEwaldStep serves an EwaldCalculator, got a {type(calculator).__name__}: use GraphedEnergyForces "
-                            "for the mesh calculators")
-        pot = calculator.potential
-        if type(pot) not in (CoulombPotential, InversePowerLawPotential):
-            raise TypeError(f"GraphedEwaldStep: the kernels know exactly CoulombPotential and InversePowerLawPotential, got a "
-                            f"{type(pot).__name__}; call the calculator eagerly")
-        if charges.dim() != 2 or charges.shape[1] != 1:
-            raise ValueError(f"GraphedEwaldStep handles a single charge channel, `charges` of shape [n_atoms, 1], got tensor with "
-                             f"shape {list(charges.shape)}")
-        if positions.dim() != 2 or positions.shape[1] != 3 or positions.shape[0] != charges.shape[0]:
-            raise ValueError(f"`positions` must be a tensor with shape [n_atoms, 3] with n_atoms = {charges.shape[0]} (the charges), "
-                             f"got tensor with shape {list(positions.shape)}")
-        if tuple(cell.shape) != (3, 3):
-            raise ValueError(f"`cell` must be a tensor with shape [3, 3], got tensor with shape {list(cell.shape)}")
-        if not (positions.dtype == charges.dtype == cell.dtype) or positions.dtype not in (torch.float32, torch.float64):
-            raise ValueError(f"`positions`, `charges` and `cell` must share one dtype, float32 or float64, got {positions.dtype}, "
-                             f"{charges.dtype} and {cell.dtype}")
-        if positions.shape[0] < 1 or positions.shape[0] > (1 << 22):
-            raise ValueError(f"GraphedEwaldStep handles 1 to 2^22 atoms (the 4-byte pair entries of the row kernel), got "
-                             f"{positions.shape[0]}")
-        self._check_list(neighbor_indices, neighbor_shifts)
+        who = "GraphedEwaldStep"
+        _check_ewald_calculator(who, calculator, "GraphedEnergyForces")
+        _check_ewald_system(who, charges, cell, positions)
+        _check_explicit_list(who, neighbor_indices, neighbor_shifts)
         self.lr_wavelength = float(calculator.lr_wavelength)
-        # (raises ValueError for a singular cell; the frequencies as the eager call forms them)
-        freq, _ = _integer_frequencies(cell.detach(), self.lr_wavelength, None)
+        self.ns, freq, mult = _ewald_kgrid(cell, self.lr_wavelength)
         for t, name in ((positions, "positions"), (charges, "charges"), (cell, "cell"), (neighbor_indices, "neighbor_indices"),
                         (neighbor_shifts, "neighbor_shifts")):
             _lib.require_device(t, name)
@@ -1329,15 +1358,11 @@ class GraphedEwaldStep(_ExplicitListStep):
         device, dtype = positions.device, positions.dtype
         self.device, self.dtype, self._dt = device, dtype, _lib.dtype_code(dtype)
         N = self.n_atoms = positions.shape[0]
-        self._desc = pot._descriptor()
+        self._desc = calculator.potential._descriptor()
         new = lambda *shape, dt=dtype: torch.empty(shape, dtype=dt, device=device)  # noqa: E731
         self.cell = cell.detach().clone().contiguous()
-        self.ns = self._ns_of(cell, self.lr_wavelength)
-        f = freq.cpu().numpy()
-        rows, weight = _compact_kvectors(f, self.ns)
-        K = self.n_k = int(len(rows))
-        self._freq = torch.tensor(np.rint(f[rows]).astype(np.int32).reshape(K, 3), device=device)
-        self._mult = torch.tensor(weight.astype(np.int32), device=device)
+        K = self.n_k = int(len(mult))
+        self._freq, self._mult = torch.tensor(freq, device=device), torch.tensor(mult, device=device)
         self._kvec, self._G, self._Sc, self._Ss = new(max(K, 1), 3), new(max(K, 1)), new(max(K, 1)), new(max(K, 1))
         self._dG = new(max(K, 1)) if self.cell_gradient else None
         self.pos = positions.detach().clone().contiguous()
@@ -1360,20 +1385,6 @@ class GraphedEwaldStep(_ExplicitListStep):
         the one of the construction cell (bit 0 of :attr:`status` clear), decided on the host."""
         return self._ns_of(cell, self.lr_wavelength) == self.ns
 
-    @staticmethod
-    def _check_list(neighbor_indices, neighbor_shifts):
-        if neighbor_indices.dim() != 2 or neighbor_indices.shape[1] != 2:
-            raise ValueError(f"`neighbor_indices` must be a tensor with shape [n_pairs, 2], got tensor with shape "
-                             f"{list(neighbor_indices.shape)}")
-        if neighbor_shifts.dim() != 2 or tuple(neighbor_shifts.shape) != (neighbor_indices.shape[0], 3):
-            raise ValueError(f"`neighbor_shifts` must be a tensor with shape [n_pairs, 3] with n_pairs = {neighbor_indices.shape[0]}, "
-                             f"got tensor with shape {list(neighbor_shifts.shape)}")
-        if neighbor_shifts.numel() > 0:
-            s = neighbor_shifts.detach()
-            if bool((s != s.round()).any()) or float(s.abs().max()) > 3:
-                raise ValueError("GraphedEwaldStep: the cell shifts must be integers in [-3, 3] (the 4-byte pair entries of the row "
-                                 "kernel); wrap the positions into the cell or use a shorter cutoff")
-
     def _launch(self):
         with _lib.on_device(self.device):
             a = _lib.EwaldStepArgs(
@@ -1392,7 +1403,7 @@ class GraphedEwaldStep(_ExplicitListStep):
                   charges: torch.Tensor | None = None, cell: torch.Tensor | None = None) -> None:
         """New neighbour list: rebuild the pair topology and capture the step again; the k grid and every buffer are kept.  The
         list is validated before anything of the object changes."""
-        self._check_list(neighbor_indices, neighbor_shifts)
+        _check_explicit_list("GraphedEwaldStep", neighbor_indices, neighbor_shifts)
         self._capture(neighbor_indices, neighbor_shifts, [(self.pos, positions), (self.q, charges), (self.cell, cell)])
 
     def __call__(self, positions: torch.Tensor | None = None, charges: torch.Tensor | None = None,
@@ -1455,17 +1466,8 @@ class GraphedEwaldBatch:
     MAX_FRAMES = 1 << 20
 
     def __init__(self, calculator, frames, cell_gradient: bool = False, warmup: int = 3):
-        from .calculators import EwaldCalculator, _integer_frequencies
-        from .potentials import CoulombPotential, InversePowerLawPotential
-
         who = "GraphedEwaldBatch"
-        if not isinstance(calculator, EwaldCalculator):
-            raise TypeError(f"{who} serves an EwaldCalculator, got a {type(calculator).__name__}: use GraphedFrameBatch for the mesh "
-                            "calculators")
-        pot = calculator.potential
-        if type(pot) not in (CoulombPotential, InversePowerLawPotential):
-            raise TypeError(f"{who}: the kernels know exactly CoulombPotential and InversePowerLawPotential, got a "
-                            f"{type(pot).__name__}; call the calculator eagerly")
+        _check_ewald_calculator(who, calculator, "GraphedFrameBatch")
         frames = [tuple(fr) for fr in frames]
         F = self.n_frames = len(frames)
         if F == 0:
@@ -1474,35 +1476,20 @@ class GraphedEwaldBatch:
             raise ValueError(f"{who} handles at most 2^20 frames, got {F}")
         self.lr_wavelength = float(calculator.lr_wavelength)
         first = frames[0][2] if len(frames[0]) == 5 else None
-        freqs = []
+        grids = []
         for f, fr in enumerate(frames):
             if len(fr) != 5:
                 raise ValueError(f"{who}: frame {f} must be (charges, cell, positions, neighbor_indices, neighbor_shifts), got "
                                  f"{len(fr)} items")
             charges, cell, positions, idx, shifts = fr
-            if charges.dim() != 2 or charges.shape[1] != 1:
-                raise ValueError(f"{who}: frame {f}: a single charge channel, `charges` of shape [n_atoms, 1], got tensor with shape "
-                                 f"{list(charges.shape)}")
-            if positions.dim() != 2 or positions.shape[1] != 3 or positions.shape[0] != charges.shape[0]:
-                raise ValueError(f"{who}: frame {f}: `positions` must be a tensor with shape [n_atoms, 3] with n_atoms = "
-                                 f"{charges.shape[0]} (the charges), got tensor with shape {list(positions.shape)}")
-            if tuple(cell.shape) != (3, 3):
-                raise ValueError(f"{who}: frame {f}: `cell` must be a tensor with shape [3, 3], got tensor with shape "
-                                 f"{list(cell.shape)}")
-            if not (positions.dtype == charges.dtype == cell.dtype == first.dtype) or positions.dtype not in (torch.float32,
-                                                                                                              torch.float64):
-                raise ValueError(f"{who}: frame {f}: `positions`, `charges` and `cell` of all frames must share one dtype, float32 or "
-                                 f"float64, got {positions.dtype}, {charges.dtype} and {cell.dtype} (frame 0: {first.dtype})")
-            if positions.shape[0] < 1 or positions.shape[0] > (1 << 22):
-                raise ValueError(f"{who}: frame {f}: a frame holds 1 to 2^22 atoms (the 4-byte pair entries of the row kernel), got "
-                                 f"{positions.shape[0]}")
-            self._check_list(f, idx, shifts)
+            _check_ewald_system(who, charges, cell, positions, frame=f, first=first)
+            _check_explicit_list(who, idx, shifts, frame=f)
             for t in (charges, cell, idx, shifts, positions):
                 if t.device != first.device:
                     raise ValueError(f"{who}: frame {f}: all tensors of all frames must be on one device, got {t.device} and "
                                      f"{first.device}")
-            try:  # (raises ValueError for a singular cell; the frequencies as the eager call forms them)
-                freqs.append(_integer_frequencies(cell.detach(), self.lr_wavelength, None)[0])
+            try:  # (raises ValueError for a singular cell)
+                grids.append(_ewald_kgrid(cell, self.lr_wavelength))
             except ValueError as e:
                 raise ValueError(f"{who}: frame {f}: {e}") from None
         for f, fr in enumerate(frames):
@@ -1514,19 +1501,12 @@ class GraphedEwaldBatch:
         lib = self._lib = _lib.load()
         device, dtype = first.device, first.dtype
         self.device, self.dtype, self._dt = device, dtype, _lib.dtype_code(dtype)
-        self._desc = pot._descriptor()
+        self._desc = calculator.potential._descriptor()
         counts = [fr[2].shape[0] for fr in frames]
         self._atom_ptr = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
         self.atom_ptr = [int(v) for v in self._atom_ptr]
-        self.ns, self.n_k, f_all, m_all = [], [], [], []
-        for fr, freq in zip(frames, freqs):
-            ns = GraphedEwaldStep._ns_of(fr[1], self.lr_wavelength)
-            fq = freq.cpu().numpy()
-            rows, weight = _compact_kvectors(fq, ns)
-            self.ns.append(ns)
-            self.n_k.append(int(len(rows)))
-            f_all.append(np.rint(fq[rows]).astype(np.int32).reshape(-1, 3))
-            m_all.append(weight.astype(np.int32))
+        self.ns, f_all, m_all = (list(x) for x in zip(*grids))
+        self.n_k = [int(len(m)) for m in m_all]
         self._k_ptr = np.concatenate([[0], np.cumsum(self.n_k)]).astype(np.int64)
         self._ns = np.ascontiguousarray(np.asarray(self.ns, dtype=np.int32).reshape(F, 3))
         n_work = int(lib.mipme_ewald_batch_work(F, self._atom_ptr.ctypes.data, self._k_ptr.ctypes.data, int(self.cell_gradient)))
@@ -1556,21 +1536,6 @@ class GraphedEwaldBatch:
         self._warmup = max(1, int(warmup))
         self._install(self._pack([(fr[3], fr[4]) for fr in frames]))
 
-    @staticmethod
-    def _check_list(f, neighbor_indices, neighbor_shifts):
-        who = f"GraphedEwaldBatch: frame {f}"
-        if neighbor_indices.dim() != 2 or neighbor_indices.shape[1] != 2:
-            raise ValueError(f"{who}: `neighbor_indices` must be a tensor with shape [n_pairs, 2], got tensor with shape "
-                             f"{list(neighbor_indices.shape)}")
-        if neighbor_shifts.dim() != 2 or tuple(neighbor_shifts.shape) != (neighbor_indices.shape[0], 3):
-            raise ValueError(f"{who}: `neighbor_shifts` must be a tensor with shape [n_pairs, 3] with n_pairs = "
-                             f"{neighbor_indices.shape[0]}, got tensor with shape {list(neighbor_shifts.shape)}")
-        if neighbor_shifts.numel() > 0:
-            s = neighbor_shifts.detach()
-            if bool((s != s.round()).any()) or float(s.abs().max()) > 3:
-                raise ValueError(f"{who}: the cell shifts must be integers in [-3, 3] (the 4-byte pair entries of the row kernel); "
-                                 "wrap the positions into the cell or use a shorter cutoff")
-
     def _pack(self, lists):
         """Validate and pack F ``(neighbor_indices, neighbor_shifts)`` into the concatenated row pointers and 4-byte entries and
         build the frame table for them.  Nothing of the object changes: what is returned goes to :meth:`_install`."""
@@ -1581,7 +1546,7 @@ class GraphedEwaldBatch:
         for f, ls in enumerate(lists):
             if len(ls) != 2:
                 raise ValueError(f"{who}: frame {f}: a list is (neighbor_indices, neighbor_shifts), got {len(ls)} items")
-            self._check_list(f, *ls)
+            _check_explicit_list(who, *ls, frame=f)
             for t, name in zip(ls, ("neighbor_indices", "neighbor_shifts")):
                 _lib.require_device(t, f"{name} of frame {f}")
         rows, ents, keep = [], [], []
