@@ -20,14 +20,12 @@
 #include "host.h"
 #include "rows_body.h"
 #include "srpot.h"
+#include "step_device.h"
 
 namespace mipme {
 
-constexpr int kCsBlock = 256;
+constexpr int kCsBlock = kStepBlock, kCsRowsPerBlock = kStepRowsPerBlock;  // (the block shapes of step_device.h)
 constexpr int kCsMaxTerms = MIPME_COMBINED_MAX_TERMS;
-constexpr int kCsRowsPerBlock = kCsBlock / 16;  // 16 lanes per atom row
-static_assert(kRowLanes == 16, "row_sum of rows_body.h adds up the 16 lanes of a row");
-static_assert(kCompactAtomBits == kStepRowsAtomBits, "check_step_rows of host.h admits what the 4-byte entries hold");
 constexpr int kCsRowPart = 4 + kCsMaxTerms;     // per row block: sum q V_sr, sum q^2, sum q phi, -, sum q u_t
 constexpr int kCsKBlocksMax = 256;              // blocks of the per-term mesh energies
 
@@ -155,12 +153,7 @@ __global__ __launch_bounds__(kCsBlock) void combined_rows_kernel(CsTerms ct, int
     term_s[tid] = CsRowTerm<T>{T(ct.inv_2s2[tid]), T(ct.c1[tid]), T(ct.pref[tid]), live ? weights[tid] : T(0)};
     p_s[tid] = live ? ct.p[tid] : 1;
   }
-  {
-    T A[9];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) A[k] = cell[k];
-    fill_shift_table<T, kCsBlock>(shift_tab, A);
-  }
+  step_fill_shift_table(shift_tab, cell);
   if constexpr (WGRAD) {
     for (int t = 0; t < kCsMaxTerms; ++t) acc_s[t][tid] = T(0);
   }

@@ -24,61 +24,16 @@
 #include "dipole_device.h"
 #include "host.h"
 #include "rows_body.h"
+#include "step_device.h"
 
 namespace mipme {
 
-constexpr int kDsBlock = 256;
-constexpr int kDsWaves = kDsBlock / 64;
-constexpr int kDsRowsPerBlock = kDsBlock / 16;  // 16 lanes per atom row
-static_assert(kRowLanes == 16, "row_sum of rows_body.h adds up the 16 lanes of a row");
-static_assert(kCompactAtomBits == kStepRowsAtomBits, "check_step_rows of host.h admits what the 4-byte entries hold");
-constexpr int kDsKPerBlock = 8;                 // k-vectors per block of the cell kernel, 32 lanes each
-constexpr int kDsKLanes = kDsBlock / kDsKPerBlock;
-constexpr int kDsTile = 256;                    // atoms staged per LDS tile of the cell kernel
-constexpr int kDsCellK = 10;                    // per k block: W (9), 1/2 sum G |S|^2
-constexpr int64_t kDsTargetBlocks = 2048;       // 256 CUs x 8 workgroups
-constexpr int64_t kDsMinSlice = 1024;           // k-vectors per slice at least (4 per thread)
+constexpr int kDsBlock = kStepBlock;   // (the name the kernels and launches of this file use)
+constexpr int64_t kDsMinSlice = 1024;  // k-vectors per slice at least (4 per thread)
 
-static int64_t ds_slices(int64_t N, int64_t K) {
-  if (N <= 0 || K <= 0) return 0;
-  int64_t s = (kDsTargetBlocks + N - 1) / N;
-  s = std::min<int64_t>(s, std::max<int64_t>(1, K / kDsMinSlice));
-  return std::max<int64_t>(1, std::min<int64_t>(s, 65535));
-}
-
-// work (float64 slots): [mu partials 3 per atom block][energy partials 1 per finish block][row cell partials 9 per row block]
-//                       [k cell partials 10 per k block][row results 6 N (values of T)][slice partials 6 N S (values of T)]
-struct DsWork {
-  int64_t n_atom_blocks, n_fin_blocks, n_row_blocks, n_k_blocks, n_slices;
-  double *mu_part, *e_part, *row_cell, *k_cell;
-  void *row_out, *slice_part;
-  int64_t total;
-};
-static DsWork ds_work_layout(int64_t N, int64_t K, bool cell, void* base) {
-  DsWork w;
-  w.n_atom_blocks = (N + kDsBlock - 1) / kDsBlock;
-  w.n_fin_blocks = (N + kDsRowsPerBlock - 1) / kDsRowsPerBlock;
-  w.n_row_blocks = cell ? w.n_fin_blocks : 0;
-  w.n_k_blocks = cell ? (K + kDsKPerBlock - 1) / kDsKPerBlock : 0;
-  w.n_slices = ds_slices(N, K);
-  double* b = (double*)base;
-  w.mu_part = b;
-  w.e_part = w.mu_part + 3 * w.n_atom_blocks;
-  w.row_cell = w.e_part + w.n_fin_blocks;
-  w.k_cell = w.row_cell + 9 * w.n_row_blocks;
-  double* row_out = w.k_cell + kDsCellK * w.n_k_blocks;
-  double* slice_part = row_out + 6 * N;
-  w.row_out = row_out;
-  w.slice_part = slice_part;
-  w.total = 3 * w.n_atom_blocks + w.n_fin_blocks + 9 * w.n_row_blocks + kDsCellK * w.n_k_blocks + 6 * N + 6 * N * w.n_slices;
-  return w;
-}
-
-// sum_b p[b * stride + off], b < n: thread t adds b = t, t + 256, ... in that order, then the threads in a fixed order
-__device__ __forceinline__ double ds_strided_sum(const double* __restrict__ p, int64_t n, int stride, int off, double* red) {
-  double s = 0.0;
-  for (int64_t b = threadIdx.x; b < n; b += kDsBlock) s += p[b * stride + off];
-  return block_sum<kDsWaves>(s, red);
+// work: the layout of step_device.h without a head: [mu partials 3 per atom block] ... [row results 6 N][slice partials 6 N S]
+static StepWork ds_work_layout(int64_t N, int64_t K, bool cell, void* base) {
+  return step_work_layout(N, K, cell, base, 0, 3, 6, kDsMinSlice);
 }
 
 // ---- 1. records ------------------------------------------------------------------------------------------------------------
@@ -86,7 +41,7 @@ template <typename T>
 __global__ __launch_bounds__(kDsBlock) void dipole_step_records_kernel(int64_t N, const T* __restrict__ pos, const T* __restrict__ mu,
                                                                       AtomRecord<T>* __restrict__ recp,
                                                                       AtomRecord<T>* __restrict__ recm, double* __restrict__ mu_part) {
-  __shared__ double red[kDsWaves];
+  __shared__ double red[kStepWaves];
   const int64_t a = int64_t(blockIdx.x) * kDsBlock + threadIdx.x;
   double m[3] = {0.0, 0.0, 0.0};
   if (a < N) {
@@ -97,7 +52,7 @@ __global__ __launch_bounds__(kDsBlock) void dipole_step_records_kernel(int64_t N
   }
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
-    const double s = block_sum<kDsWaves>(m[c], red);
+    const double s = block_sum<kStepWaves>(m[c], red);
     if (threadIdx.x == 0) mu_part[3 * int64_t(blockIdx.x) + c] = s;
   }
 }
@@ -110,7 +65,7 @@ __global__ __launch_bounds__(kDsBlock) void dipole_step_atom_kernel(int64_t K, i
                                                                    const T* __restrict__ kvec, const T* __restrict__ G,
                                                                    const T* __restrict__ Sc, const T* __restrict__ Ss,
                                                                    T* __restrict__ part) {
-  __shared__ T red[kDsWaves][6];
+  __shared__ T red[kStepWaves][6];
   const int64_t i = blockIdx.x, N = gridDim.x;
   const int64_t k0 = int64_t(blockIdx.y) * chunk, k1 = min<int64_t>(K, k0 + chunk);
   const AtomRecord<T> p = recp[i], m = recm[i];
@@ -142,7 +97,7 @@ __global__ __launch_bounds__(kDsBlock) void dipole_step_atom_kernel(int64_t K, i
   if (threadIdx.x < 6) {
     T s = T(0);
 #pragma unroll
-    for (int w = 0; w < kDsWaves; ++w) s += red[w][threadIdx.x];
+    for (int w = 0; w < kStepWaves; ++w) s += red[w][threadIdx.x];
     part[(int64_t(blockIdx.y) * N + i) * 6 + threadIdx.x] = s;
   }
 }
@@ -160,34 +115,18 @@ __global__ __launch_bounds__(kDsBlock) void dipole_step_rows_kernel(DipPot<T> P,
                                                                    const AtomRecord<T>* __restrict__ recm, const T* __restrict__ cell,
                                                                    T scale, T* __restrict__ row_out, double* __restrict__ cell_part) {
   __shared__ AtomRecord<T> shift_tab[kShiftTableSize];
-  __shared__ double red[kDsWaves][9];
-  const int tid = threadIdx.x;
-  {
-    T A[9];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) A[k] = cell[k];
-    fill_shift_table<T, kDsBlock>(shift_tab, A);
-  }
+  __shared__ double red[kStepWaves][9];
+  step_fill_shift_table(shift_tab, cell);
   __syncthreads();
-  const int sub = tid % 16;
-  int64_t a = int64_t(blockIdx.x) * kDsRowsPerBlock + tid / 16;
-  const bool valid = a < N;
-  if (!valid) a = N - 1;
-  const int* __restrict__ rp = row_ptr + 2 * a;
-  const int beg = rp[0], mid = rp[1], end = valid ? rp[2] : beg;
-  const AtomRecord<T> pa = recp[a], ma = recm[a];
-  const unsigned last_atom = unsigned(N - 1);
+  const StepRow row = step_row(N, blockIdx.x, row_ptr);
+  const AtomRecord<T> pa = recp[row.a], ma = recm[row.a];
   T fx = T(0), fy = T(0), fz = T(0), gx = T(0), gy = T(0), gz = T(0);
   T w00 = T(0), w01 = T(0), w02 = T(0), w10 = T(0), w11 = T(0), w12 = T(0), w20 = T(0), w21 = T(0), w22 = T(0);
-  for (int base = beg; base < end; base += 16) {
-    const int e = base + sub;
-    const bool ok = e < end;
-    const unsigned word = unsigned(ent32[ok ? e : beg]);  // (beg < end here: a real entry, left out of the sums)
-    // (a valid stream never needs the two clamps; they keep a damaged one inside the buffers)
-    const unsigned o = min(word & unsigned(kCompactMaxAtoms - 1), last_atom);
-    const unsigned code = min(word >> kCompactAtomBits, unsigned(kShiftTableSize - 1));
-    const AtomRecord<T> po = recp[o], mo = recm[o];
-    const AtomRecord<T> sh = shift_tab[code];
+  for (int base = row.beg; base < row.end; base += 16) {
+    const int e = base + row.sub;
+    const StepEntry en = step_entry(ent32, e, row);
+    const AtomRecord<T> po = recp[en.o], mo = recm[en.o];
+    const AtomRecord<T> sh = shift_tab[en.code];
     const T vx = (po.x - pa.x) + sh.x, vy = (po.y - pa.y) + sh.y, vz = (po.z - pa.z) + sh.z;
     const T r2 = vx * vx + vy * vy + vz * vz;
     const T ri = T(1) / fsqrt(r2);
@@ -196,17 +135,16 @@ __global__ __launch_bounds__(kDsBlock) void dipole_step_rows_kernel(DipPot<T> P,
     const T cr = C * (mo.x * vx + mo.y * vy + mo.z * vz);
     T ex = T(0), ey = T(0), ez = T(0);
     dipole_pair_grad<T>(vx, vy, vz, C, dB, dC, ma.x, ma.y, ma.z, mo.x, mo.y, mo.z, ex, ey, ez);
-    if (ok) {
+    if (en.ok) {
       fx += B * mo.x - cr * vx;
       fy += B * mo.y - cr * vy;
       fz += B * mo.z - cr * vz;
       gx += ex;
       gy += ey;
       gz += ez;
-      if (CELL && e < mid) {  // role i: the listed pair, its own shift
-        const int ic = int(code);
-        const T sx = T(ic % kShiftTableBase - kShiftTableRange), sy = T((ic / kShiftTableBase) % kShiftTableBase - kShiftTableRange),
-                sz = T(ic / (kShiftTableBase * kShiftTableBase) - kShiftTableRange);
+      if (CELL && e < row.mid) {  // role i: the listed pair, its own shift
+        T sx, sy, sz;
+        step_shift_of_code(en.code, sx, sy, sz);
         w00 += sx * ex, w01 += sx * ey, w02 += sx * ez;
         w10 += sy * ex, w11 += sy * ey, w12 += sy * ez;
         w20 += sz * ex, w21 += sz * ey, w22 += sz * ez;
@@ -215,13 +153,13 @@ __global__ __launch_bounds__(kDsBlock) void dipole_step_rows_kernel(DipPot<T> P,
   }
   fx = row_sum(fx), fy = row_sum(fy), fz = row_sum(fz);
   gx = row_sum(gx), gy = row_sum(gy), gz = row_sum(gz);
-  if (sub == 0 && valid) {
-    T* o = row_out + 6 * a;
+  if (row.sub == 0 && row.valid) {
+    T* o = row_out + 6 * row.a;
     o[0] = scale * fx, o[1] = scale * fy, o[2] = scale * fz;
     o[3] = scale * gx, o[4] = scale * gy, o[5] = scale * gz;
   }
   if (CELL) {
-    const int lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const double s0 = wave_sum(double(w00)), s1 = wave_sum(double(w01)), s2 = wave_sum(double(w02));
     const double s3 = wave_sum(double(w10)), s4 = wave_sum(double(w11)), s5 = wave_sum(double(w12));
     const double s6 = wave_sum(double(w20)), s7 = wave_sum(double(w21)), s8 = wave_sum(double(w22));
@@ -234,7 +172,7 @@ __global__ __launch_bounds__(kDsBlock) void dipole_step_rows_kernel(DipPot<T> P,
     if (tid < 9) {
       double s = 0.0;
 #pragma unroll
-      for (int w = 0; w < kDsWaves; ++w) s += red[w][tid];
+      for (int w = 0; w < kStepWaves; ++w) s += red[w][tid];
       cell_part[9 * int64_t(blockIdx.x) + tid] = double(scale) * s;
     }
   }
@@ -249,18 +187,18 @@ __global__ __launch_bounds__(kDsBlock) void dipole_step_cellk_kernel(int64_t N, 
                                                                     const T* __restrict__ G, const T* __restrict__ dG,
                                                                     const T* __restrict__ Sc, const T* __restrict__ Ss,
                                                                     double* __restrict__ k_part) {
-  __shared__ T sp[kDsTile * 3];
-  __shared__ T sm[kDsTile * 3];
-  __shared__ double red[kDsKPerBlock][kDsCellK];
-  const int al = threadIdx.x % kDsKLanes, kl = threadIdx.x / kDsKLanes;
-  const int64_t k = int64_t(blockIdx.x) * kDsKPerBlock + kl;
+  __shared__ T sp[kStepTile * 3];
+  __shared__ T sm[kStepTile * 3];
+  __shared__ double red[kStepKPerBlock][kStepCellK];
+  const int al = threadIdx.x % kStepKLanes, kl = threadIdx.x / kStepKLanes;
+  const int64_t k = int64_t(blockIdx.x) * kStepKPerBlock + kl;
   const bool live = k < K && (G[k] != T(0) || dG[k] != T(0));
   const int64_t kc = k < K ? k : 0;
   const T kx = kvec[3 * kc], ky = kvec[3 * kc + 1], kz = kvec[3 * kc + 2];
   const T lSc = Sc[kc], lSs = Ss[kc];
   T ax = T(0), ay = T(0), az = T(0);
-  for (int64_t base = 0; base < N; base += kDsTile) {
-    const int n = int(min<int64_t>(kDsTile, N - base));
+  for (int64_t base = 0; base < N; base += kStepTile) {
+    const int n = int(min<int64_t>(kStepTile, N - base));
     __syncthreads();
     for (int t = threadIdx.x; t < 3 * n; t += kDsBlock) {
       sp[t] = pos[3 * base + t];
@@ -268,7 +206,7 @@ __global__ __launch_bounds__(kDsBlock) void dipole_step_cellk_kernel(int64_t N, 
     }
     __syncthreads();
     if (live)
-      for (int i = al; i < n; i += kDsKLanes) {
+      for (int i = al; i < n; i += kStepKLanes) {
         const T x = sp[3 * i], y = sp[3 * i + 1], z = sp[3 * i + 2];
         const T mx = sm[3 * i], my = sm[3 * i + 1], mz = sm[3 * i + 2];
         T s, c;
@@ -281,10 +219,10 @@ __global__ __launch_bounds__(kDsBlock) void dipole_step_cellk_kernel(int64_t N, 
       }
   }
 #pragma unroll
-  for (int off = kDsKLanes / 2; off > 0; off >>= 1) {
-    ax += __shfl_xor(ax, off, kDsKLanes);
-    ay += __shfl_xor(ay, off, kDsKLanes);
-    az += __shfl_xor(az, off, kDsKLanes);
+  for (int off = kStepKLanes / 2; off > 0; off >>= 1) {
+    ax += __shfl_xor(ax, off, kStepKLanes);
+    ay += __shfl_xor(ay, off, kStepKLanes);
+    az += __shfl_xor(az, off, kStepKLanes);
   }
   if (al == 0) {
     double g[3] = {0.0, 0.0, 0.0}, e = 0.0;
@@ -303,11 +241,11 @@ __global__ __launch_bounds__(kDsBlock) void dipole_step_cellk_kernel(int64_t N, 
     red[kl][9] = e;
   }
   __syncthreads();
-  if (threadIdx.x < kDsCellK) {
+  if (threadIdx.x < kStepCellK) {
     double s = 0.0;
 #pragma unroll
-    for (int q = 0; q < kDsKPerBlock; ++q) s += red[q][threadIdx.x];
-    k_part[kDsCellK * int64_t(blockIdx.x) + threadIdx.x] = s;
+    for (int q = 0; q < kStepKPerBlock; ++q) s += red[q][threadIdx.x];
+    k_part[kStepCellK * int64_t(blockIdx.x) + threadIdx.x] = s;
   }
 }
 
@@ -321,14 +259,14 @@ __global__ __launch_bounds__(kDsBlock) void dipole_step_finish_kernel(int64_t N,
                                                                      const double* __restrict__ mu_part, int64_t n_mu_blocks,
                                                                      T* __restrict__ forces, T* __restrict__ grad_mu,
                                                                      double* __restrict__ e_part) {
-  __shared__ double red[kDsWaves];
+  __shared__ double red[kStepWaves];
   double M[3] = {0.0, 0.0, 0.0};
   if (bg_over_v != T(0)) {  // (uniform) sum_j mu_j, the same fixed order in every block
 #pragma unroll
-    for (int c = 0; c < 3; ++c) M[c] = ds_strided_sum(mu_part, n_mu_blocks, 3, c, red);
+    for (int c = 0; c < 3; ++c) M[c] = step_strided_sum(mu_part, n_mu_blocks, 3, c, red);
   }
   const int sub = threadIdx.x % 16;
-  const int64_t a = int64_t(blockIdx.x) * kDsRowsPerBlock + threadIdx.x / 16;
+  const int64_t a = int64_t(blockIdx.x) * kStepRowsPerBlock + threadIdx.x / 16;
   const bool valid = a < N;
   T f0 = T(0), f1 = T(0), f2 = T(0), b0 = T(0), b1 = T(0), b2 = T(0);
   if (valid)
@@ -353,7 +291,7 @@ __global__ __launch_bounds__(kDsBlock) void dipole_step_finish_kernel(int64_t N,
       e += 0.5 * double(mv[c]) * double(d);
     }
   }
-  e = block_sum<kDsWaves>(e, red);
+  e = block_sum<kStepWaves>(e, red);
   if (threadIdx.x == 0) e_part[blockIdx.x] = e;
 }
 
@@ -365,22 +303,15 @@ __global__ __launch_bounds__(kDsBlock) void dipole_step_final_kernel(int64_t n_e
                                                                     const double* __restrict__ k_cell, int64_t n_mu_blocks,
                                                                     const double* __restrict__ mu_part, double inv_vol, double bg,
                                                                     const T* __restrict__ inv_cell, T* __restrict__ grad_cell) {
-  __shared__ double red[kDsWaves];
-  __shared__ double tot[9 + kDsCellK + 3];
-  const double E = ds_strided_sum(e_part, n_e_blocks, 1, 0, red);
+  __shared__ double red[kStepWaves];
+  __shared__ double tot[9 + kStepCellK + 3];
+  const double E = step_strided_sum(e_part, n_e_blocks, 1, 0, red);
   if (threadIdx.x == 0) energy[0] = T(E);
   if (CELL) {
-    for (int j = 0; j < 9; ++j) {
-      const double s = ds_strided_sum(row_cell, n_row_blocks, 9, j, red);
-      if (threadIdx.x == 0) tot[j] = s;
-    }
-    for (int j = 0; j < kDsCellK; ++j) {
-      const double s = ds_strided_sum(k_cell, n_k_blocks, kDsCellK, j, red);
-      if (threadIdx.x == 0) tot[9 + j] = s;
-    }
+    step_cell_totals(row_cell, n_row_blocks, k_cell, n_k_blocks, tot, red);
     for (int j = 0; j < 3; ++j) {
-      const double s = ds_strided_sum(mu_part, n_mu_blocks, 3, j, red);
-      if (threadIdx.x == 0) tot[9 + kDsCellK + j] = s;
+      const double s = step_strided_sum(mu_part, n_mu_blocks, 3, j, red);
+      if (threadIdx.x == 0) tot[9 + kStepCellK + j] = s;
     }
     __syncthreads();
     if (threadIdx.x < 9) {
@@ -388,7 +319,7 @@ __global__ __launch_bounds__(kDsBlock) void dipole_step_final_kernel(int64_t n_e
       const double* Wr = tot;
       const double* Wk = tot + 9;
       const double Ek = tot[9 + 9];
-      const double* M = tot + 9 + kDsCellK;
+      const double* M = tot + 9 + kStepCellK;
       const double e_v = inv_vol * (Ek + 0.5 * bg * (M[0] * M[0] + M[1] * M[1] + M[2] * M[2]));  // what scales with 1/V
       double chain = 0.0;
       for (int a = 0; a < 3; ++a) chain += double(inv_cell[3 * a + m]) * Wk[3 * a + n];
@@ -399,9 +330,9 @@ __global__ __launch_bounds__(kDsBlock) void dipole_step_final_kernel(int64_t n_e
 
 // ---- host --------------------------------------------------------------------------------------------------------------------
 template <typename T, bool EXCL>
-static void dipole_step_rows_launch(hipStream_t st, const mipme_dipole_step_args_t& a, const DipPot<T>& dp, const DsWork& w,
+static void dipole_step_rows_launch(hipStream_t st, const mipme_dipole_step_args_t& a, const DipPot<T>& dp, const StepWork& w,
                                     const AtomRecord<T>* recp, const AtomRecord<T>* recm) {
-  const unsigned blocks = unsigned((a.n_atoms + kDsRowsPerBlock - 1) / kDsRowsPerBlock);
+  const unsigned blocks = unsigned((a.n_atoms + kStepRowsPerBlock - 1) / kStepRowsPerBlock);
   const T scale = T(a.full_list ? 0.5 : 1.0) * dp.pref;
   if (a.cell_gradient)
     dipole_step_rows_kernel<T, EXCL, true><<<blocks, kDsBlock, 0, st>>>(dp, a.n_atoms, (const int*)a.row_ptr, (const int*)a.entries,
@@ -416,12 +347,12 @@ static int dipole_step_t(const mipme_dipole_step_args_t& a, const DipPot<T>& dp)
   hipStream_t st = (hipStream_t)a.stream;
   const int64_t N = a.n_atoms, K = a.n_k;
   const bool cell = a.cell_gradient != 0;
-  const DsWork w = ds_work_layout(N, K, cell, a.work);
+  const StepWork w = ds_work_layout(N, K, cell, a.work);
   AtomRecord<T>* recp = (AtomRecord<T>*)a.records;
   AtomRecord<T>* recm = recp + N;
   int rc;
   dipole_step_records_kernel<T><<<unsigned(w.n_atom_blocks), kDsBlock, 0, st>>>(N, (const T*)a.positions, (const T*)a.dipoles, recp,
-                                                                               recm, w.mu_part);
+                                                                               recm, w.atom_part);
   MIPME_LAUNCH_CHECK();
   if (K > 0) {
     if ((rc = mipme_dipole_structure(a.stream, a.dtype, N, K, a.positions, a.dipoles, a.kvectors, a.G, cell ? a.dG : nullptr, a.s_cos,
@@ -445,11 +376,11 @@ static int dipole_step_t(const mipme_dipole_step_args_t& a, const DipPot<T>& dp)
   }
   dipole_step_finish_kernel<T><<<unsigned(w.n_fin_blocks), kDsBlock, 0, st>>>(
       N, int(w.n_slices), T(a.inv_volume), T(a.self_term), T(a.background * a.inv_volume), recm, (const T*)w.slice_part,
-      (const T*)w.row_out, w.mu_part, w.n_atom_blocks, (T*)a.forces, (T*)a.grad_dipoles, w.e_part);
+      (const T*)w.row_out, w.atom_part, w.n_atom_blocks, (T*)a.forces, (T*)a.grad_dipoles, w.e_part);
   MIPME_LAUNCH_CHECK();
   if (cell)
     dipole_step_final_kernel<T, true><<<1, kDsBlock, 0, st>>>(w.n_fin_blocks, w.e_part, (T*)a.energy, w.n_row_blocks, w.row_cell,
-                                                             w.n_k_blocks, w.k_cell, w.n_atom_blocks, w.mu_part, a.inv_volume,
+                                                             w.n_k_blocks, w.k_cell, w.n_atom_blocks, w.atom_part, a.inv_volume,
                                                              a.background, (const T*)a.inv_cell, (T*)a.grad_cell);
   else
     dipole_step_final_kernel<T, false><<<1, kDsBlock, 0, st>>>(w.n_fin_blocks, w.e_part, (T*)a.energy, 0, nullptr, 0, nullptr, 0,
@@ -473,7 +404,7 @@ using namespace mipme;
 extern "C" {
 
 int64_t mipme_dipole_step_work(int64_t n_atoms, int64_t n_k, int cell_gradient) {
-  if (n_atoms < 1 || n_atoms > kCompactMaxAtoms || n_k < 0 || n_k > int64_t(kDsKPerBlock) * 0x7fffffff) return 0;
+  if (n_atoms < 1 || n_atoms > kCompactMaxAtoms || n_k < 0 || n_k > int64_t(kStepKPerBlock) * 0x7fffffff) return 0;
   return ds_work_layout(n_atoms, n_k, cell_gradient != 0, nullptr).total;
 }
 
@@ -487,7 +418,7 @@ int mipme_dipole_step(const mipme_dipole_step_args_t* in) {
   MIPME_REQUIRE(a.pot != nullptr, "%s: dipole descriptor is NULL", who);
   MIPME_REQUIRE(!(a.pot->exclusion_radius > 0) || a.pot->exclusion_degree >= 1, "%s: exclusion_degree must be >= 1, got %d", who,
                 int(a.pot->exclusion_degree));
-  MIPME_REQUIRE(a.n_k >= 0 && a.n_k <= int64_t(kDsKPerBlock) * 0x7fffffff, "%s: n_k must be >= 0, got %lld", who, (long long)a.n_k);
+  MIPME_REQUIRE(a.n_k >= 0 && a.n_k <= int64_t(kStepKPerBlock) * 0x7fffffff, "%s: n_k must be >= 0, got %lld", who, (long long)a.n_k);
   MIPME_REQUIRE(a.n_k == 0 || a.pot->smearing > 0,
                 "%s: n_k is %lld but the potential has no smearing (`smearing` is %g): a direct potential has no reciprocal part",
                 who, (long long)a.n_k, a.pot->smearing);

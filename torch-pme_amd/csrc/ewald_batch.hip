@@ -15,8 +15,9 @@
 //
 // Inside its blocks a frame is computed as the single step computes it -- by the same bodies (ewald_step_bodies.h), which see
 // one system and nothing of the table -- with LOCAL indices (partner atoms, row pointers and k-vectors count from the start of
-// the frame): the slice count of the atom kernel is es_slices(N_f, K_f), every cross-block sum is float64 block partials of that
-// frame added in index order by a later launch, and nothing a block reads belongs to another frame.  So the bits a frame gets depend on its own inputs alone -- not on its index, on F or on its neighbours in the batch.
+// the frame): the slice count of the atom kernel is that of the single step for (N_f, K_f), every cross-block sum is float64
+// block partials of that frame added in index order by a later launch, and nothing a block reads belongs to another frame.  So
+// the bits a frame gets depend on its own inputs alone -- not on its index, on F or on its neighbours in the batch.
 // No atomics, no workgroup waits for another.  A singular cell gives ITS frame a zero k table, E = NaN, dE/dcell = NaN and
 // status bit 1, and no other frame anything.
 #include <cmath>

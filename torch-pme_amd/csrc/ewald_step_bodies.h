@@ -24,16 +24,16 @@ __device__ __forceinline__ void es_prep_body(const KPot& kp, int64_t N, int64_t 
                                              const T* __restrict__ q, T* __restrict__ kvec, T* __restrict__ G, T* __restrict__ dG,
                                              AtomRecord<T>* __restrict__ rec, double* __restrict__ q_part, double* __restrict__ geom,
                                              int* __restrict__ status) {
-  __shared__ double red[kEsWaves];
+  __shared__ double red[kStepWaves];
   if (blk >= n_table_blocks) {  // (uniform per block)
-    const int64_t a = int64_t(blk - n_table_blocks) * kEsBlock + threadIdx.x;
+    const int64_t a = int64_t(blk - n_table_blocks) * kStepBlock + threadIdx.x;
     double qa = 0.0;
     if (a < N) {
       const T qv = q[a];
       rec[a] = AtomRecord<T>{pos[3 * a], pos[3 * a + 1], pos[3 * a + 2], qv};
       qa = double(qv);
     }
-    const double s = block_sum<kEsWaves>(qa, red);
+    const double s = block_sum<kStepWaves>(qa, red);
     if (threadIdx.x == 0) q_part[blk - n_table_blocks] = s;
     return;
   }
@@ -57,7 +57,7 @@ __device__ __forceinline__ void es_prep_body(const KPot& kp, int64_t N, int64_t 
     }
     status[0] = st;
   }
-  const int64_t k = int64_t(blk) * kEsBlock + threadIdx.x;
+  const int64_t k = int64_t(blk) * kStepBlock + threadIdx.x;
   if (k >= K) return;
   double kv[3] = {0.0, 0.0, 0.0}, v = 0.0, dv = 0.0;
   if (!g.bad) {  // (a singular cell: a table of zeros, and the final launch writes NaN as the energy)
@@ -82,19 +82,19 @@ __device__ __forceinline__ void es_prep_body(const KPot& kp, int64_t N, int64_t 
 template <typename T>
 __device__ __forceinline__ void es_structure_body(int64_t N, int64_t K, int64_t blk, const AtomRecord<T>* __restrict__ rec,
                                                   const T* __restrict__ kvec, T* __restrict__ Sc, T* __restrict__ Ss) {
-  __shared__ AtomRecord<T> sr[kEsTile];
-  const int al = threadIdx.x % kEsKLanes;
-  const int64_t k = blk * kEsKPerBlock + threadIdx.x / kEsKLanes;
+  __shared__ AtomRecord<T> sr[kStepTile];
+  const int al = threadIdx.x % kStepKLanes;
+  const int64_t k = blk * kStepKPerBlock + threadIdx.x / kStepKLanes;
   const bool valid = k < K;
   const int64_t kc = valid ? k : 0;
   const T kx = kvec[3 * kc], ky = kvec[3 * kc + 1], kz = kvec[3 * kc + 2];
   T ac = T(0), as = T(0);
-  for (int64_t base = 0; base < N; base += kEsTile) {
-    const int n = int(min<int64_t>(kEsTile, N - base));
+  for (int64_t base = 0; base < N; base += kStepTile) {
+    const int n = int(min<int64_t>(kStepTile, N - base));
     __syncthreads();
-    for (int t = threadIdx.x; t < n; t += kEsBlock) sr[t] = rec[base + t];
+    for (int t = threadIdx.x; t < n; t += kStepBlock) sr[t] = rec[base + t];
     __syncthreads();
-    for (int i = al; i < n; i += kEsKLanes) {
+    for (int i = al; i < n; i += kStepKLanes) {
       const AtomRecord<T> r = sr[i];
       T s, c;
       dipole_phase3(kx, ky, kz, r.x, r.y, r.z, s, c);
@@ -103,9 +103,9 @@ __device__ __forceinline__ void es_structure_body(int64_t N, int64_t K, int64_t 
     }
   }
 #pragma unroll
-  for (int off = kEsKLanes / 2; off > 0; off >>= 1) {
-    ac += __shfl_xor(ac, off, kEsKLanes);
-    as += __shfl_xor(as, off, kEsKLanes);
+  for (int off = kStepKLanes / 2; off > 0; off >>= 1) {
+    ac += __shfl_xor(ac, off, kStepKLanes);
+    as += __shfl_xor(as, off, kStepKLanes);
   }
   if (valid && al == 0) Sc[k] = ac, Ss[k] = as;
 }
@@ -117,11 +117,11 @@ __device__ __forceinline__ void es_atom_body(int64_t i, int64_t slice, int64_t N
                                              const AtomRecord<T>* __restrict__ rec, const T* __restrict__ kvec,
                                              const T* __restrict__ G, const T* __restrict__ Sc, const T* __restrict__ Ss,
                                              T* __restrict__ part) {
-  __shared__ T red[kEsWaves][4];
+  __shared__ T red[kStepWaves][4];
   const int64_t k0 = slice * chunk, k1 = min<int64_t>(K, k0 + chunk);
   const AtomRecord<T> p = rec[i];
   T phi = T(0), bx = T(0), by = T(0), bz = T(0);
-  for (int64_t k = k0 + threadIdx.x; k < k1; k += kEsBlock) {
+  for (int64_t k = k0 + threadIdx.x; k < k1; k += kStepBlock) {
     const T gk = G[k];
     if (gk == T(0)) continue;  // exact: the term is G(k) times a finite sum
     const T kx = kvec[3 * k], ky = kvec[3 * k + 1], kz = kvec[3 * k + 2];
@@ -141,7 +141,7 @@ __device__ __forceinline__ void es_atom_body(int64_t i, int64_t slice, int64_t N
   if (threadIdx.x < 4) {
     T s = T(0);
 #pragma unroll
-    for (int w = 0; w < kEsWaves; ++w) s += red[w][threadIdx.x];
+    for (int w = 0; w < kStepWaves; ++w) s += red[w][threadIdx.x];
     part[(slice * N + i) * 4 + threadIdx.x] = s;
   }
 }
@@ -159,35 +159,19 @@ __device__ __forceinline__ void es_rows_body(const SRPot& sp, const FastRS& cf, 
                                              const T* __restrict__ cell, T scale, T* __restrict__ row_out,
                                              double* __restrict__ cell_part) {
   __shared__ AtomRecord<T> shift_tab[kShiftTableSize];
-  __shared__ double red[kEsWaves][9];
-  const int tid = threadIdx.x;
-  {
-    T A[9];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) A[k] = cell[k];
-    fill_shift_table<T, kEsBlock>(shift_tab, A);
-  }
+  __shared__ double red[kStepWaves][9];
+  step_fill_shift_table(shift_tab, cell);
   __syncthreads();
   const T c_inv2s2 = T(cf.inv_2s2), c1 = T(cf.c1), cpref = T(cf.pref);
-  const int sub = tid % 16;
-  int64_t a = blk * kEsRowsPerBlock + tid / 16;
-  const bool valid = a < N;
-  if (!valid) a = N - 1;
-  const int* __restrict__ rp = row_ptr + 2 * a;
-  const int beg = rp[0], mid = rp[1], end = valid ? rp[2] : beg;
-  const AtomRecord<T> pa = rec[a];
-  const unsigned last_atom = unsigned(N - 1);
+  const StepRow row = step_row(N, blk, row_ptr);
+  const AtomRecord<T> pa = rec[row.a];
   T pot = T(0), fx = T(0), fy = T(0), fz = T(0);
   T w00 = T(0), w01 = T(0), w02 = T(0), w10 = T(0), w11 = T(0), w12 = T(0), w20 = T(0), w21 = T(0), w22 = T(0);
-  for (int base = beg; base < end; base += 16) {
-    const int e = base + sub;
-    const bool ok = e < end;
-    const unsigned word = unsigned(ent32[ok ? e : beg]);  // (beg < end here: a real entry, left out of the sums)
-    // (a valid stream never needs the two clamps; they keep a damaged one inside the system's records and the table)
-    const unsigned o = min(word & unsigned(kCompactMaxAtoms - 1), last_atom);
-    const unsigned code = min(word >> kCompactAtomBits, unsigned(kShiftTableSize - 1));
-    const AtomRecord<T> po = rec[o];
-    const AtomRecord<T> sh = shift_tab[code];
+  for (int base = row.beg; base < row.end; base += 16) {
+    const int e = base + row.sub;
+    const StepEntry en = step_entry(ent32, e, row);
+    const AtomRecord<T> po = rec[en.o];
+    const AtomRecord<T> sh = shift_tab[en.code];
     const T vx = (po.x - pa.x) + sh.x, vy = (po.y - pa.y) + sh.y, vz = (po.z - pa.z) + sh.z;
     const T d2 = vx * vx + vy * vy + vz * vz;
     T v, dvd;  // v_SR(d) and v_SR'(d) / d
@@ -199,17 +183,16 @@ __device__ __forceinline__ void es_rows_body(const SRPot& sp, const FastRS& cf, 
       sr_eval<T, true>(sp, d, v, dv);
       dvd = dv / d;
     }
-    if (ok) {
+    if (en.ok) {
       pot += po.w * v;
       const T w = po.w * dvd;
       const T ex = w * vx, ey = w * vy, ez = w * vz;
       fx += ex;
       fy += ey;
       fz += ez;
-      if (CELL && e < mid) {  // role i: the listed pair, its own shift
-        const int ic = int(code);
-        const T sx = T(ic % kShiftTableBase - kShiftTableRange), sy = T((ic / kShiftTableBase) % kShiftTableBase - kShiftTableRange),
-                sz = T(ic / (kShiftTableBase * kShiftTableBase) - kShiftTableRange);
+      if (CELL && e < row.mid) {  // role i: the listed pair, its own shift
+        T sx, sy, sz;
+        step_shift_of_code(en.code, sx, sy, sz);
         w00 += sx * ex, w01 += sx * ey, w02 += sx * ez;
         w10 += sy * ex, w11 += sy * ey, w12 += sy * ez;
         w20 += sz * ex, w21 += sz * ey, w22 += sz * ez;
@@ -217,13 +200,13 @@ __device__ __forceinline__ void es_rows_body(const SRPot& sp, const FastRS& cf, 
     }
   }
   pot = row_sum(pot), fx = row_sum(fx), fy = row_sum(fy), fz = row_sum(fz);
-  if (sub == 0 && valid) {
-    T* o = row_out + 4 * a;
+  if (row.sub == 0 && row.valid) {
+    T* o = row_out + 4 * row.a;
     const T sq = scale * pa.w;
     o[0] = scale * pot, o[1] = sq * fx, o[2] = sq * fy, o[3] = sq * fz;
   }
   if (CELL) {
-    const int lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const double qa = double(pa.w);  // (the rows of a wavefront belong to different atoms: q_a goes in before the wave sum)
     const double s0 = wave_sum(qa * double(w00)), s1 = wave_sum(qa * double(w01)), s2 = wave_sum(qa * double(w02));
     const double s3 = wave_sum(qa * double(w10)), s4 = wave_sum(qa * double(w11)), s5 = wave_sum(qa * double(w12));
@@ -237,7 +220,7 @@ __device__ __forceinline__ void es_rows_body(const SRPot& sp, const FastRS& cf, 
     if (tid < 9) {
       double s = 0.0;
 #pragma unroll
-      for (int w = 0; w < kEsWaves; ++w) s += red[w][tid];
+      for (int w = 0; w < kStepWaves; ++w) s += red[w][tid];
       cell_part[9 * blk + tid] = double(scale) * s;
     }
   }
@@ -250,22 +233,22 @@ template <typename T>
 __device__ __forceinline__ void es_cellk_body(int64_t N, int64_t K, int64_t blk, const AtomRecord<T>* __restrict__ rec,
                                               const T* __restrict__ kvec, const T* __restrict__ G, const T* __restrict__ dG,
                                               const T* __restrict__ Sc, const T* __restrict__ Ss, double* __restrict__ k_part) {
-  __shared__ AtomRecord<T> sr[kEsTile];
-  __shared__ double red[kEsKPerBlock][kEsCellK];
-  const int al = threadIdx.x % kEsKLanes, kl = threadIdx.x / kEsKLanes;
-  const int64_t k = blk * kEsKPerBlock + kl;
+  __shared__ AtomRecord<T> sr[kStepTile];
+  __shared__ double red[kStepKPerBlock][kStepCellK];
+  const int al = threadIdx.x % kStepKLanes, kl = threadIdx.x / kStepKLanes;
+  const int64_t k = blk * kStepKPerBlock + kl;
   const bool live = k < K && (G[k] != T(0) || dG[k] != T(0));
   const int64_t kc = k < K ? k : 0;
   const T kx = kvec[3 * kc], ky = kvec[3 * kc + 1], kz = kvec[3 * kc + 2];
   const T lSc = Sc[kc], lSs = Ss[kc];
   T ax = T(0), ay = T(0), az = T(0);
-  for (int64_t base = 0; base < N; base += kEsTile) {
-    const int n = int(min<int64_t>(kEsTile, N - base));
+  for (int64_t base = 0; base < N; base += kStepTile) {
+    const int n = int(min<int64_t>(kStepTile, N - base));
     __syncthreads();
-    for (int t = threadIdx.x; t < n; t += kEsBlock) sr[t] = rec[base + t];
+    for (int t = threadIdx.x; t < n; t += kStepBlock) sr[t] = rec[base + t];
     __syncthreads();
     if (live)
-      for (int i = al; i < n; i += kEsKLanes) {
+      for (int i = al; i < n; i += kStepKLanes) {
         const AtomRecord<T> r = sr[i];
         T s, c;
         dipole_phase3(kx, ky, kz, r.x, r.y, r.z, s, c);
@@ -276,10 +259,10 @@ __device__ __forceinline__ void es_cellk_body(int64_t N, int64_t K, int64_t blk,
       }
   }
 #pragma unroll
-  for (int off = kEsKLanes / 2; off > 0; off >>= 1) {
-    ax += __shfl_xor(ax, off, kEsKLanes);
-    ay += __shfl_xor(ay, off, kEsKLanes);
-    az += __shfl_xor(az, off, kEsKLanes);
+  for (int off = kStepKLanes / 2; off > 0; off >>= 1) {
+    ax += __shfl_xor(ax, off, kStepKLanes);
+    ay += __shfl_xor(ay, off, kStepKLanes);
+    az += __shfl_xor(az, off, kStepKLanes);
   }
   if (al == 0) {
     double g[3] = {0.0, 0.0, 0.0}, e = 0.0;
@@ -298,11 +281,11 @@ __device__ __forceinline__ void es_cellk_body(int64_t N, int64_t K, int64_t blk,
     red[kl][9] = e;
   }
   __syncthreads();
-  if (threadIdx.x < kEsCellK) {
+  if (threadIdx.x < kStepCellK) {
     double s = 0.0;
 #pragma unroll
-    for (int q = 0; q < kEsKPerBlock; ++q) s += red[q][threadIdx.x];
-    k_part[kEsCellK * blk + threadIdx.x] = s;
+    for (int q = 0; q < kStepKPerBlock; ++q) s += red[q][threadIdx.x];
+    k_part[kStepCellK * blk + threadIdx.x] = s;
   }
 }
 
@@ -315,13 +298,13 @@ __device__ __forceinline__ void es_finish_body(int64_t N, int n_slices, int64_t 
                                                const T* __restrict__ part, const T* __restrict__ row_out,
                                                const double* __restrict__ q_part, int64_t n_q_blocks, T* __restrict__ forces,
                                                T* __restrict__ grad_q, double* __restrict__ e_part) {
-  __shared__ double red[kEsWaves];
+  __shared__ double red[kStepWaves];
   const double inv_vol_d = geom[9];
   double Q = 0.0;
-  if (two_bg != 0.0) Q = es_strided_sum(q_part, n_q_blocks, 1, 0, red);  // (uniform) the same fixed order in every block
+  if (two_bg != 0.0) Q = step_strided_sum(q_part, n_q_blocks, 1, 0, red);  // (uniform) the same fixed order in every block
   const T inv_vol = T(inv_vol_d), bg_term = T(two_bg * Q * inv_vol_d);
   const int sub = threadIdx.x % 16;
-  const int64_t a = blk * kEsRowsPerBlock + threadIdx.x / 16;
+  const int64_t a = blk * kStepRowsPerBlock + threadIdx.x / 16;
   const bool valid = a < N;
   T phi = T(0), b0 = T(0), b1 = T(0), b2 = T(0);
   if (valid)
@@ -342,7 +325,7 @@ __device__ __forceinline__ void es_finish_body(int64_t N, int n_slices, int64_t 
     forces[3 * a + 2] = r[3] - qv * b2;
     e = 0.5 * double(qa) * double(d);
   }
-  e = block_sum<kEsWaves>(e, red);
+  e = block_sum<kStepWaves>(e, red);
   if (threadIdx.x == 0) e_part[blk] = e;
 }
 
@@ -353,30 +336,23 @@ __device__ __forceinline__ void es_final_body(int64_t n_e_blocks, const double* 
                                               int64_t n_row_blocks, const double* __restrict__ row_cell, int64_t n_k_blocks,
                                               const double* __restrict__ k_cell, int64_t n_q_blocks, const double* __restrict__ q_part,
                                               double bg, const double* __restrict__ geom, T* __restrict__ grad_cell) {
-  __shared__ double red[kEsWaves];
-  __shared__ double tot[9 + kEsCellK + 1];
+  __shared__ double red[kStepWaves];
+  __shared__ double tot[9 + kStepCellK + 1];
   const bool bad = geom[10] != 0.0;
-  const double E = es_strided_sum(e_part, n_e_blocks, 1, 0, red);
+  const double E = step_strided_sum(e_part, n_e_blocks, 1, 0, red);
   if (threadIdx.x == 0) energy[0] = bad ? T(NAN) : T(E);
   if (CELL) {
-    for (int j = 0; j < 9; ++j) {
-      const double s = es_strided_sum(row_cell, n_row_blocks, 9, j, red);
-      if (threadIdx.x == 0) tot[j] = s;
-    }
-    for (int j = 0; j < kEsCellK; ++j) {
-      const double s = es_strided_sum(k_cell, n_k_blocks, kEsCellK, j, red);
-      if (threadIdx.x == 0) tot[9 + j] = s;
-    }
+    step_cell_totals(row_cell, n_row_blocks, k_cell, n_k_blocks, tot, red);
     {
-      const double s = es_strided_sum(q_part, n_q_blocks, 1, 0, red);
-      if (threadIdx.x == 0) tot[9 + kEsCellK] = s;
+      const double s = step_strided_sum(q_part, n_q_blocks, 1, 0, red);
+      if (threadIdx.x == 0) tot[9 + kStepCellK] = s;
     }
     __syncthreads();
     if (threadIdx.x < 9) {
       const int m = threadIdx.x / 3, n = threadIdx.x % 3;
       const double* Wr = tot;
       const double* Wk = tot + 9;
-      const double Ek = tot[9 + 9], Q = tot[9 + kEsCellK], inv_vol = geom[9];
+      const double Ek = tot[9 + 9], Q = tot[9 + kStepCellK], inv_vol = geom[9];
       const double e_v = inv_vol * (Ek - bg * Q * Q);  // what scales with 1/V
       double chain = 0.0;
       for (int a = 0; a < 3; ++a) chain += geom[3 * a + m] * Wk[3 * a + n];

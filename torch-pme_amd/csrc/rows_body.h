@@ -103,7 +103,7 @@ __device__ __forceinline__ double block_sum(double v, double* red) {
 }
 
 // tab[code] = the Cartesian shift vector of table code `code` in the cell A (rows), filled by the BS threads of the workgroup;
-// the caller synchronises.  For the step kernels (combined_step.hip, dipole_step.hip): the three row bodies below keep their own
+// the caller synchronises.  For the graphed steps (step_fill_shift_table of step_device.h): the three row bodies below keep their own
 // copy of this loop, since calling the helper there changes the instruction text of 48 settled kernels of topology.hip
 template <typename T, int BS>
 __device__ __forceinline__ void fill_shift_table(AtomRecord<T>* tab, const T (&A)[9]) {
