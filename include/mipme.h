@@ -557,6 +557,12 @@ int mipme_last_cell_riders(void);
  * rounds of two per lane group (1: gather + energy + forces launches of orders up to 5 on dense bricks, at most two workgroups
  * per CU in fp32; MIPME_GATHER_PAIRS, docs/SWITCHES.md) or one by one (0: every other gather).  Same numbers either way. */
 int mipme_last_gather_pairs(void);
+/* Workgroups per x plane of the inverse (y,z) transform of the last fused convolution the calling thread launched -- or captured
+ * into a graph: 2 or 4 = each plane split over that many workgroups, every one of which produces the output rows y = h (mod S)
+ * from one decimation-in-frequency stage and a transform of length ny / S (MIPME_INV_PLANE_SPLIT, docs/SWITCHES.md: the plan's own
+ * single-launch plane kernels, one mesh, ny >= 4 S); 1 = one workgroup per plane, the two-launch planes of 256-wide meshes, a
+ * frame batch, or hipFFT planes.  Same numbers up to the order of the fp32 / fp64 additions of the y transform. */
+int mipme_last_inverse_split(void);
 /* Workgroups per x plane of the PLANE SPREAD that mipme_kspace_forward uses for this mesh / system when the caller sets
  * MIPME_FWD_RHO_MESH_UNUSED and rho_hat == NULL (0: the owner-computes bricks + the forward plane launch): single channel,
  * power-of-two nx, ny, nz, planes whose accumulation tile fits a workgroup's LDS, dense bricks, not MIPME_DETERMINISTIC.  For

@@ -22,6 +22,8 @@ static thread_local int g_last_cell_riders = 0;
 void note_cell_riders(int n) { g_last_cell_riders = n; }
 static thread_local int g_last_gather_pairs = 0;
 void note_gather_pairs(int paired) { g_last_gather_pairs = paired; }
+static thread_local int g_last_inverse_split = 1;
+void note_inverse_split(int split) { g_last_inverse_split = split; }
 void set_error(const char* fmt, ...) {
   va_list ap;
   va_start(ap, fmt);
@@ -1001,6 +1003,7 @@ const char* mipme_last_cosched_kernel(void) { return g_last_cosched; }
 int mipme_last_slot_fill(void) { return g_last_slot_fill; }
 int mipme_last_gather_pairs(void) { return g_last_gather_pairs; }
 int mipme_last_cell_riders(void) { return g_last_cell_riders; }
+int mipme_last_inverse_split(void) { return g_last_inverse_split; }
 int mipme_version(void) { return MIPME_VERSION; }
 
 int mipme_fft_plan_create(int dtype, int nx, int ny, int nz, int batch, mipme_fft_plan** out) {

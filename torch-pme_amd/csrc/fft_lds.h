@@ -334,6 +334,17 @@ __device__ __forceinline__ void yz_forward_finish(const YzTile<T>& t, int ny, in
   }
 }
 
+#if defined(MIPME_WG_TIMELINE) && MIPME_WG_TIMELINE == 2  // measurement builds only (tools/inverse_planes_timeline.py)
+// clock stamps of the first 1024 inverse plane workgroups: 0 entry, 1 tile loaded, 2 y done, 3 z done, 4 stored
+static __device__ long long g_yz_phase[8 * 1024];
+#define MIPME_YZ_PHASE(wg, k)                                                                                             \
+  do {                                                                                                                    \
+    if (threadIdx.x == 0 && (wg) < 1024) g_yz_phase[(wg) * 8 + (k)] = (long long)__builtin_amdgcn_s_memrealtime();         \
+  } while (0)
+#else
+#define MIPME_YZ_PHASE(wg, k)
+#endif
+
 // YSTAGE = false: only the z rows are transformed (`ny` is then just the number of rows this workgroup takes, y stays in natural
 // order, blockIdx.x = row group): the first / last of the two launches for planes that do not fit LDS (split_yz).
 template <typename T, bool INVERSE, bool YSTAGE = true>
@@ -356,6 +367,7 @@ __device__ __forceinline__ void yz_plane_body(int ny, int nz, int logny, int log
     __syncthreads();
     yz_forward_finish<T, YSTAGE>(yt, ny, nz, logny, loglz, hat + plane * int64_t(ny) * RZ);
   } else {
+    MIPME_YZ_PHASE(plane, 0);
     const Cplx<T>* src = hat + plane * int64_t(ny) * RZ;
     for (int idx = tid; idx < ny * RZ; idx += nthr) {
       const int y = idx / RZ, k = idx - y * RZ;
@@ -363,8 +375,11 @@ __device__ __forceinline__ void yz_plane_body(int ny, int nz, int logny, int log
       tile[yr * RZ + k] = src[idx];
     }
     __syncthreads();
+    MIPME_YZ_PHASE(plane, 1);
     if constexpr (YSTAGE) lds_fft_radix2<T, true, true, MIPME_FFT_BFAST ? 2 : 0>(tile, logny, RZ, 1, RZ, tw, Ltab);
+    MIPME_YZ_PHASE(plane, 2);
     // merge step (un-normalised: twice the textbook one):  C_k = (A_k + conj A_{Lz-k}) + i e^{+2 pi i k / nz} (A_k - conj A_{Lz-k})
+    // (this step, the z rows and the store exist a second time in yz_inverse_split_body below: change both together)
     for (int idx = tid; idx < ny * (Lz / 2 + 1); idx += nthr) {
       const int y = idx / (Lz / 2 + 1), k = idx - y * (Lz / 2 + 1);
       Cplx<T>* row = tile + y * RZ;
@@ -390,13 +405,125 @@ __device__ __forceinline__ void yz_plane_body(int ny, int nz, int logny, int log
     __syncthreads();
     // rows: DIF along z (natural in, bit-reversed out), read back through the bit reversal
     lds_fft_radix2<T, false, true, MIPME_FFT_ZROWS>(tile, loglz, ny, RZ, 1, tw, Ltab);
+    MIPME_YZ_PHASE(plane, 3);
     T* dst = real_out + plane * int64_t(ny) * nz;
     for (int idx = tid; idx < ny * Lz; idx += nthr) {
       const int y = idx / Lz, j = idx - y * Lz;
       const int jr = loglz ? int(__brev(unsigned(j)) >> (32 - loglz)) : 0;
       reinterpret_cast<Cplx<T>*>(dst)[idx] = tile[y * RZ + jr];
     }
+#if defined(MIPME_WG_TIMELINE) && MIPME_WG_TIMELINE == 2
+    __syncthreads();  // (every thread's stores issued)
+    MIPME_YZ_PHASE(plane, 4);
+#endif
   }
+}
+
+// ---- the inverse plane transform split over S workgroups (S = 2 or 4), without any hand-off between them ----------------------
+// Workgroup (plane, h) produces the output rows y = S m + h, m < M = ny / S, and nothing else.  Along y the inverse transform
+//     x_y = sum_k X_k e^{+2 pi i k y / ny}
+// taken at y = S m + h, with k = k' + M j (k' < M, j < S), is a length-M inverse transform over k' of
+//     a_k' = e^{+2 pi i k' h / ny} sum_j X_{k' + M j} e^{+2 pi i j h / S}:
+// ONE radix-S decimation-in-frequency stage of which only residue h is kept.  It is formed from the registers the plane was loaded
+// into (each thread loads the S values an a_k' needs; every load of a round is issued before its first LDS store), so the tile in
+// LDS has M rows; then the length-M y transform, the merge step and the z rows of those M rows, as in yz_plane_body (same
+// conventions: un-normalised, imaginary parts of the k_z = 0 and Nyquist entries ignored).  The S workgroups of a plane read the
+// same input and write disjoint rows of the output: no flag, ticket or fence.  Needs ny >= 4 S (M >= 4) and output != input.
+// (yz_plane_body keeps its own text: MIPME_INV_PLANE_SPLIT=1 is the kernel as it was, instruction for instruction.)
+#ifndef MIPME_INV_SPLIT_NARROW
+#define MIPME_INV_SPLIT_NARROW 0  // 1: split workgroups of 1024 / S threads (A/B builds: profiles/inverse_planes_split.txt items 2, 5)
+#endif
+template <typename T, int S>
+__device__ __forceinline__ void yz_inverse_split_body(int ny, int nz, int logny, int loglz, const Cplx<T>* __restrict__ hat,
+                                                      T* __restrict__ real_out, int64_t plane, int h, unsigned wg, char* smem_yz) {
+  static_assert(S == 2 || S == 4, "radix of the split stage");
+  constexpr int LOGS = S == 2 ? 1 : 2;
+  const int M = ny >> LOGS, logM = logny - LOGS;
+  MIPME_YZ_PHASE(wg, 0);
+  const YzTile<T> yt = yz_tile_setup<T, true>(M, nz, smem_yz);
+  const int Lz = yt.Lz, RZ = yt.RZ, Ltab = yt.Ltab;
+  Cplx<T>* tile = yt.tile;
+  const Cplx<T>*tw = yt.tw, *twr = yt.twr;
+  const int tid = threadIdx.x, nthr = blockDim.x;
+  const Cplx<T>* src = hat + plane * int64_t(ny) * RZ;
+  const int items = M * RZ, jstride = M * RZ;  // element (k' + M j, kz) sits j * M * RZ behind (k', kz)
+  const T s2 = (h & 1) ? T(-1) : T(1);                                                            // e^{+2 pi i 2 h / 4}
+  const Cplx<T> ih{T(h == 0 ? 1 : (h == 2 ? -1 : 0)), T(h == 1 ? 1 : (h == 3 ? -1 : 0))};         // e^{+2 pi i h / 4}
+  // (k', kz) points per thread and round: one round at 64^3 (1056 / 528 points on 1024 threads; NARROW: on 512 / 256)
+  constexpr int U = MIPME_INV_SPLIT_NARROW ? 3 : 4 / S;
+  for (int base = tid; base < items; base += U * nthr) {
+    Cplx<T> x[U][S];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int idx = base + u * nthr;
+      const Cplx<T>* q = src + (idx < items ? idx : 0);
+#pragma unroll
+      for (int j = 0; j < S; ++j) x[u][j] = q[j * jstride];
+    }
+    // (the twiddles and LDS slots first: they wait for nothing, the sums below wait for the loads)
+    Cplx<T> w[U];
+    int slot[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int idx = base + u * nthr;
+      const int k = idx / RZ, kz = idx - k * RZ;
+      unit_root(idx < items ? k * h : 0, ny, w[u].re, w[u].im);
+      slot[u] = int(__brev(unsigned(k)) >> (32 - logM)) * RZ + kz;
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int idx = base + u * nthr;
+      if (idx < items) {
+        Cplx<T> a;
+        if constexpr (S == 2) {
+          a = Cplx<T>{x[u][0].re + s2 * x[u][1].re, x[u][0].im + s2 * x[u][1].im};
+        } else {
+          const Cplx<T> e{x[u][0].re + s2 * x[u][2].re, x[u][0].im + s2 * x[u][2].im};
+          const Cplx<T> o{x[u][1].re + s2 * x[u][3].re, x[u][1].im + s2 * x[u][3].im};
+          a = cadd(e, cmul(o, ih));
+        }
+        tile[slot[u]] = cmulc(a, w[u]);  // times e^{+2 pi i k' h / ny}
+      }
+    }
+  }
+  __syncthreads();
+  MIPME_YZ_PHASE(wg, 1);
+  lds_fft_radix2<T, true, true, MIPME_FFT_BFAST ? 2 : 0>(tile, logM, RZ, 1, RZ, tw, Ltab);
+  MIPME_YZ_PHASE(wg, 2);
+  // merge step and z rows of the M rows: yz_plane_body's, row m is output row S m + h
+  for (int idx = tid; idx < M * (Lz / 2 + 1); idx += nthr) {
+    const int y = idx / (Lz / 2 + 1), k = idx - y * (Lz / 2 + 1);
+    Cplx<T>* row = tile + y * RZ;
+    const int k2 = Lz - k;
+    Cplx<T> ak = row[k], am = row[k2];
+    if (k == 0) {
+      ak.im = T(0);
+      am.im = T(0);
+    }
+    const Cplx<T> wk = twr[k], wm = twr[k2];
+    auto merge = [](Cplx<T> a, Cplx<T> b, Cplx<T> w) {  // a = A_k, b = A_{Lz-k}, w = e^{-2 pi i k / nz}
+      const Cplx<T> e{a.re + b.re, a.im - b.im};
+      const Cplx<T> d{a.re - b.re, a.im + b.im};
+      const Cplx<T> dw = cmulc(d, w);
+      return Cplx<T>{e.re - dw.im, e.im + dw.re};
+    };
+    const Cplx<T> ck = merge(ak, am, wk), cm = merge(am, ak, wm);
+    if (k < Lz) row[k] = ck;
+    if (k2 < Lz && k2 != k) row[k2] = cm;
+  }
+  __syncthreads();
+  lds_fft_radix2<T, false, true, MIPME_FFT_ZROWS>(tile, loglz, M, RZ, 1, tw, Ltab);
+  MIPME_YZ_PHASE(wg, 3);
+  Cplx<T>* dst = reinterpret_cast<Cplx<T>*>(real_out + plane * int64_t(ny) * nz);  // the plane as ny x Lz pairs
+  for (int idx = tid; idx < M * Lz; idx += nthr) {
+    const int m = idx / Lz, j = idx - m * Lz;
+    const int jr = loglz ? int(__brev(unsigned(j)) >> (32 - loglz)) : 0;
+    dst[(S * m + h) * Lz + j] = tile[m * RZ + jr];
+  }
+#if defined(MIPME_WG_TIMELINE) && MIPME_WG_TIMELINE == 2
+  __syncthreads();  // (every thread's stores issued)
+  MIPME_YZ_PHASE(wg, 4);
+#endif
 }
 
 }  // namespace mipme

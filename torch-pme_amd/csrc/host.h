@@ -88,6 +88,25 @@ bool fft_plan_plane_forward_ok_batched(const mipme_fft_plan* p);
 void fft_plan_set_forward_done(mipme_fft_plan* p, bool done, int parts);
 void fft_plan_set_forward_ycols(mipme_fft_plan* p, bool pending);
 void* fft_plan_hat_parts(mipme_fft_plan* p, hipStream_t st, int n_more);
+// MIPME_INV_PLANE_SPLIT (docs/SWITCHES.md): workgroups per x plane of the single-launch inverse (y,z) planes -- 1, 2 or 4; unset
+// or anything else: 0 = chosen from the mesh (inverse_plane_split_auto).  Read at every launch (a captured graph keeps what it was
+// captured with).
+inline int inverse_plane_split_setting() {
+  const char* e = getenv("MIPME_INV_PLANE_SPLIT");
+  const int s = e ? atoi(e) : 0;
+  return (s == 1 || s == 2 || s == 4) ? s : 0;
+}
+// The default: the largest S of 4, 2 whose S x nx plane workgroups are at most 128, half the CUs -- 256 workgroups of 16 waves
+// take every CU and the slot riders queue behind them (64^3 fp32: the launch 7.69 us unsplit, 7.04 at S = 2, 9.15 at S = 4; 32^3
+// fp64: the step 44.68 / 44.86 / 44.00 us; profiles/inverse_planes_split.txt) -- and whose transform is long enough (ny >= 4 S).
+static constexpr int kInvPlaneSplitMaxWorkgroups = 128;
+inline int inverse_plane_split_auto(int nx, int ny) {
+  for (int s = 4; s > 1; s >>= 1)
+    if (s * nx <= kInvPlaneSplitMaxWorkgroups && ny >= 4 * s) return s;
+  return 1;
+}
+// (mipme_last_inverse_split: workgroups per plane of the last inverse (y,z) transform of a fused convolution; 1: the unsplit kernels)
+void note_inverse_split(int split);
 // *out = the plan's scratch for the energy partial sums of a gather tail (`bytes` of it, zeroed when first allocated), or
 // MIPME_EINVAL with the advice to warm up before a stream capture
 int fft_plan_tail_scratch(mipme_fft_plan* p, int64_t bytes, void** out);

@@ -522,6 +522,45 @@ __device__ __forceinline__ unsigned xcd_tile(unsigned b, unsigned n) {
   return x * per + (x < rem ? x : rem) + (b >> 3);
 }
 
+// The inverse planes with S workgroups per plane (fft_lds.h yz_inverse_split_body; MIPME_INV_PLANE_SPLIT), each as wide as the
+// unsplit launch's (every phase of the body is a chain of latencies with at most one work item per thread: workgroups of
+// 1024 / S threads do the same work per thread and end no sooner, profiles/inverse_planes_split.txt);
+// n_items = S x planes work items in front of the riders.  Work item (plane, h) = (item / S, item % S) with item taken through
+// xcd_tile: the S workgroups of a plane are neighbours in an XCD's range, so its L2 serves the plane they all read.
+template <typename T, int S>
+__global__ __launch_bounds__(1024) void yz_planes_split_kernel(int ny, int nz, int logny, int loglz, const Cplx<T>* __restrict__ hat,
+                                                                 T* __restrict__ real_out, const int* __restrict__ skip,
+                                                                 unsigned n_items, CellRider rider) {
+  MIPME_SKIP_IF_SET(skip);
+  extern __shared__ __attribute__((aligned(16))) char smem_yz[];
+  if (blockIdx.x >= n_items) {  // (uniform; rider.n_riders workgroups behind the planes)
+    cell_rider_body<T>(rider, blockIdx.x - n_items, int(blockDim.x), reinterpret_cast<double*>(smem_yz));
+    return;
+  }
+  const unsigned item = xcd_tile(blockIdx.x, n_items);
+  yz_inverse_split_body<T, S>(ny, nz, logny, loglz, hat, real_out, item / S, int(item % S), item, smem_yz);
+}
+
+// ... of a forward call with a deferred slot fill: riders as in yz_planes_slots_kernel
+template <int SCHEME, int N, typename T, int S>
+__global__ __launch_bounds__(1024) void yz_planes_slots_split_kernel(int ny, int nz, int logny, int loglz,
+                                                                       const Cplx<T>* __restrict__ hat, T* __restrict__ real_out,
+                                                                       const int* __restrict__ skip, unsigned n_items,
+                                                                       CellRider rider, SlotRider slots) {
+  MIPME_SKIP_IF_SET(skip);
+  extern __shared__ __attribute__((aligned(16))) char smem_yz[];
+  if (blockIdx.x >= n_items + unsigned(rider.n_riders)) {  // (uniform)
+    slot_rider_body<SCHEME, N, T>(slots, blockIdx.x - n_items - unsigned(rider.n_riders));
+    return;
+  }
+  if (blockIdx.x >= n_items) {  // (uniform)
+    cell_rider_body<T>(rider, blockIdx.x - n_items, int(blockDim.x), reinterpret_cast<double*>(smem_yz));
+    return;
+  }
+  const unsigned item = xcd_tile(blockIdx.x, n_items);
+  yz_inverse_split_body<T, S>(ny, nz, logny, loglz, hat, real_out, item / S, int(item % S), item, smem_yz);
+}
+
 template <typename T, bool INVERSE>
 __global__ __launch_bounds__(256) void ycols_kernel(int ny, int nzh, int logny, int kzs, int nchunk, Cplx<T>* __restrict__ hat,
                                                    const int* __restrict__ skip) {
@@ -616,6 +655,54 @@ static void yz_launch_shape(const mipme_fft_plan* p, size_t real_bytes, int& log
   threads = work >= 2048 ? 1024 : (work >= 512 ? 256 : 64);
 }
 
+// Workgroups per plane of the single-launch inverse planes: the setting where the split body can serve the plan -- one mesh (frame
+// batches keep one workgroup per plane), M = ny / S >= 4, a plane within the 64 KB of LDS a kernel has without a raised limit
+// (`lds1`: the unsplit launch's; the 128 x 128 planes that the plane spread takes in bands keep one workgroup each), and an output
+// that does not overlap the input (the S workgroups of a plane read all of it while the others store) -- 1 otherwise.
+template <typename T>
+static int inverse_split_for(const mipme_fft_plan* p, size_t lds1, const void* hat, const void* real_out) {
+  int s = inverse_plane_split_setting();
+  if (s == 0) s = inverse_plane_split_auto(p->nx, p->ny);
+  if (s == 1 || p->batch != 1 || p->ny < 4 * s || lds1 > 64 * 1024) return 1;
+  const char *h0 = static_cast<const char*>(hat), *r0 = static_cast<const char*>(real_out);
+  const size_t planes = size_t(p->nx) * p->ny;
+  const char *h1 = h0 + planes * (p->nz / 2 + 1) * 2 * sizeof(T), *r1 = r0 + planes * p->nz * sizeof(T);
+  return (h0 < r1 && r0 < h1) ? 1 : s;
+}
+
+// the split launch: S x nx plane workgroups of the unsplit launch's width, riders behind them
+template <typename T, int SPLIT>
+static int yz_planes_split(mipme_fft_plan* p, hipStream_t st, const void* hat, void* real_out, int logny, int loglz, int threads,
+                           const CellRider* rider, const SlotRider* slots) {
+#if MIPME_INV_SPLIT_NARROW  // (measurement builds: workgroups of 1024 / S threads, at least a wavefront)
+  threads = threads / SPLIT > 64 ? threads / SPLIT : 64;
+#endif
+  const int Lz = p->nz / 2, M = p->ny / SPLIT, Ltab = M > Lz ? M : Lz;
+  size_t lds = sizeof(Cplx<T>) * (size_t(M) * (Lz + 1) + size_t(Ltab) / 2 + size_t(Lz + 1));
+  const unsigned n_items = unsigned(p->nx) * unsigned(SPLIT);
+  const unsigned n_riders = rider ? unsigned(rider->n_riders) : 0u;
+  if (n_riders && lds < sizeof(double) * 16 * kCellRow) lds = sizeof(double) * 16 * kCellRow;  // the riders' reduction scratch
+  if (slots) {
+    SlotRider sr = *slots;
+    sr.per_rider = threads < kSlotRiderAtoms ? threads : kSlotRiderAtoms;
+    const unsigned n_slot_riders = unsigned((sr.n_atoms + sr.per_rider - 1) / sr.per_rider);
+    int slot_rc = MIPME_OK;
+    MIPME_DISPATCH_STENCIL_B(sr.scheme, sr.order, (slot_rc = [&]() -> int {
+      yz_planes_slots_split_kernel<S, N, T, SPLIT><<<n_items + n_riders + n_slot_riders, threads, lds, st>>>(
+          p->ny, p->nz, logny, loglz, (const Cplx<T>*)hat, (T*)real_out, skip_flag_slot(), n_items, n_riders ? *rider : CellRider{}, sr);
+      return MIPME_OK;
+    }()));
+    if (slot_rc) return slot_rc;
+    note_slot_fill(sr.per_rider);
+    note_cell_riders(int(n_riders));
+  } else {
+    yz_planes_split_kernel<T, SPLIT><<<n_items + n_riders, threads, lds, st>>>(p->ny, p->nz, logny, loglz, (const Cplx<T>*)hat, (T*)real_out,
+                                                                          skip_flag_slot(), n_items, n_riders ? *rider : CellRider{});
+  }
+  MIPME_LAUNCH_CHECK();
+  return MIPME_OK;
+}
+
 // rider (inverse only, nullable): the cell-gradient riders of an energy step, appended to the launch where there is ONE launch
 // per direction, a launch of their own otherwise
 template <typename T>
@@ -639,6 +726,12 @@ static int yz_planes(mipme_fft_plan* p, hipStream_t st, bool inverse, const void
   yz_launch_shape(p, sizeof(T), logny, loglz, lds, threads);
   const unsigned grid = unsigned(p->nx) * unsigned(p->batch);
   const unsigned n_riders = (inverse && rider) ? unsigned(rider->n_riders) : 0u;
+  if (inverse) {
+    const int split = inverse_split_for<T>(p, lds, hat, real_out);
+    note_inverse_split(split);  // (1 too: the plan's self-test comes here without a convolution)
+    if (split == 2) return yz_planes_split<T, 2>(p, st, hat, real_out, logny, loglz, threads, n_riders ? rider : nullptr, slots);
+    if (split == 4) return yz_planes_split<T, 4>(p, st, hat, real_out, logny, loglz, threads, n_riders ? rider : nullptr, slots);
+  }
   if (n_riders && lds < sizeof(double) * 16 * kCellRow) lds = sizeof(double) * 16 * kCellRow;  // the riders' reduction scratch
   if (lds > 64 * 1024) {  // once per instantiation: allow the large dynamic allocation
     static bool raised[2] = {false, false};
@@ -1088,6 +1181,7 @@ static int convolve_xfused_t(mipme_fft_plan* p, hipStream_t st, const void* mesh
   MIPME_LAUNCH_CHECK();
   const SlotRider* slots = (cc && cc->slots && cc->slots->n_atoms > 0) ? cc->slots : nullptr;
   MIPME_REQUIRE(!slots || (p->own_yz && p->batch == 1), "slot riders need the plan's own (y,z) plane kernels and a single mesh");
+  note_inverse_split(1);  // (the single-launch planes say otherwise where they split)
   if (p->own_yz) {
     int rc = yz_planes<T>(p, st, true, nullptr, hat, mesh_out, riders ? &rider : nullptr, slots);
     if (rc) return rc;
@@ -1589,3 +1683,9 @@ template int cellgrad_finalize_impl<double>(hipStream_t, const mipme_mesh_t*, do
                                             void*, int64_t, const void*, const void*);
 
 }  // namespace mipme
+
+#if defined(MIPME_WG_TIMELINE) && MIPME_WG_TIMELINE == 2  // measurement builds only (tools/inverse_planes_timeline.py)
+extern "C" int mipme_debug_yz_phase(void* out, int n_words) {
+  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(mipme::g_yz_phase), size_t(n_words) * 8);
+}
+#endif
