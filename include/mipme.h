@@ -1246,6 +1246,80 @@ int64_t mipme_ewald_batch_table_bytes(int n_frames, const int64_t* atom_ptr, con
 int mipme_ewald_batch_table_build(int n_frames, const int64_t* atom_ptr, const int64_t* k_ptr, const int64_t* entry_ptr,
                                   const int32_t* ns, int cell_gradient, void* host_table, int64_t host_table_bytes);
 
+/* mipme_dipole_step with the CELL as an input of every call, the MD form of CalculatorDipole for constant-pressure runs:
+ * GraphedDipoleStep(follow_cell=True), graphed.py; csrc/dipole_step.hip.  energy, forces, grad_dipoles and grad_cell mean word for
+ * word what they mean in mipme_dipole_step_args_t, evaluated with the CURRENT contents of `cell` and summed over the k grid given
+ * by `frequencies`; energy (and grad_cell) are NaN when status bit 1 is set.
+ *   status        = one int32: bit 0 -- some ceil(|a_d| / lr_wavelength) of the current cell differs from ns[d], i.e. the eager call
+ *                   would sum another k grid (the step keeps the grid it was given; never set by a potential without smearing);
+ *                   bit 1 -- det(cell) is zero or not finite
+ * The caller supplies what does NOT depend on the cell's values: the COMPACTED integer frequencies int32 (n_k, 3) -- k = 0 dropped,
+ * one of every +-k pair -- with their multiplicities int32 (n_k) (2, or 1 where the mirror is not in the grid), ns and
+ * lr_wavelength of the construction cell (read for `status` alone), the dipole descriptor, self_term = prefactor 4 pi/3
+ * (alpha/pi)^(3/2) and background = prefactor 4 pi / (2 epsilon + 1) (0: none).  positions (N,3), dipoles (N,3) and cell (3,3, rows =
+ * lattice vectors) are device buffers in `dtype`, read by every call.  Nothing that depends on the cell's values is a by-value
+ * argument -- there is no inv_volume and no inv_cell: the same argument struct serves every cell.  n_k = 0 with a potential
+ * without smearing: pair rows only (lr_wavelength and ns are not read).
+ * Launches, one after the other on `stream` (capturable; nothing runs beside anything else), as many as mipme_dipole_step's:
+ *   prep        k blocks: every thread inverts the 3 x 3 cell in float64 and writes k = 2 pi F cell^-T, G = mult v_LR^(k^2) and
+ *               dG = mult dv_LR^/dk^2 (Coulomb's kernel with the descriptor's smearing and prefactor) of one compacted frequency,
+ *               formed in double and rounded once; block 0 also the geometry record (cell^-1, 1/|det|, bad) at the head of `work`
+ *               and `status`.  Atom blocks: the two records of every atom and the float64 block partials of sum_j mu_j, as the
+ *               records launch of mipme_dipole_step.  For a singular cell the k table is zeros.
+ *   structure, atoms, rows, cell k      the launches of mipme_dipole_step as they are (they read device pointers only; the rows
+ *               build their shift table from the device cell)
+ *   finish      as mipme_dipole_step's, 1/V and background/V from the geometry record
+ *   final       as mipme_dipole_step's, 1/V and cell^-1 from the geometry record; E = NaN and grad_cell = NaN for a bad cell
+ * No address, loop bound or launch shape depends on the cell's values.  No atomics anywhere: every sum has a fixed order, equal
+ * inputs (cell included) give equal bits.
+ * Scratch, all written: records 8 N reals (16-byte aligned); kvectors 3 n_k, G, dG (with cell_gradient), s_cos, s_sin n_k reals
+ * each; work: float64[mipme_dipole_cell_step_work(n_atoms, n_k, cell_gradient)] (0 for invalid sizes; mipme_dipole_step_work plus
+ * the 16 doubles of the geometry record).
+ * MIPME_EINVAL before anything is launched: a NULL struct, another struct version, an implausible size, a bad dtype, a NULL
+ * descriptor, n_k > 0 with a potential without smearing or without a positive lr_wavelength and ns >= 1, an exclusion radius with
+ * exclusion_degree < 1, another shift format, n_atoms outside 1..2^22, n_k < 0, cell_gradient without grad_cell (or without dG when
+ * n_k > 0), a NULL status or required buffer.  Versioned like mipme_ewald_step_args_t: size and version first, fields only ever
+ * appended. */
+#define MIPME_DIPOLE_CELL_STEP_VERSION 1
+typedef struct mipme_dipole_cell_step_args {
+  uint32_t size;
+  uint32_t version;
+  void* stream;
+  int32_t dtype;
+  int32_t full_list;
+  const mipme_dipole_t* pot;
+  double self_term;
+  double background;
+  int64_t n_atoms;
+  int64_t n_k;
+  double lr_wavelength;
+  int32_t ns[3];
+  int32_t cell_gradient;
+  const void* positions;
+  const void* dipoles;
+  const void* cell;
+  const void* frequencies;
+  const void* multiplicities;
+  const void* row_ptr;
+  const void* entries;
+  int32_t shift_format;
+  int32_t _pad;
+  void* records;
+  void* kvectors;
+  void* G;
+  void* dG;
+  void* s_cos;
+  void* s_sin;
+  void* energy;
+  void* forces;
+  void* grad_dipoles;
+  void* grad_cell;
+  void* status;
+  void* work;
+} mipme_dipole_cell_step_args_t;
+int mipme_dipole_cell_step(const mipme_dipole_cell_step_args_t* args);
+int64_t mipme_dipole_cell_step_work(int64_t n_atoms, int64_t n_k, int cell_gradient);
+
 /* ---- device neighbour list (the reference uses third-party vesin on the host,
  * tests/helpers.py:240-275, and hands a fresh list to every call, examples/02-neighbor-lists-usage.py:97-164) -------------
  * One cell-list traversal, two products:

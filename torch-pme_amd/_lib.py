@@ -48,6 +48,7 @@ EXPORTS = (
     "mipme_dipole_step", "mipme_dipole_step_work",
     "mipme_ewald_step", "mipme_ewald_step_work",
     "mipme_ewald_batch", "mipme_ewald_batch_work", "mipme_ewald_batch_table_bytes", "mipme_ewald_batch_table_build",
+    "mipme_dipole_cell_step", "mipme_dipole_cell_step_work",
 )
 
 
@@ -375,6 +376,34 @@ class DipoleStepArgs(_VersionedArgs):
         C.Structure.__init__(self, size=C.sizeof(type(self)), version=DIPOLE_STEP_VERSION, **fields)
 
 
+DIPOLE_CELL_STEP_VERSION = 1
+
+
+class DipoleCellStepArgs(_VersionedArgs):
+    """``mipme_dipole_cell_step_args_t`` (version ``MIPME_DIPOLE_CELL_STEP_VERSION``)"""
+
+    _fields_ = [
+        ("size", C.c_uint32), ("version", C.c_uint32),
+        ("stream", C.c_void_p), ("dtype", C.c_int32), ("full_list", C.c_int32),
+        ("pot", C.POINTER(DipoleDesc)), ("self_term", C.c_double), ("background", C.c_double),
+        ("n_atoms", C.c_int64), ("n_k", C.c_int64),
+        ("lr_wavelength", C.c_double), ("ns", C.c_int32 * 3), ("cell_gradient", C.c_int32),
+        ("positions", C.c_void_p), ("dipoles", C.c_void_p), ("cell", C.c_void_p),
+        ("frequencies", C.c_void_p), ("multiplicities", C.c_void_p),
+        ("row_ptr", C.c_void_p), ("entries", C.c_void_p), ("shift_format", C.c_int32), ("_pad", C.c_int32),
+        ("records", C.c_void_p), ("kvectors", C.c_void_p), ("G", C.c_void_p), ("dG", C.c_void_p),
+        ("s_cos", C.c_void_p), ("s_sin", C.c_void_p),
+        ("energy", C.c_void_p), ("forces", C.c_void_p), ("grad_dipoles", C.c_void_p), ("grad_cell", C.c_void_p),
+        ("status", C.c_void_p), ("work", C.c_void_p),
+    ]
+
+    def __init__(self, **fields):
+        unknown = set(fields) - {name for name, _ in self._fields_}
+        if unknown:
+            raise TypeError(f"{type(self).__name__}: unknown field(s) {sorted(unknown)}")
+        C.Structure.__init__(self, size=C.sizeof(type(self)), version=DIPOLE_CELL_STEP_VERSION, **fields)
+
+
 EWALD_STEP_VERSION = 1
 EWALD_BATCH_VERSION = 1
 
@@ -503,6 +532,7 @@ def _declare(lib):
         "mipme_combined_kfilter_build": [vp, ci, MP, C.POINTER(CombinedDesc), vp],
         "mipme_combined_step": [C.POINTER(CombinedStepArgs)],
         "mipme_dipole_step": [C.POINTER(DipoleStepArgs)],
+        "mipme_dipole_cell_step": [C.POINTER(DipoleCellStepArgs)],
         "mipme_ewald_step": [C.POINTER(EwaldStepArgs)],
         "mipme_ewald_batch": [C.POINTER(EwaldBatchArgs)],
         "mipme_ewald_batch_table_build": [ci, vp, vp, vp, vp, ci, vp, i64],
@@ -589,6 +619,8 @@ def _declare(lib):
     lib.mipme_combined_step_work.argtypes = [vp, MP, i64, ci]
     lib.mipme_dipole_step_work.restype = i64
     lib.mipme_dipole_step_work.argtypes = [i64, i64, ci]
+    lib.mipme_dipole_cell_step_work.restype = i64
+    lib.mipme_dipole_cell_step_work.argtypes = [i64, i64, ci]
     lib.mipme_ewald_step_work.restype = i64
     lib.mipme_ewald_step_work.argtypes = [i64, i64, ci]
     lib.mipme_ewald_batch_work.restype = i64

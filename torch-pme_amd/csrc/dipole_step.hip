@@ -19,9 +19,14 @@
 //
 // The compacted list holds one of every +-k pair (the two terms of every sum above are equal) with the multiplicity folded into
 // G and dG by the caller.  No atomics: every sum has a fixed order, results are the same bits run after run.
+//
+// mipme_dipole_cell_step is the same step with the CELL as an input of every call: dipole_cell_step_prep_kernel in the place of
+// records (and of the caller's tables: k, G, dG, A^-1, 1/V from the nine values of the device cell), dipole_cell_step_finish_kernel
+// and dipole_cell_step_final_kernel in the place of finish and final; see the section behind the final kernel.
 #include <cmath>
 
 #include "dipole_device.h"
+#include "ewald_step_device.h"  // kEsGeom, es_invert_cell, lr_kernel_dev: what the step that follows its cell shares with the Ewald step
 #include "host.h"
 #include "rows_body.h"
 #include "step_device.h"
@@ -328,9 +333,175 @@ __global__ __launch_bounds__(kDsBlock) void dipole_step_final_kernel(int64_t n_e
   }
 }
 
+// ---- the step that follows its cell (mipme_dipole_cell_step) ------------------------------------------------------------------
+// Everything that depends on the cell's values comes from the nine values of the device cell in every call: prep takes the place
+// of the records launch and also writes the k table, the geometry record (the head of the work area: the record of the Ewald
+// step, kEsGeom doubles) and the status word; finish and final read 1/V and A^-1 from that record.  Structure, atoms, rows and
+// cell k are the kernels above.  The three kernels are written out in full: a body shared with the kernels above through a helper
+// is not compiled as the text it replaces (docs/HISTORY.md, the step_device.h entry).
+
+// work: ds_work_layout behind the geometry record
+static StepWork dcs_work_layout(int64_t N, int64_t K, bool cell, void* base) {
+  return step_work_layout(N, K, cell, base, kEsGeom, 3, 6, kDsMinSlice);
+}
+static int64_t dcs_table_blocks(int64_t K) {
+  return std::max<int64_t>(1, (K + kDsBlock - 1) / kDsBlock);  // (block 0 writes the geometry: at least one)
+}
+
+// ---- 1'. prep: k table and geometry (blocks blockIdx.x < n_table_blocks), records and dipole partials (the blocks behind them) ---
+// lr_wavelength <= 0 (a potential without smearing): bit 0 of the status word is never set
+template <typename T>
+__global__ __launch_bounds__(kDsBlock) void dipole_cell_step_prep_kernel(KPot kp, int64_t N, int64_t K, int n_table_blocks,
+                                                                        const T* __restrict__ cell, const int* __restrict__ freq,
+                                                                        const int* __restrict__ mult, int ns0, int ns1, int ns2,
+                                                                        double lr_wavelength, const T* __restrict__ pos,
+                                                                        const T* __restrict__ mu, T* __restrict__ kvec,
+                                                                        T* __restrict__ G, T* __restrict__ dG,
+                                                                        AtomRecord<T>* __restrict__ recp,
+                                                                        AtomRecord<T>* __restrict__ recm, double* __restrict__ mu_part,
+                                                                        double* __restrict__ geom, int* __restrict__ status) {
+  __shared__ double red[kStepWaves];
+  const int blk = int(blockIdx.x);
+  if (blk >= n_table_blocks) {  // (uniform per block) what dipole_step_records_kernel does
+    const int64_t a = int64_t(blk - n_table_blocks) * kDsBlock + threadIdx.x;
+    double m[3] = {0.0, 0.0, 0.0};
+    if (a < N) {
+      const T mx = mu[3 * a], my = mu[3 * a + 1], mz = mu[3 * a + 2];
+      recp[a] = AtomRecord<T>{pos[3 * a], pos[3 * a + 1], pos[3 * a + 2], T(0)};
+      recm[a] = AtomRecord<T>{mx, my, mz, T(0)};
+      m[0] = double(mx), m[1] = double(my), m[2] = double(mz);
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const double s = block_sum<kStepWaves>(m[c], red);
+      if (threadIdx.x == 0) mu_part[3 * int64_t(blk - n_table_blocks) + c] = s;
+    }
+    return;
+  }
+  double A[9];
+  const EsCell g = es_invert_cell(cell, A);
+  if (blk == 0 && threadIdx.x == 0) {
+    // A^-1 = (A^-T)^T, row-major
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+      for (int c = 0; c < 3; ++c) geom[3 * r + c] = g.recip[3 * c + r];
+    geom[9] = g.inv_vol;
+    geom[10] = g.bad ? 1.0 : 0.0;
+    // bit 0: the eager call would choose another k grid for this cell, ns_d = ceil(|a_d| / lr_wavelength)
+    const int ns[3] = {ns0, ns1, ns2};
+    int st = g.bad ? 2 : 0;
+    if (lr_wavelength > 0.0) {
+#pragma unroll
+      for (int d = 0; d < 3; ++d) {
+        const double norm = sqrt(A[3 * d] * A[3 * d] + A[3 * d + 1] * A[3 * d + 1] + A[3 * d + 2] * A[3 * d + 2]);
+        if (!(ceil(norm / lr_wavelength) == double(ns[d]))) st |= 1;
+      }
+    }
+    status[0] = st;
+  }
+  const int64_t k = int64_t(blk) * kDsBlock + threadIdx.x;
+  if (k >= K) return;
+  double kv[3] = {0.0, 0.0, 0.0}, v = 0.0, dv = 0.0;
+  if (!g.bad) {  // (a singular cell: a table of zeros, and the final launch writes NaN as the energy)
+    const double f0 = double(freq[3 * k]), f1 = double(freq[3 * k + 1]), f2 = double(freq[3 * k + 2]);
+#pragma unroll
+    for (int n = 0; n < 3; ++n) kv[n] = (2.0 * kPi) * (f0 * g.recip[n] + f1 * g.recip[3 + n] + f2 * g.recip[6 + n]);
+    lr_kernel_dev(kp, kv[0] * kv[0] + kv[1] * kv[1] + kv[2] * kv[2], v, dv);
+    const double m = double(mult[k]);
+    v *= m;
+    dv *= m;
+  }
+  kvec[3 * k] = T(kv[0]), kvec[3 * k + 1] = T(kv[1]), kvec[3 * k + 2] = T(kv[2]);
+  G[k] = T(v);
+  if (dG) dG[k] = T(dv);
+}
+
+// ---- 5'. finish: dipole_step_finish_kernel with 1/V and bg/V from the geometry record ----------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(kDsBlock) void dipole_cell_step_finish_kernel(int64_t N, int n_slices, T self_term, double background,
+                                                                          const double* __restrict__ geom,
+                                                                          const AtomRecord<T>* __restrict__ recm,
+                                                                          const T* __restrict__ part, const T* __restrict__ row_out,
+                                                                          const double* __restrict__ mu_part, int64_t n_mu_blocks,
+                                                                          T* __restrict__ forces, T* __restrict__ grad_mu,
+                                                                          double* __restrict__ e_part) {
+  __shared__ double red[kStepWaves];
+  const double inv_vol_d = geom[9];
+  const T inv_vol = T(inv_vol_d), bg_over_v = T(background * inv_vol_d);
+  double M[3] = {0.0, 0.0, 0.0};
+  if (background != 0.0) {  // (uniform, and the same for every cell) sum_j mu_j, the same fixed order in every block
+#pragma unroll
+    for (int c = 0; c < 3; ++c) M[c] = step_strided_sum(mu_part, n_mu_blocks, 3, c, red);
+  }
+  const int sub = threadIdx.x % 16;
+  const int64_t a = int64_t(blockIdx.x) * kStepRowsPerBlock + threadIdx.x / 16;
+  const bool valid = a < N;
+  T f0 = T(0), f1 = T(0), f2 = T(0), b0 = T(0), b1 = T(0), b2 = T(0);
+  if (valid)
+    for (int s = sub; s < n_slices; s += 16) {
+      const T* __restrict__ p = part + (int64_t(s) * N + a) * 6;
+      f0 += p[0], f1 += p[1], f2 += p[2];
+      b0 += p[3], b1 += p[4], b2 += p[5];
+    }
+  f0 = row_sum(f0), f1 = row_sum(f1), f2 = row_sum(f2);
+  b0 = row_sum(b0), b1 = row_sum(b1), b2 = row_sum(b2);
+  double e = 0.0;
+  if (valid && sub == 0) {
+    const T f[3] = {f0, f1, f2}, b[3] = {b0, b1, b2};
+    const AtomRecord<T> m = recm[a];
+    const T mv[3] = {m.x, m.y, m.z};
+    const T* __restrict__ r = row_out + 6 * a;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const T d = (inv_vol * f[c] - self_term * mv[c] + bg_over_v * T(M[c])) + r[c];
+      grad_mu[3 * a + c] = d;
+      forces[3 * a + c] = r[3 + c] - inv_vol * b[c];
+      e += 0.5 * double(mv[c]) * double(d);
+    }
+  }
+  e = block_sum<kStepWaves>(e, red);
+  if (threadIdx.x == 0) e_part[blockIdx.x] = e;
+}
+
+// ---- 6'. final: dipole_step_final_kernel with 1/V and A^-1 from the geometry record; NaN for a bad cell ---------------------------
+template <typename T, bool CELL>
+__global__ __launch_bounds__(kDsBlock) void dipole_cell_step_final_kernel(int64_t n_e_blocks, const double* __restrict__ e_part,
+                                                                         T* __restrict__ energy, int64_t n_row_blocks,
+                                                                         const double* __restrict__ row_cell, int64_t n_k_blocks,
+                                                                         const double* __restrict__ k_cell, int64_t n_mu_blocks,
+                                                                         const double* __restrict__ mu_part, double bg,
+                                                                         const double* __restrict__ geom, T* __restrict__ grad_cell) {
+  __shared__ double red[kStepWaves];
+  __shared__ double tot[9 + kStepCellK + 3];
+  const bool bad = geom[10] != 0.0;
+  const double E = step_strided_sum(e_part, n_e_blocks, 1, 0, red);
+  if (threadIdx.x == 0) energy[0] = bad ? T(NAN) : T(E);
+  if (CELL) {
+    step_cell_totals(row_cell, n_row_blocks, k_cell, n_k_blocks, tot, red);
+    for (int j = 0; j < 3; ++j) {
+      const double s = step_strided_sum(mu_part, n_mu_blocks, 3, j, red);
+      if (threadIdx.x == 0) tot[9 + kStepCellK + j] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x < 9) {
+      const int m = threadIdx.x / 3, n = threadIdx.x % 3;
+      const double* Wr = tot;
+      const double* Wk = tot + 9;
+      const double Ek = tot[9 + 9], inv_vol = geom[9];
+      const double* M = tot + 9 + kStepCellK;
+      const double e_v = inv_vol * (Ek + 0.5 * bg * (M[0] * M[0] + M[1] * M[1] + M[2] * M[2]));  // what scales with 1/V
+      double chain = 0.0;
+      for (int a = 0; a < 3; ++a) chain += geom[3 * a + m] * Wk[3 * a + n];
+      grad_cell[3 * m + n] = bad ? T(NAN) : T(Wr[3 * m + n] - inv_vol * chain - e_v * geom[3 * n + m]);
+    }
+  }
+}
+
 // ---- host --------------------------------------------------------------------------------------------------------------------
-template <typename T, bool EXCL>
-static void dipole_step_rows_launch(hipStream_t st, const mipme_dipole_step_args_t& a, const DipPot<T>& dp, const StepWork& w,
+// Args: mipme_dipole_step_args_t or mipme_dipole_cell_step_args_t (the fields read here have the same names in both)
+template <typename T, bool EXCL, typename Args>
+static void dipole_step_rows_launch(hipStream_t st, const Args& a, const DipPot<T>& dp, const StepWork& w,
                                     const AtomRecord<T>* recp, const AtomRecord<T>* recm) {
   const unsigned blocks = unsigned((a.n_atoms + kStepRowsPerBlock - 1) / kStepRowsPerBlock);
   const T scale = T(a.full_list ? 0.5 : 1.0) * dp.pref;
@@ -397,11 +568,110 @@ static int dipole_step_run(const mipme_dipole_step_args_t& a) {
   return dipole_step_t<T>(a, dp);
 }
 
+template <typename T>
+static int dipole_cell_step_t(const mipme_dipole_cell_step_args_t& a, const DipPot<T>& dp, const KPot& kp) {
+  hipStream_t st = (hipStream_t)a.stream;
+  const int64_t N = a.n_atoms, K = a.n_k;
+  const bool cell = a.cell_gradient != 0;
+  const StepWork w = dcs_work_layout(N, K, cell, a.work);
+  const int64_t n_table_blocks = dcs_table_blocks(K);
+  AtomRecord<T>* recp = (AtomRecord<T>*)a.records;
+  AtomRecord<T>* recm = recp + N;
+  int rc;
+  dipole_cell_step_prep_kernel<T><<<unsigned(n_table_blocks + w.n_atom_blocks), kDsBlock, 0, st>>>(
+      kp, N, K, int(n_table_blocks), (const T*)a.cell, (const int*)a.frequencies, (const int*)a.multiplicities, a.ns[0], a.ns[1],
+      a.ns[2], a.pot->smearing > 0 ? a.lr_wavelength : 0.0, (const T*)a.positions, (const T*)a.dipoles, (T*)a.kvectors, (T*)a.G,
+      cell ? (T*)a.dG : nullptr, recp, recm, w.atom_part, w.head, (int*)a.status);
+  MIPME_LAUNCH_CHECK();
+  if (K > 0) {
+    if ((rc = mipme_dipole_structure(a.stream, a.dtype, N, K, a.positions, a.dipoles, a.kvectors, a.G, cell ? a.dG : nullptr, a.s_cos,
+                                     a.s_sin)))
+      return rc;
+    const int64_t chunk = (K + w.n_slices - 1) / w.n_slices;
+    dipole_step_atom_kernel<T><<<dim3(unsigned(N), unsigned(w.n_slices)), kDsBlock, 0, st>>>(
+        K, chunk, recp, recm, (const T*)a.kvectors, (const T*)a.G, (const T*)a.s_cos, (const T*)a.s_sin, (T*)w.slice_part);
+    MIPME_LAUNCH_CHECK();
+  }
+  if (dp.mode == 2)
+    dipole_step_rows_launch<T, true>(st, a, dp, w, recp, recm);
+  else
+    dipole_step_rows_launch<T, false>(st, a, dp, w, recp, recm);
+  MIPME_LAUNCH_CHECK();
+  if (cell && K > 0) {
+    dipole_step_cellk_kernel<T><<<unsigned(w.n_k_blocks), kDsBlock, 0, st>>>(N, K, (const T*)a.positions, (const T*)a.dipoles,
+                                                                            (const T*)a.kvectors, (const T*)a.G, (const T*)a.dG,
+                                                                            (const T*)a.s_cos, (const T*)a.s_sin, w.k_cell);
+    MIPME_LAUNCH_CHECK();
+  }
+  dipole_cell_step_finish_kernel<T><<<unsigned(w.n_fin_blocks), kDsBlock, 0, st>>>(
+      N, int(w.n_slices), T(a.self_term), a.background, w.head, recm, (const T*)w.slice_part, (const T*)w.row_out, w.atom_part,
+      w.n_atom_blocks, (T*)a.forces, (T*)a.grad_dipoles, w.e_part);
+  MIPME_LAUNCH_CHECK();
+  if (cell)
+    dipole_cell_step_final_kernel<T, true><<<1, kDsBlock, 0, st>>>(w.n_fin_blocks, w.e_part, (T*)a.energy, w.n_row_blocks, w.row_cell,
+                                                                  w.n_k_blocks, w.k_cell, w.n_atom_blocks, w.atom_part, a.background,
+                                                                  w.head, (T*)a.grad_cell);
+  else
+    dipole_cell_step_final_kernel<T, false><<<1, kDsBlock, 0, st>>>(w.n_fin_blocks, w.e_part, (T*)a.energy, 0, nullptr, 0, nullptr, 0,
+                                                                   nullptr, a.background, w.head, nullptr);
+  MIPME_LAUNCH_CHECK();
+  return MIPME_OK;
+}
+
+template <typename T>
+static int dipole_cell_step_run(const mipme_dipole_cell_step_args_t& a) {
+  DipPot<T> dp;
+  int rc = make_dippot<T>(a.pot, dp);
+  if (rc) return rc;
+  KPot kp{};
+  if (a.n_k > 0) {  // the reciprocal-space kernel 4 pi prefactor exp(-sigma^2 k^2 / 2) / k^2 is Coulomb's
+    mipme_potential_t coulomb{};
+    coulomb.kind = MIPME_COULOMB, coulomb.exponent = 1, coulomb.smearing = a.pot->smearing, coulomb.prefactor = a.pot->prefactor;
+    coulomb.exclusion_radius = -1.0, coulomb.exclusion_degree = 1;
+    if ((rc = make_kpot(&coulomb, kp))) return rc;
+  }
+  return dipole_cell_step_t<T>(a, dp, kp);
+}
+
 }  // namespace mipme
 
 using namespace mipme;
 
 extern "C" {
+
+// (the entry points of the step that follows its cell come first: templates are instantiated in the order of their first use, and
+// with this order the kernels of mipme_dipole_step stay where they were at the end of the code object, byte for byte)
+int64_t mipme_dipole_cell_step_work(int64_t n_atoms, int64_t n_k, int cell_gradient) {
+  if (n_atoms < 1 || n_atoms > kCompactMaxAtoms || n_k < 0 || n_k > int64_t(kStepKPerBlock) * 0x7fffffff) return 0;
+  return dcs_work_layout(n_atoms, n_k, cell_gradient != 0, nullptr).total;
+}
+
+int mipme_dipole_cell_step(const mipme_dipole_cell_step_args_t* in) {
+  const char* who = "mipme_dipole_cell_step";
+  mipme_dipole_cell_step_args_t a;
+  int rc = load_args(in, a, MIPME_DIPOLE_CELL_STEP_VERSION, who);
+  if (rc) return rc;
+  // everything the arguments alone decide, before anything touches a device
+  MIPME_REQUIRE(a.dtype == MIPME_F32 || a.dtype == MIPME_F64, "%s: invalid dtype %d", who, int(a.dtype));
+  MIPME_REQUIRE(a.pot != nullptr, "%s: dipole descriptor is NULL", who);
+  MIPME_REQUIRE(a.n_k >= 0 && a.n_k <= int64_t(kStepKPerBlock) * 0x7fffffff, "%s: n_k must be >= 0, got %lld", who, (long long)a.n_k);
+  MIPME_REQUIRE(a.n_k == 0 || a.pot->smearing > 0,
+                "%s: n_k is %lld but the potential has no smearing (`smearing` is %g): a direct potential has no reciprocal part",
+                who, (long long)a.n_k, a.pot->smearing);
+  MIPME_REQUIRE(a.n_k == 0 || (std::isfinite(a.lr_wavelength) && a.lr_wavelength > 0 && a.ns[0] >= 1 && a.ns[1] >= 1 && a.ns[2] >= 1),
+                "%s: lr_wavelength must be positive and ns >= 1 (the grid `status` compares with), got %g and (%d, %d, %d)", who,
+                a.lr_wavelength, int(a.ns[0]), int(a.ns[1]), int(a.ns[2]));
+  MIPME_REQUIRE(!(a.pot->exclusion_radius > 0) || a.pot->exclusion_degree >= 1, "%s: exclusion_degree must be >= 1, got %d", who,
+                int(a.pot->exclusion_degree));
+  if ((rc = check_step_rows(a.shift_format, a.n_atoms, who))) return rc;
+  MIPME_REQUIRE(!a.cell_gradient || a.grad_cell, "%s: cell_gradient needs grad_cell", who);
+  MIPME_REQUIRE(!a.cell_gradient || a.n_k == 0 || a.dG, "%s: cell_gradient needs dG (n_k reals of scratch)", who);
+  MIPME_REQUIRE(a.status != nullptr, "%s: status is NULL (one int32 on the device, written by every call)", who);
+  MIPME_REQUIRE(a.positions && a.dipoles && a.cell && a.row_ptr && a.entries && a.records && a.energy && a.forces && a.grad_dipoles &&
+                    a.work && (a.n_k == 0 || (a.frequencies && a.multiplicities && a.kvectors && a.G && a.s_cos && a.s_sin)),
+                "%s: NULL required buffer", who);
+  DT_SWITCH(a.dtype, dipole_cell_step_run<float>(a), dipole_cell_step_run<double>(a));
+}
 
 int64_t mipme_dipole_step_work(int64_t n_atoms, int64_t n_k, int cell_gradient) {
   if (n_atoms < 1 || n_atoms > kCompactMaxAtoms || n_k < 0 || n_k > int64_t(kStepKPerBlock) * 0x7fffffff) return 0;

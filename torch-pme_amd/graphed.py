@@ -1167,7 +1167,8 @@ def _ewald_kgrid(cell, lr_wavelength):
 
 class GraphedDipoleStep(_ExplicitListStep):
     """``E, F, dE_dmu = step(positions, dipoles)`` for a :class:`~torchpme_amd.CalculatorDipole`, replayed from one HIP graph: the
-    MD form of the eager call for a fixed neighbour list and cell (dipolar fluids, polarisable models).
+    MD form of the eager call for a fixed neighbour list and a cell that is fixed or, with ``follow_cell=True``, an input of
+    every call (dipolar fluids, polarisable models).
 
     With ``V`` what the eager calculator returns for the same arguments and ``neighbor_vectors = r_j - r_i + S cell`` -- the step
     forms the pair vectors itself from the list and its cell shifts -- ``E = sum_i mu_i . V_i`` (0-dim), ``F = -dE/dpositions``
@@ -1178,8 +1179,21 @@ class GraphedDipoleStep(_ExplicitListStep):
 
     All outputs are buffers of the object, overwritten by every call.  A call copies the given positions and dipoles into the
     object's buffers and replays the graph: no host reads, and -- as on the eager dipole path -- no check for non-finite input.
-    Every sum of the step has a fixed order (no floating-point atomics), so equal inputs give equal bits.  The cell is fixed for
-    the life of the object; a new list needs :meth:`recapture`.
+    Every sum of the step has a fixed order (no floating-point atomics), so equal inputs give equal bits.  A new list needs
+    :meth:`recapture`.
+
+    Without ``follow_cell`` the cell is fixed for the life of the object: everything that depends on it is built once on the host.
+    With ``follow_cell=True`` the cell is an input of the replay like the positions (NPT runs, cell relaxations, strain scans):
+    ``step(positions, dipoles, cell)`` copies whichever of the three are given into the object's buffers (:attr:`cell` is the
+    (3, 3) input buffer) and replays the one graph -- no host reads, nothing re-captured.  The k-vectors, G(k), dG/dk^2, the
+    inverse cell, 1/V and the Cartesian shift vectors of the pair rows are rebuilt on the device inside the replay from the nine
+    values of the cell buffer (``mipme_dipole_cell_step``; as many launches as the fixed-cell step).  The outputs mean what they
+    mean above, at the current cell.  The SET of k-vectors is frozen at construction, as in :class:`GraphedEwaldStep`: the
+    integer frequencies the eager call chooses for the construction cell, ``ns_d = ceil(|a_d| / lr_wavelength)`` (:attr:`ns`),
+    one of every pair +-k (:attr:`n_k`).  :attr:`status` is a device ``int32`` (1,) tensor every replay writes -- bit 0: the
+    eager call would sum another grid for this cell (never set for a direct potential); bit 1: ``det(cell)`` is zero or not
+    finite (then E is NaN and the k table zeros) -- and :meth:`kgrid_matches` decides bit 0 on the host.  The skin of the list
+    under a changing cell is the caller's business.
 
     E is quadratic in the dipoles, so the structure factors are formed once, one kernel evaluates the field and the position
     gradient from one phase per (atom, k), and only one of every pair +-k of the reciprocal grid is summed (:attr:`n_k` vectors);
@@ -1194,10 +1208,11 @@ class GraphedDipoleStep(_ExplicitListStep):
     :param neighbor_indices, neighbor_shifts: an explicit list (P, 2) with integer cell shifts (P, 3) in [-3, 3]; at most 2^22 atoms
     :param cell_gradient: also return ``dE/dcell``
     :param warmup: eager runs before the capture
+    :param follow_cell: the cell is an input of every replay (``cell=`` of a call and of :meth:`recapture`)
     """
 
     def __init__(self, calculator, dipoles, cell, positions, neighbor_indices, neighbor_shifts, cell_gradient: bool = False,
-                 warmup: int = 3):
+                 warmup: int = 3, follow_cell: bool = False):
         from .calculators import _integer_frequencies, _reciprocal_and_det
         from .dipoles import CalculatorDipole
 
@@ -1223,6 +1238,7 @@ class GraphedDipoleStep(_ExplicitListStep):
             _lib.require_device(t, name)
         self.calc = calculator
         self.cell_gradient = bool(cell_gradient)
+        self.follow_cell = bool(follow_cell)
         self.full = bool(calculator.full_neighbor_list)
         lib = self._lib = _lib.load()
         device, dtype = positions.device, positions.dtype
@@ -1237,6 +1253,11 @@ class GraphedDipoleStep(_ExplicitListStep):
         det = float(np.linalg.det(cell_host))
         if det == 0.0 or not np.isfinite(det):
             raise ValueError(f"provided `cell` has a determinant of {det}, i.e. it is not a valid unit cell")
+        if self.follow_cell:
+            self._init_follow_cell(sm, eps, pref, new)
+            self._finish_init(positions, dipoles, neighbor_indices, neighbor_shifts, warmup, new,
+                              lib.mipme_dipole_cell_step_work)
+            return
         self._inv_volume = 1.0 / abs(det)
         self._inv_cell = torch.tensor(np.linalg.inv(cell_host), dtype=dtype, device=device).contiguous()
         self._self_term, self._background = 0.0, 0.0
@@ -1262,16 +1283,82 @@ class GraphedDipoleStep(_ExplicitListStep):
                 self._kvec, self._G = kvec, G * w  # the multiplicity folded into the filter
                 self._dG = dG * w if self.cell_gradient else None
                 self._Sc, self._Ss = new(K), new(K)
+        self._finish_init(positions, dipoles, neighbor_indices, neighbor_shifts, warmup, new, lib.mipme_dipole_step_work)
+
+    def _init_follow_cell(self, sm, eps, pref, new):
+        """What ``follow_cell=True`` freezes: the integer k grid of the construction cell (the rule and the helper of
+        :class:`GraphedEwaldStep`) and the constants of the potential that do not depend on the cell.  The k-vectors, G, dG, 1/V
+        and the inverse cell are buffers every replay writes."""
+        self.status = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self._self_term, self._background = 0.0, 0.0
+        self._freq = self._mult = self._kvec = self._G = self._dG = self._Sc = self._Ss = None
+        self.n_k, self.ns, self.lr_wavelength = 0, (1, 1, 1), 0.0  # (a direct potential: no grid to compare with)
+        if sm is None:
+            return
+        self.lr_wavelength = float(self.calc.lr_wavelength)
+        self.ns, freq, mult = _ewald_kgrid(self.cell, self.lr_wavelength)
+        K = self.n_k = int(len(mult))
+        alpha = 0.5 / sm**2
+        self._self_term = pref * 4 * math.pi / 3 * (alpha / math.pi) ** 1.5
+        self._background = pref * 4 * math.pi / (2 * eps + 1) if eps != 0.0 else 0.0
+        if K > 0:
+            self._freq, self._mult = torch.tensor(freq, device=self.device), torch.tensor(mult, device=self.device)
+            self._kvec, self._G, self._Sc, self._Ss = new(K, 3), new(K), new(K), new(K)
+            self._dG = new(K) if self.cell_gradient else None
+
+    def _finish_init(self, positions, dipoles, neighbor_indices, neighbor_shifts, warmup, new, work_size):
+        N = self.n_atoms
         self.pos = positions.detach().clone().contiguous()
         self.mu = dipoles.detach().clone().contiguous()
         self._rec = new(2 * N, 4)
         self.energy, self.forces, self.dipole_grad = new(), new(N, 3), new(N, 3)
         self.cell_grad = new(3, 3) if self.cell_gradient else None
-        self._work = new(max(1, int(lib.mipme_dipole_step_work(N, self.n_k, int(self.cell_gradient)))), dt=torch.float64)
+        self._work = new(max(1, int(work_size(N, self.n_k, int(self.cell_gradient)))), dt=torch.float64)
         self._warmup = max(1, int(warmup))
         self._capture(neighbor_indices, neighbor_shifts)
 
+    def kgrid_matches(self, cell) -> bool:
+        """Whether the eager calculator would sum the step's k grid for ``cell``: every ``ceil(|a_d| / lr_wavelength)`` equals
+        the one of the construction cell (bit 0 of :attr:`status` clear), decided on the host with the rule of
+        :meth:`GraphedEwaldStep.kgrid_matches`.  A direct potential sums no grid: always ``True``."""
+        self._need_follow_cell("kgrid_matches")
+        if self.lr_wavelength <= 0.0:
+            return True
+        return GraphedEwaldStep._ns_of(cell, self.lr_wavelength) == self.ns
+
+    def _need_follow_cell(self, what):
+        if not self.follow_cell:
+            raise ValueError(f"GraphedDipoleStep: {what} needs an object built with follow_cell=True: the cell of this one is "
+                             "fixed for the life of the object")
+
+    def _checked_cell(self, cell):
+        """The ``cell=`` argument of a call or of :meth:`recapture`, refused before anything of the object changes."""
+        if cell is None:
+            return None
+        self._need_follow_cell("`cell=`")
+        if not isinstance(cell, torch.Tensor) or tuple(cell.shape) != (3, 3) or cell.dtype != self.dtype or cell.device != self.device:
+            got = (f"a {type(cell).__name__}" if not isinstance(cell, torch.Tensor) else
+                   f"shape {list(cell.shape)}, {cell.dtype} on {cell.device}")
+            raise ValueError(f"GraphedDipoleStep: `cell` must be a tensor with shape [3, 3], {self.dtype} on {self.device}, got {got}")
+        return cell
+
+    def _launch_follow_cell(self):
+        with _lib.on_device(self.device):
+            a = _lib.DipoleCellStepArgs(
+                stream=_lib.current_stream(self.device), dtype=self._dt, full_list=int(self.full), pot=C.pointer(self._desc),
+                self_term=self._self_term, background=self._background, n_atoms=self.n_atoms, n_k=self.n_k,
+                lr_wavelength=self.lr_wavelength, ns=(C.c_int32 * 3)(*self.ns), cell_gradient=int(self.cell_gradient),
+                positions=self.pos.data_ptr(), dipoles=self.mu.data_ptr(), cell=self.cell.data_ptr(),
+                frequencies=_lib.ptr(self._freq), multiplicities=_lib.ptr(self._mult), row_ptr=self._row_ptr.data_ptr(),
+                entries=self._ent32.data_ptr(), shift_format=2, records=self._rec.data_ptr(), kvectors=_lib.ptr(self._kvec),
+                G=_lib.ptr(self._G), dG=_lib.ptr(self._dG), s_cos=_lib.ptr(self._Sc), s_sin=_lib.ptr(self._Ss),
+                energy=self.energy.data_ptr(), forces=self.forces.data_ptr(), grad_dipoles=self.dipole_grad.data_ptr(),
+                grad_cell=_lib.ptr(self.cell_grad), status=self.status.data_ptr(), work=self._work.data_ptr())
+            _lib.check(self._lib.mipme_dipole_cell_step(C.byref(a)))
+
     def _launch(self):
+        if self.follow_cell:
+            return self._launch_follow_cell()
         with _lib.on_device(self.device):
             a = _lib.DipoleStepArgs(
                 stream=_lib.current_stream(self.device), dtype=self._dt, full_list=int(self.full), pot=C.pointer(self._desc),
@@ -1285,19 +1372,26 @@ class GraphedDipoleStep(_ExplicitListStep):
             _lib.check(self._lib.mipme_dipole_step(C.byref(a)))
 
     def recapture(self, neighbor_indices, neighbor_shifts, positions: torch.Tensor | None = None,
-                  dipoles: torch.Tensor | None = None) -> None:
-        """New neighbour list: rebuild the pair topology and capture the step again; every other buffer is kept."""
+                  dipoles: torch.Tensor | None = None, cell: torch.Tensor | None = None) -> None:
+        """New neighbour list: rebuild the pair topology and capture the step again; every other buffer (and, with
+        ``follow_cell``, the k grid) is kept.  ``cell`` needs ``follow_cell=True``.  The list and the cell are validated before
+        anything of the object changes."""
+        cell = self._checked_cell(cell)
         _check_explicit_list("GraphedDipoleStep", neighbor_indices, neighbor_shifts)
-        self._capture(neighbor_indices, neighbor_shifts, [(self.pos, positions), (self.mu, dipoles)])
+        self._capture(neighbor_indices, neighbor_shifts, [(self.pos, positions), (self.mu, dipoles), (self.cell, cell)])
 
-    def __call__(self, positions: torch.Tensor | None = None, dipoles: torch.Tensor | None = None):
-        """``E, F, dE_dmu`` (+ ``dE_dcell`` with ``cell_gradient``) of the current -- or the given -- positions and dipoles: up to
-        two small copies and one graph replay."""
+    def __call__(self, positions: torch.Tensor | None = None, dipoles: torch.Tensor | None = None,
+                 cell: torch.Tensor | None = None):
+        """``E, F, dE_dmu`` (+ ``dE_dcell`` with ``cell_gradient``) of the current -- or the given -- positions, dipoles and, with
+        ``follow_cell=True``, cell: up to three small copies and one graph replay."""
+        cell = self._checked_cell(cell)
         with torch.no_grad():
             if positions is not None:
                 self.pos.copy_(positions)
             if dipoles is not None:
                 self.mu.copy_(dipoles)
+            if cell is not None:
+                self.cell.copy_(cell)
         self.graph.replay()
         out = (self.energy, self.forces, self.dipole_grad)
         if self.cell_gradient:
