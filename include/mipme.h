@@ -1320,6 +1320,95 @@ typedef struct mipme_dipole_cell_step_args {
 int mipme_dipole_cell_step(const mipme_dipole_cell_step_args_t* args);
 int64_t mipme_dipole_cell_step_work(int64_t n_atoms, int64_t n_k, int cell_gradient);
 
+/* The step above for MANY small systems in one call: F frames of point dipoles, each with its own cell, atom count, k grid and
+ * pair list, one dipole descriptor and list kind for all (GraphedDipoleBatch, graphed.py; csrc/dipole_batch.hip).  For frame f,
+ * energies[f], its slice of forces and grad_dipoles, grad_cells[f] and status[f] mean word for word what energy, forces,
+ * grad_dipoles, grad_cell and status of mipme_dipole_cell_step mean for that system alone, with the frame's own cell, k grid,
+ * dipoles and list; self_term and background are those of mipme_dipole_cell_step_args_t.  The bits a frame gets depend on its own
+ * inputs only -- not on its index, on n_frames or on the other frames.  A singular cell gives ITS frame a zero k table, E = NaN,
+ * grad_cell = NaN and status bit 1, and changes nothing of any other frame.
+ * Concatenated buffers, all in frame order (N_f, K_f, P_f: atoms, compacted k-vectors and pairs of frame f):
+ *   positions, dipoles, forces, grad_dipoles (sum N, 3) each; records 8 sum N reals (16-byte aligned): the two record arrays of
+ *   frame f lie as the single step lays them out, N_f position records then N_f dipole records, from record 2 atom0_f;
+ *   cells (F, 3, 3) -- DEVICE, read by every call --, energies (F), grad_cells (F, 3, 3), status int32 (F);
+ *   frequencies int32 (sum K, 3), multiplicities int32 (sum K), kvectors 3 sum K reals, G, dG (with cell_gradient), s_cos, s_sin
+ *   sum K reals each (all nullable when sum K = 0: a frame whose grid is (1, 1, 1) has K_f = 0 and is served, and so is a
+ *   potential without smearing, whose frames all have K_f = 0);
+ *   row_ptr int32: 2 N_f + 1 words per frame, entries int32: 2 P_f + 1 words per frame (shift_format 2), both LOCAL to the frame:
+ *   the row pointers count from the frame's first entry word and the partners from the frame's first atom.
+ * The HOST arrays atom_ptr, k_ptr, entry_ptr (int64, n_frames + 1 each, first element 0: prefix sums of N_f, K_f and
+ * 2 P_f + 1) say where a frame's slices begin; they are read by the call itself (to size the launches), never by a kernel.
+ * The frame table.  mipme_dipole_batch_table_build fills a HOST buffer of mipme_dipole_batch_table_bytes bytes from atom_ptr,
+ * k_ptr, entry_ptr, ns (int32 (F, 3): the grid `status` compares with, per frame; (1, 1, 1) without smearing) and cell_gradient;
+ * the caller uploads it once per capture and passes the copy as device_table.  Nothing in it depends on any cell's values.  It is
+ * the table of mipme_ewald_batch with the layout constants of the dipole step:
+ *   per frame (152 bytes): the offsets of its slices of every concatenated buffer, N_f, K_f, the k-vectors per slice of its atom
+ *   blocks, the offsets of the parts of its work area, its block counts and ns;
+ *   per workgroup of the prep, k (structure and cell k), atom and row (rows and finish) launches (8 bytes each): (frame, local
+ *   block), in frame order -- every launch is a flat grid with exactly the workgroups its frames need, and no workgroup
+ *   straddles two frames.  Per frame these are  max(1, ceil(K/256)) + ceil(N/256),  ceil(K/8),  N x slices(N, K)  and
+ *   ceil(N/16)  workgroups; slices(N, K) = min(ceil(2048 / N), max(1, floor(K / 1024))), 0 for K = 0: the rule of
+ *   mipme_dipole_cell_step, from the frame's own sizes alone.
+ * Launches, one after the other on `stream` (capturable: a single chain, nothing runs beside anything else), each ONCE for the
+ * whole batch and each doing for the frame of a workgroup what the launch of the same name does in mipme_dipole_cell_step: prep,
+ * structure [sum K > 0], atoms [sum K > 0], rows, cell k [cell_gradient, sum K > 0], finish, final (one workgroup per frame).
+ * No atomics and no workgroup waits for another: every cross-block sum is float64 block partials of ONE frame added in index
+ * order by a later launch.  No address, loop bound or launch shape depends on any cell's values.
+ * Scratch, all written: records, kvectors, G, dG, s_cos, s_sin as above; work: float64[mipme_dipole_batch_work(...)] = the sum
+ * over the frames of mipme_dipole_cell_step_work(N_f, K_f, cell_gradient), the work areas of the frames one behind the other,
+ * each laid out as the single step's.  Both size functions return 0 for sizes the batch does not serve.
+ * Limits: n_frames in 1..2^20; every frame 1..2^22 atoms, K_f >= 0; sum N, sum K and sum (2 P_f + 1) below 2^31; at most
+ * 2^24 - 1 workgroups in any launch (256 threads each: fewer than 2^32 threads), which bounds sum_f N_f slices_f.
+ * MIPME_EINVAL before anything is launched: a NULL struct or required buffer, another struct version, an implausible size, a bad
+ * dtype, a NULL descriptor, an exclusion radius with exclusion_degree < 1, another shift format, n_frames outside 1..2^20, host
+ * arrays that break a limit above, sum K > 0 with a potential without smearing, lr_wavelength not finite or <= 0 (accepted as
+ * <= 0 only when sum K = 0 and the potential has no smearing), cell_gradient without grad_cells (or without dG when sum K > 0).
+ * Versioned like mipme_ewald_step_args_t: size and version first, fields only ever appended. */
+#define MIPME_DIPOLE_BATCH_VERSION 1
+typedef struct mipme_dipole_batch_args {
+  uint32_t size;
+  uint32_t version;
+  void* stream;
+  int32_t dtype;
+  int32_t full_list;
+  const mipme_dipole_t* pot;
+  double self_term;
+  double background;
+  int32_t n_frames;
+  int32_t cell_gradient;
+  double lr_wavelength;
+  const int64_t* atom_ptr;
+  const int64_t* k_ptr;
+  const int64_t* entry_ptr;
+  const void* device_table;
+  const void* positions;
+  const void* dipoles;
+  const void* cells;
+  const void* frequencies;
+  const void* multiplicities;
+  const void* row_ptr;
+  const void* entries;
+  int32_t shift_format;
+  int32_t _pad;
+  void* records;
+  void* kvectors;
+  void* G;
+  void* dG;
+  void* s_cos;
+  void* s_sin;
+  void* energies;
+  void* forces;
+  void* grad_dipoles;
+  void* grad_cells;
+  void* status;
+  void* work;
+} mipme_dipole_batch_args_t;
+int mipme_dipole_batch(const mipme_dipole_batch_args_t* args);
+int64_t mipme_dipole_batch_work(int n_frames, const int64_t* atom_ptr, const int64_t* k_ptr, int cell_gradient);
+int64_t mipme_dipole_batch_table_bytes(int n_frames, const int64_t* atom_ptr, const int64_t* k_ptr, int cell_gradient);
+int mipme_dipole_batch_table_build(int n_frames, const int64_t* atom_ptr, const int64_t* k_ptr, const int64_t* entry_ptr,
+                                   const int32_t* ns, int cell_gradient, void* host_table, int64_t host_table_bytes);
+
 /* ---- device neighbour list (the reference uses third-party vesin on the host,
  * tests/helpers.py:240-275, and hands a fresh list to every call, examples/02-neighbor-lists-usage.py:97-164) -------------
  * One cell-list traversal, two products:

@@ -10,8 +10,8 @@ from . import lib, library, ops, prefactors, tuning, workloads  # noqa: F401  (l
 from ._lib import LIB_PATH, MipmeError  # noqa: F401
 from .calculators import Calculator, EwaldCalculator, P3MCalculator, PMECalculator
 from .dipoles import CalculatorDipole, PotentialDipole
-from .graphed import (EnergyLog, GraphedCombinedStep, GraphedDipoleStep, GraphedEnergyForces, GraphedEwaldBatch,
-                      GraphedEwaldStep, GraphedFrameBatch)
+from .graphed import (EnergyLog, GraphedCombinedStep, GraphedDipoleBatch, GraphedDipoleStep, GraphedEnergyForces,
+                      GraphedEwaldBatch, GraphedEwaldStep, GraphedFrameBatch)
 from .neighbors import NeighborStream, neighbor_list, neighbor_list_device
 from .ops import pair_distances, weighted_sum
 from .potentials import CombinedPotential, CoulombPotential, InversePowerLawPotential, Potential, SplinePotential
@@ -35,6 +35,7 @@ __all__ = [
     "weighted_sum",
     "EnergyLog",
     "GraphedCombinedStep",
+    "GraphedDipoleBatch",
     "GraphedDipoleStep",
     "GraphedEnergyForces",
     "GraphedEwaldBatch",

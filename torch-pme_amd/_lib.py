@@ -49,6 +49,7 @@ EXPORTS = (
     "mipme_ewald_step", "mipme_ewald_step_work",
     "mipme_ewald_batch", "mipme_ewald_batch_work", "mipme_ewald_batch_table_bytes", "mipme_ewald_batch_table_build",
     "mipme_dipole_cell_step", "mipme_dipole_cell_step_work",
+    "mipme_dipole_batch", "mipme_dipole_batch_work", "mipme_dipole_batch_table_bytes", "mipme_dipole_batch_table_build",
 )
 
 
@@ -458,6 +459,36 @@ class EwaldBatchArgs(_VersionedArgs):
         C.Structure.__init__(self, size=C.sizeof(type(self)), version=EWALD_BATCH_VERSION, **fields)
 
 
+DIPOLE_BATCH_VERSION = 1
+
+
+class DipoleBatchArgs(_VersionedArgs):
+    """``mipme_dipole_batch_args_t`` (version ``MIPME_DIPOLE_BATCH_VERSION``); ``atom_ptr``, ``k_ptr`` and ``entry_ptr`` are HOST
+    arrays of int64"""
+
+    _fields_ = [
+        ("size", C.c_uint32), ("version", C.c_uint32),
+        ("stream", C.c_void_p), ("dtype", C.c_int32), ("full_list", C.c_int32),
+        ("pot", C.POINTER(DipoleDesc)), ("self_term", C.c_double), ("background", C.c_double),
+        ("n_frames", C.c_int32), ("cell_gradient", C.c_int32),
+        ("lr_wavelength", C.c_double),
+        ("atom_ptr", C.c_void_p), ("k_ptr", C.c_void_p), ("entry_ptr", C.c_void_p), ("device_table", C.c_void_p),
+        ("positions", C.c_void_p), ("dipoles", C.c_void_p), ("cells", C.c_void_p),
+        ("frequencies", C.c_void_p), ("multiplicities", C.c_void_p),
+        ("row_ptr", C.c_void_p), ("entries", C.c_void_p), ("shift_format", C.c_int32), ("_pad", C.c_int32),
+        ("records", C.c_void_p), ("kvectors", C.c_void_p), ("G", C.c_void_p), ("dG", C.c_void_p),
+        ("s_cos", C.c_void_p), ("s_sin", C.c_void_p),
+        ("energies", C.c_void_p), ("forces", C.c_void_p), ("grad_dipoles", C.c_void_p), ("grad_cells", C.c_void_p),
+        ("status", C.c_void_p), ("work", C.c_void_p),
+    ]
+
+    def __init__(self, **fields):
+        unknown = set(fields) - {name for name, _ in self._fields_}
+        if unknown:
+            raise TypeError(f"{type(self).__name__}: unknown field(s) {sorted(unknown)}")
+        C.Structure.__init__(self, size=C.sizeof(type(self)), version=DIPOLE_BATCH_VERSION, **fields)
+
+
 #: OR-ed into a shift format: rows written by ``mipme_nl_stream`` (``row_ptr`` int32[3N+1], every neighbour once per row)
 ROWS_PADDED = 0x100
 FWD_RHO_MESH_UNUSED = 1  # mipme_kspace_forward_args_t.flags: the caller never reads rho_mesh after the call
@@ -536,6 +567,8 @@ def _declare(lib):
         "mipme_ewald_step": [C.POINTER(EwaldStepArgs)],
         "mipme_ewald_batch": [C.POINTER(EwaldBatchArgs)],
         "mipme_ewald_batch_table_build": [ci, vp, vp, vp, vp, ci, vp, i64],
+        "mipme_dipole_batch": [C.POINTER(DipoleBatchArgs)],
+        "mipme_dipole_batch_table_build": [ci, vp, vp, vp, vp, ci, vp, i64],
         "mipme_dot_forward": [vp, ci, i64, vp, vp, vp, vp],
         "mipme_dot_backward": [vp, ci, i64, vp, vp, vp, vp, vp],
         "mipme_energy_log_push": [vp, ci, ci, vp, vp, vp, ci],
@@ -627,6 +660,10 @@ def _declare(lib):
     lib.mipme_ewald_batch_work.argtypes = [ci, vp, vp, ci]
     lib.mipme_ewald_batch_table_bytes.restype = i64
     lib.mipme_ewald_batch_table_bytes.argtypes = [ci, vp, vp, ci]
+    lib.mipme_dipole_batch_work.restype = i64
+    lib.mipme_dipole_batch_work.argtypes = [ci, vp, vp, ci]
+    lib.mipme_dipole_batch_table_bytes.restype = i64
+    lib.mipme_dipole_batch_table_bytes.argtypes = [ci, vp, vp, ci]
     lib.mipme_frames_slab_work.restype = i64
     lib.mipme_frames_slab_work.argtypes = []
     lib.mipme_frames_table_bytes.restype = i64

@@ -22,91 +22,15 @@
 // status bit 1, and no other frame anything.
 #include <cmath>
 
+#include "batch_table.h"  // EbFrame, EbBlock, EbLayout, eb_layout: the frame table, shared with dipole_batch.hip
 #include "ewald_step_bodies.h"
 #include "ewald_step_device.h"
 #include "host.h"
 
 namespace mipme {
 
-constexpr int kEbMaxFrames = 1 << 20;
-constexpr int64_t kEbMaxBlocks = (int64_t(1) << 24) - 1;  // workgroups per launch: 256 threads each, fewer than 2^32 threads
-constexpr int64_t kEbMaxSum = 0x7fffffff;                 // sum of the atoms, of the k-vectors, of the entries: int32 on the host side
-
-// One frame of the table.  Offsets count from the start of the concatenated buffers (atoms, k-vectors, row pointers, entries) and
-// of the work area (float64 slots).
-struct EbFrame {
-  int64_t atom0, n_atoms, k0, n_k, rp0, ent0, chunk;
-  int64_t geom, q_part, e_part, row_cell, k_cell, row_out, slice_part;
-  int32_t n_table_blocks, n_atom_blocks, n_fin_blocks, n_row_blocks, n_k_blocks, n_slices;
-  int32_t ns[3], _pad;
-};
-static_assert(sizeof(EbFrame) == 152, "mipme_ewald_batch_table_bytes documents 152 bytes per frame");
-struct EbBlock {
-  int32_t frame, local;
-};
-static_assert(sizeof(EbBlock) == 8, "mipme_ewald_batch_table_bytes documents 8 bytes per workgroup");
-
-struct EbLayout {
-  int64_t n_prep, n_kblk, n_atomblk, n_rowblk;  // workgroups of the launches
-  int64_t sum_atoms, sum_k, work_total, table_bytes;
-};
-
-// The sizes decide everything: false for sizes the batch does not serve.  frames / blocks (nullable): the host table to fill.
-static bool eb_layout(int F, const int64_t* atom_ptr, const int64_t* k_ptr, const int64_t* entry_ptr, const int32_t* ns, bool cell,
-                      EbLayout& L, EbFrame* frames, EbBlock* blocks) {
-  L = EbLayout{};
-  if (F < 1 || F > kEbMaxFrames || !atom_ptr || !k_ptr || atom_ptr[0] != 0 || k_ptr[0] != 0) return false;
-  if (entry_ptr && entry_ptr[0] != 0) return false;
-  for (int f = 0; f < F; ++f) {
-    const int64_t N = atom_ptr[f + 1] - atom_ptr[f], K = k_ptr[f + 1] - k_ptr[f];
-    if (N < 1 || N > kCompactMaxAtoms || K < 0 || K > kEbMaxSum) return false;
-    if (atom_ptr[f + 1] > kEbMaxSum || k_ptr[f + 1] > kEbMaxSum) return false;
-    if (entry_ptr && (entry_ptr[f + 1] - entry_ptr[f] < 1 || entry_ptr[f + 1] > kEbMaxSum)) return false;  // (2 P_f + 1 words)
-    const EsWork w = es_work_layout(N, K, cell, nullptr);
-    const int64_t n_k8 = (K + kEsKPerBlock - 1) / kEsKPerBlock;
-    L.n_prep += w.n_table_blocks + w.n_atom_blocks;
-    L.n_kblk += n_k8;
-    L.n_atomblk += N * w.n_slices;
-    L.n_rowblk += w.n_fin_blocks;
-    if (L.n_prep > kEbMaxBlocks || L.n_kblk > kEbMaxBlocks || L.n_atomblk > kEbMaxBlocks || L.n_rowblk > kEbMaxBlocks) return false;
-    L.work_total += w.total;
-  }
-  L.sum_atoms = atom_ptr[F], L.sum_k = k_ptr[F];
-  L.table_bytes = int64_t(sizeof(EbFrame)) * F + int64_t(sizeof(EbBlock)) * (L.n_prep + L.n_kblk + L.n_atomblk + L.n_rowblk);
-  if (!frames) return true;
-  EbBlock* b_prep = blocks;
-  EbBlock* b_k = b_prep + L.n_prep;
-  EbBlock* b_atom = b_k + L.n_kblk;
-  EbBlock* b_row = b_atom + L.n_atomblk;
-  int64_t work0 = 0;
-  for (int f = 0; f < F; ++f) {
-    const int64_t N = atom_ptr[f + 1] - atom_ptr[f], K = k_ptr[f + 1] - k_ptr[f];
-    const EsWork w = es_work_layout(N, K, cell, nullptr);
-    const int64_t n_k8 = (K + kEsKPerBlock - 1) / kEsKPerBlock;
-    EbFrame& r = frames[f];
-    memset(&r, 0, sizeof(r));
-    r.atom0 = atom_ptr[f], r.n_atoms = N, r.k0 = k_ptr[f], r.n_k = K;
-    r.rp0 = 2 * atom_ptr[f] + f;  // (2 N + 1 row pointers per frame)
-    r.ent0 = entry_ptr[f];
-    r.chunk = w.n_slices > 0 ? (K + w.n_slices - 1) / w.n_slices : 0;
-    r.geom = work0 + (w.geom - (double*)nullptr);
-    r.q_part = work0 + (w.q_part - (double*)nullptr);
-    r.e_part = work0 + (w.e_part - (double*)nullptr);
-    r.row_cell = work0 + (w.row_cell - (double*)nullptr);
-    r.k_cell = work0 + (w.k_cell - (double*)nullptr);
-    r.row_out = work0 + ((double*)w.row_out - (double*)nullptr);
-    r.slice_part = work0 + ((double*)w.slice_part - (double*)nullptr);
-    r.n_table_blocks = int32_t(w.n_table_blocks), r.n_atom_blocks = int32_t(w.n_atom_blocks), r.n_fin_blocks = int32_t(w.n_fin_blocks);
-    r.n_row_blocks = int32_t(w.n_row_blocks), r.n_k_blocks = int32_t(w.n_k_blocks), r.n_slices = int32_t(w.n_slices);
-    r.ns[0] = ns[3 * f], r.ns[1] = ns[3 * f + 1], r.ns[2] = ns[3 * f + 2];
-    for (int64_t b = 0; b < w.n_table_blocks + w.n_atom_blocks; ++b) *b_prep++ = EbBlock{f, int32_t(b)};
-    for (int64_t b = 0; b < n_k8; ++b) *b_k++ = EbBlock{f, int32_t(b)};
-    for (int64_t b = 0; b < N * w.n_slices; ++b) *b_atom++ = EbBlock{f, int32_t(b)};
-    for (int64_t b = 0; b < w.n_fin_blocks; ++b) *b_row++ = EbBlock{f, int32_t(b)};
-    work0 += w.total;
-  }
-  return true;
-}
+// the constants of es_work_layout: the table lays out a frame's work area as the single step does
+constexpr EbShape kEbEwaldShape = {kEsGeom, 1, 4, kEsMinSlice};
 
 // ---- the kernels: the bodies of ewald_step_bodies.h with the sizes, the slices and the local block index of the block's frame ----
 // blk and everything read from the frame's record is uniform per block.  Partner atoms, row pointers and k-vectors are local to
@@ -124,7 +48,7 @@ __global__ __launch_bounds__(kEsBlock) void ewald_batch_prep_kernel(KPot kp, con
   const EbFrame& fr = frames[blk.frame];
   es_prep_body<T>(kp, fr.n_atoms, fr.n_k, fr.n_table_blocks, blk.local, cells + 9 * int64_t(blk.frame), freq_all + 3 * fr.k0,
                   mult_all + fr.k0, fr.ns[0], fr.ns[1], fr.ns[2], lr_wavelength, pos_all + 3 * fr.atom0, q_all + fr.atom0,
-                  kvec_all + 3 * fr.k0, G_all + fr.k0, dG_all ? dG_all + fr.k0 : nullptr, rec_all + fr.atom0, work + fr.q_part,
+                  kvec_all + 3 * fr.k0, G_all + fr.k0, dG_all ? dG_all + fr.k0 : nullptr, rec_all + fr.atom0, work + fr.atom_part,
                   work + fr.geom, status + blk.frame);
 }
 
@@ -188,7 +112,7 @@ __global__ __launch_bounds__(kEsBlock) void ewald_batch_finish_kernel(const EbFr
   const EbBlock blk = blocks[blockIdx.x];
   const EbFrame& fr = frames[blk.frame];
   es_finish_body<T>(fr.n_atoms, fr.n_slices, int64_t(blk.local), self_c, two_bg, work + fr.geom, rec_all + fr.atom0,
-                    (const T*)(work + fr.slice_part), (const T*)(work + fr.row_out), work + fr.q_part, fr.n_atom_blocks,
+                    (const T*)(work + fr.slice_part), (const T*)(work + fr.row_out), work + fr.atom_part, fr.n_atom_blocks,
                     forces_all + 3 * fr.atom0, grad_q_all + fr.atom0, work + fr.e_part);
 }
 
@@ -200,7 +124,7 @@ __global__ __launch_bounds__(kEsBlock) void ewald_batch_final_kernel(const EbFra
   const int64_t f = blockIdx.x;
   const EbFrame& fr = frames[f];
   es_final_body<T, CELL>(fr.n_fin_blocks, work + fr.e_part, energies + f, fr.n_row_blocks, work + fr.row_cell, fr.n_k_blocks,
-                         work + fr.k_cell, fr.n_atom_blocks, work + fr.q_part, bg, work + fr.geom, CELL ? grad_cells + 9 * f : nullptr);
+                         work + fr.k_cell, fr.n_atom_blocks, work + fr.atom_part, bg, work + fr.geom, CELL ? grad_cells + 9 * f : nullptr);
 }
 
 // ---- host --------------------------------------------------------------------------------------------------------------------
@@ -257,13 +181,13 @@ extern "C" {
 
 int64_t mipme_ewald_batch_work(int n_frames, const int64_t* atom_ptr, const int64_t* k_ptr, int cell_gradient) {
   EbLayout L;
-  if (!eb_layout(n_frames, atom_ptr, k_ptr, nullptr, nullptr, cell_gradient != 0, L, nullptr, nullptr)) return 0;
+  if (!eb_layout(kEbEwaldShape, n_frames, atom_ptr, k_ptr, nullptr, nullptr, cell_gradient != 0, L, nullptr, nullptr)) return 0;
   return L.work_total;
 }
 
 int64_t mipme_ewald_batch_table_bytes(int n_frames, const int64_t* atom_ptr, const int64_t* k_ptr, int cell_gradient) {
   EbLayout L;
-  if (!eb_layout(n_frames, atom_ptr, k_ptr, nullptr, nullptr, cell_gradient != 0, L, nullptr, nullptr)) return 0;
+  if (!eb_layout(kEbEwaldShape, n_frames, atom_ptr, k_ptr, nullptr, nullptr, cell_gradient != 0, L, nullptr, nullptr)) return 0;
   return L.table_bytes;
 }
 
@@ -276,13 +200,13 @@ int mipme_ewald_batch_table_build(int n_frames, const int64_t* atom_ptr, const i
     MIPME_REQUIRE(ns[3 * f] >= 1 && ns[3 * f + 1] >= 1 && ns[3 * f + 2] >= 1, "%s: frame %d: ns must be >= 1, got (%d, %d, %d)", who, f,
                   int(ns[3 * f]), int(ns[3 * f + 1]), int(ns[3 * f + 2]));
   EbLayout L;
-  MIPME_REQUIRE(eb_layout(n_frames, atom_ptr, k_ptr, entry_ptr, ns, cell_gradient != 0, L, nullptr, nullptr),
+  MIPME_REQUIRE(eb_layout(kEbEwaldShape, n_frames, atom_ptr, k_ptr, entry_ptr, ns, cell_gradient != 0, L, nullptr, nullptr),
                 "%s: sizes the batch does not serve (each frame 1..2^22 atoms, n_k >= 0, at least one entry word; the sums of the atoms, "
                 "k-vectors and entries below 2^31; at most 2^24 - 1 workgroups per launch)", who);
   MIPME_REQUIRE(host_table_bytes == L.table_bytes, "%s: host_table_bytes is %lld, mipme_ewald_batch_table_bytes says %lld", who,
                 (long long)host_table_bytes, (long long)L.table_bytes);
   EbFrame* frames = (EbFrame*)host_table;
-  eb_layout(n_frames, atom_ptr, k_ptr, entry_ptr, ns, cell_gradient != 0, L, frames, (EbBlock*)(frames + n_frames));
+  eb_layout(kEbEwaldShape, n_frames, atom_ptr, k_ptr, entry_ptr, ns, cell_gradient != 0, L, frames, (EbBlock*)(frames + n_frames));
   return MIPME_OK;
 }
 
@@ -301,7 +225,7 @@ int mipme_ewald_batch(const mipme_ewald_batch_args_t* in) {
   MIPME_REQUIRE(a.atom_ptr && a.k_ptr && a.entry_ptr && a.device_table, "%s: NULL required buffer (atom_ptr, k_ptr, entry_ptr, device_table)",
                 who);
   EbLayout L;
-  MIPME_REQUIRE(eb_layout(a.n_frames, a.atom_ptr, a.k_ptr, a.entry_ptr, nullptr, a.cell_gradient != 0, L, nullptr, nullptr),
+  MIPME_REQUIRE(eb_layout(kEbEwaldShape, a.n_frames, a.atom_ptr, a.k_ptr, a.entry_ptr, nullptr, a.cell_gradient != 0, L, nullptr, nullptr),
                 "%s: sizes the batch does not serve (each frame 1..2^22 atoms, n_k >= 0, at least one entry word; the sums of the atoms, "
                 "k-vectors and entries below 2^31; at most 2^24 - 1 workgroups per launch)", who);
   MIPME_REQUIRE(!a.cell_gradient || a.grad_cells, "%s: cell_gradient needs grad_cells", who);

@@ -1518,7 +1518,84 @@ class GraphedEwaldStep(_ExplicitListStep):
         return out
 
 
-class GraphedEwaldBatch:
+class _FrameTableBatch:
+    """What the batches of explicit-list steps share (:class:`GraphedEwaldBatch`, :class:`GraphedDipoleBatch`): packing F lists
+    into concatenated row pointers and 4-byte entries, the frame table, the capture, and the copies of a call.  A subclass names
+    itself (``_who``) and the two table functions of its entry point, keeps the per-atom values beside the positions (charges or
+    dipoles) in ``self._values`` and supplies ``_launch``."""
+
+    MAX_FRAMES = 1 << 20
+    _who = _table_bytes = _table_build = None
+
+    def _pack(self, lists):
+        """Validate and pack F ``(neighbor_indices, neighbor_shifts)`` into the concatenated row pointers and 4-byte entries and
+        build the frame table for them.  Nothing of the object changes: what is returned goes to :meth:`_install`."""
+        who = self._who
+        lists = [tuple(ls) for ls in lists]
+        if len(lists) != self.n_frames:
+            raise ValueError(f"{who}: {self.n_frames} lists wanted, one (neighbor_indices, neighbor_shifts) per frame, got {len(lists)}")
+        for f, ls in enumerate(lists):
+            if len(ls) != 2:
+                raise ValueError(f"{who}: frame {f}: a list is (neighbor_indices, neighbor_shifts), got {len(ls)} items")
+            _check_explicit_list(who, *ls, frame=f)
+            for t, name in zip(ls, ("neighbor_indices", "neighbor_shifts")):
+                _lib.require_device(t, f"{name} of frame {f}")
+        rows, ents, keep = [], [], []
+        for f, (idx, shifts) in enumerate(lists):
+            sh = shifts.to(self.dtype).contiguous()
+            topo = ops.get_topology(idx, self.atom_ptr[f + 1] - self.atom_ptr[f])
+            ent32 = topo.compact_entries(sh, shifts)
+            if ent32 is None:
+                raise ValueError(f"{who}: frame {f}: the cell shifts must be integers in [-3, 3] (the 4-byte pair entries of the row "
+                                 "kernel) and the frame at most 2^22 atoms")
+            rows.append(topo.row_ptr)
+            ents.append(ent32)
+            keep.append(topo)
+        entry_ptr = np.concatenate([[0], np.cumsum([e.shape[0] for e in ents])]).astype(np.int64)
+        if int(entry_ptr[-1]) >= (1 << 31):
+            raise ValueError(f"{who}: the lists hold {int(entry_ptr[-1])} entry words, the frame table 2^31 - 1 at most")
+        lib, F, cg = self._lib, self.n_frames, int(self.cell_gradient)
+        n_bytes = int(getattr(lib, self._table_bytes)(F, self._atom_ptr.ctypes.data, self._k_ptr.ctypes.data, cg))
+        host = np.zeros(n_bytes, dtype=np.uint8)
+        _lib.check(getattr(lib, self._table_build)(F, self._atom_ptr.ctypes.data, self._k_ptr.ctypes.data, entry_ptr.ctypes.data,
+                                                   self._ns.ctypes.data, cg, host.ctypes.data, n_bytes))
+        with torch.no_grad():
+            row_ptr = torch.cat(rows).to(torch.int32).contiguous()
+            ent32 = torch.cat(ents).contiguous()
+        table = torch.from_numpy(host).to(self.device)  # one upload per capture
+        return [ls[0] for ls in lists], row_ptr, ent32, entry_ptr, table
+
+    def _install(self, packed):
+        self.pairs, self._row_ptr, self._ent32, self._entry_ptr, self._table = packed
+        self.graph = _capture_graph(self.device, self._warm_up, self._launch)
+
+    def _warm_up(self):
+        for _ in range(self._warmup):
+            self._launch()
+
+    def _load(self, positions=None, values=None, cells=None):
+        """Each input given, a flat tensor or a list of F per-frame tensors, into the object's buffer: one copy each."""
+        with torch.no_grad():
+            for buf, new in ((self.pos, positions), (self._values, values), (self.cells.view(-1, 3), cells)):
+                if new is None:
+                    continue
+                if isinstance(new, (list, tuple)):
+                    if len(new) != self.n_frames:
+                        raise ValueError(f"{self._who}: a list of {self.n_frames} per-frame tensors wanted, got {len(new)}")
+                    if sum(int(t.shape[0]) for t in new) != buf.shape[0]:
+                        raise ValueError(f"{self._who}: the per-frame tensors hold {sum(int(t.shape[0]) for t in new)} rows, the "
+                                         f"buffer {buf.shape[0]}")
+                    torch.cat([t.detach() for t in new], out=buf)
+                else:
+                    buf.copy_(new.detach().reshape(buf.shape))
+
+    def _recapture(self, lists, positions, values, cells):
+        packed = self._pack(lists)
+        self._load(positions, values, cells)
+        self._install(packed)
+
+
+class GraphedEwaldBatch(_FrameTableBatch):
     """``energies, forces, dE_dq = batch(positions, charges, cells)`` for MANY small systems and one
     :class:`~torchpme_amd.EwaldCalculator`, replayed from one HIP graph: the data-set form of :class:`GraphedEwaldStep` --
     hundreds to thousands of structures of 10 to 500 atoms, each with its own cell, its own atom count and its own k grid, whose
@@ -1557,7 +1634,9 @@ class GraphedEwaldBatch:
     :param warmup: eager runs before the capture
     """
 
-    MAX_FRAMES = 1 << 20
+    _who = "GraphedEwaldBatch"
+    _table_bytes, _table_build = "mipme_ewald_batch_table_bytes", "mipme_ewald_batch_table_build"
+    _values = property(lambda self: self.q)
 
     def __init__(self, calculator, frames, cell_gradient: bool = False, warmup: int = 3):
         who = "GraphedEwaldBatch"
@@ -1630,52 +1709,6 @@ class GraphedEwaldBatch:
         self._warmup = max(1, int(warmup))
         self._install(self._pack([(fr[3], fr[4]) for fr in frames]))
 
-    def _pack(self, lists):
-        """Validate and pack F ``(neighbor_indices, neighbor_shifts)`` into the concatenated row pointers and 4-byte entries and
-        build the frame table for them.  Nothing of the object changes: what is returned goes to :meth:`_install`."""
-        who = "GraphedEwaldBatch"
-        lists = [tuple(ls) for ls in lists]
-        if len(lists) != self.n_frames:
-            raise ValueError(f"{who}: {self.n_frames} lists wanted, one (neighbor_indices, neighbor_shifts) per frame, got {len(lists)}")
-        for f, ls in enumerate(lists):
-            if len(ls) != 2:
-                raise ValueError(f"{who}: frame {f}: a list is (neighbor_indices, neighbor_shifts), got {len(ls)} items")
-            _check_explicit_list(who, *ls, frame=f)
-            for t, name in zip(ls, ("neighbor_indices", "neighbor_shifts")):
-                _lib.require_device(t, f"{name} of frame {f}")
-        rows, ents, keep = [], [], []
-        for f, (idx, shifts) in enumerate(lists):
-            sh = shifts.to(self.dtype).contiguous()
-            topo = ops.get_topology(idx, self.atom_ptr[f + 1] - self.atom_ptr[f])
-            ent32 = topo.compact_entries(sh, shifts)
-            if ent32 is None:
-                raise ValueError(f"{who}: frame {f}: the cell shifts must be integers in [-3, 3] (the 4-byte pair entries of the row "
-                                 "kernel) and the frame at most 2^22 atoms")
-            rows.append(topo.row_ptr)
-            ents.append(ent32)
-            keep.append(topo)
-        entry_ptr = np.concatenate([[0], np.cumsum([e.shape[0] for e in ents])]).astype(np.int64)
-        if int(entry_ptr[-1]) >= (1 << 31):
-            raise ValueError(f"{who}: the lists hold {int(entry_ptr[-1])} entry words, the frame table 2^31 - 1 at most")
-        lib, F, cg = self._lib, self.n_frames, int(self.cell_gradient)
-        n_bytes = int(lib.mipme_ewald_batch_table_bytes(F, self._atom_ptr.ctypes.data, self._k_ptr.ctypes.data, cg))
-        host = np.zeros(n_bytes, dtype=np.uint8)
-        _lib.check(lib.mipme_ewald_batch_table_build(F, self._atom_ptr.ctypes.data, self._k_ptr.ctypes.data, entry_ptr.ctypes.data,
-                                                     self._ns.ctypes.data, cg, host.ctypes.data, n_bytes))
-        with torch.no_grad():
-            row_ptr = torch.cat(rows).to(torch.int32).contiguous()
-            ent32 = torch.cat(ents).contiguous()
-        table = torch.from_numpy(host).to(self.device)  # one upload per capture
-        return [ls[0] for ls in lists], row_ptr, ent32, entry_ptr, table
-
-    def _install(self, packed):
-        self.pairs, self._row_ptr, self._ent32, self._entry_ptr, self._table = packed
-        self.graph = _capture_graph(self.device, self._warm_up, self._launch)
-
-    def _warm_up(self):
-        for _ in range(self._warmup):
-            self._launch()
-
     def _launch(self):
         with _lib.on_device(self.device):
             a = _lib.EwaldBatchArgs(
@@ -1691,22 +1724,6 @@ class GraphedEwaldBatch:
                 work=self._work.data_ptr())
             _lib.check(self._lib.mipme_ewald_batch(C.byref(a)))
 
-    def _load(self, positions=None, charges=None, cells=None):
-        """Each input given, a flat tensor or a list of F per-frame tensors, into the object's buffer: one copy each."""
-        with torch.no_grad():
-            for buf, new in ((self.pos, positions), (self.q, charges), (self.cells.view(-1, 3), cells)):
-                if new is None:
-                    continue
-                if isinstance(new, (list, tuple)):
-                    if len(new) != self.n_frames:
-                        raise ValueError(f"GraphedEwaldBatch: a list of {self.n_frames} per-frame tensors wanted, got {len(new)}")
-                    if sum(int(t.shape[0]) for t in new) != buf.shape[0]:
-                        raise ValueError(f"GraphedEwaldBatch: the per-frame tensors hold {sum(int(t.shape[0]) for t in new)} rows, the "
-                                         f"buffer {buf.shape[0]}")
-                    torch.cat([t.detach() for t in new], out=buf)
-                else:
-                    buf.copy_(new.detach().reshape(buf.shape))
-
     def kgrid_matches(self, cells) -> list:
         """Per frame, whether the eager calculator would sum the frame's k grid for its cell in ``cells`` ((F, 3, 3) or a list):
         bit 0 of :attr:`status` clear, decided on the host."""
@@ -1718,9 +1735,7 @@ class GraphedEwaldBatch:
         """New neighbour lists, a sequence of F ``(neighbor_indices, neighbor_shifts)``: pack them, build the frame table again
         and capture the step again; the k grids and every buffer are kept.  Every list is validated and packed before anything of
         the object changes: a refused call leaves the object replaying what it replayed."""
-        packed = self._pack(lists)
-        self._load(positions, charges, cells)
-        self._install(packed)
+        self._recapture(lists, positions, charges, cells)
 
     def __call__(self, positions=None, charges=None, cells=None):
         """``energies, forces, dE_dq`` (+ ``dE_dcell`` with ``cell_gradient``) of the current -- or the given -- positions, charges
@@ -1728,6 +1743,203 @@ class GraphedEwaldBatch:
         self._load(positions, charges, cells)
         self.graph.replay()
         out = (self.energies, self.forces, self.charge_grads)
+        if self.cell_gradient:
+            out += (self.cell_grads,)
+        return out
+
+
+class GraphedDipoleBatch(_FrameTableBatch):
+    """``energies, forces, dE_dmu = batch(positions, dipoles, cells)`` for MANY small systems of point dipoles and one
+    :class:`~torchpme_amd.CalculatorDipole`, replayed from one HIP graph: the data-set form of
+    ``GraphedDipoleStep(follow_cell=True)``, as :class:`GraphedEwaldBatch` is the data-set form of :class:`GraphedEwaldStep` --
+    hundreds to thousands of polarisable or dipolar structures of 10 to 500 atoms, each with its own cell, its own atom count
+    and its own k grid, whose energies, forces, fields (``-dE/dmu``) and stress labels are wanted together.  A
+    :class:`GraphedDipoleStep` replay at these sizes is six or seven launches of a few dozen workgroups: latency, not work.  The
+    batch runs the same seven launches ONCE for all frames (``mipme_dipole_batch``, csrc/dipole_batch.hip; a table maps every
+    workgroup to its frame, no workgroup straddles two).
+
+    For frame f, ``energies[f]``, ``forces[f]``, ``dE_dmu[f]`` and -- with ``cell_gradient`` -- ``dE_dcell[f]`` mean word for word
+    what ``E``, ``F``, ``dE_dmu`` and ``dE_dcell`` of a ``GraphedDipoleStep(follow_cell=True)`` of that frame mean: total
+    derivatives, the cell gradient at fixed Cartesian positions.  ``energies`` is (F,); ``forces`` and ``dE_dmu`` are lists of
+    per-frame views into one flat buffer each, (sum N, 3), also exposed as :attr:`forces_flat` and :attr:`dipole_grads_flat`
+    (the list of views as :attr:`dipole_grads`); ``dE_dcell`` is :attr:`cell_grads`, one (F, 3, 3) tensor.  All outputs are
+    buffers of the object, overwritten by every call.
+
+    A call copies whichever of ``positions``, ``dipoles`` and ``cells`` are given into the object's buffers -- each either one
+    flat tensor in frame order or a list of F per-frame tensors, which goes in through ONE ``torch.cat(..., out=buffer)``
+    (:attr:`cells` is the (F, 3, 3) input buffer) -- and replays one graph: no host reads, nothing re-captured, and nothing
+    launched depends on any cell having the values it had at construction.  Every sum has a fixed order (no floating-point
+    atomics), and a frame is computed from its own inputs alone: the bits it gets do not depend on its index, on F or on the
+    other frames of the batch.
+
+    The k grid of every frame is frozen at construction, as in the single step: :attr:`ns` ``[f]``, :attr:`n_k` ``[f]`` (one of
+    every pair +-k).  :attr:`status` is a device ``int32`` (F,) tensor every replay writes, with the single step's two bits per
+    frame -- bit 0: the eager call would use another k grid for this cell; bit 1: ``det(cell)`` is zero or not finite (that
+    frame's energy and cell gradient are NaN, no other frame is touched) -- and :meth:`kgrid_matches` is the comparison of bit 0
+    on the host.  :attr:`atom_ptr` holds the F + 1 host offsets of the frames in the flat buffers.  A direct potential (no
+    smearing) sums no grid: ``lr_wavelength == 0.0``, every ``ns[f] == (1, 1, 1)`` and ``n_k[f] == 0``, bit 0 is never set.
+    Frames with ``n_k == 0``, frames of one atom and frames with an empty list are served, mixed with others or alone.
+
+    Not served: ``neighbors=`` streams, frames with different potentials, a double backward (the outputs are plain buffers, not
+    part of an autograd graph).
+
+    :param calculator: one :class:`CalculatorDipole` for all frames, with any :class:`PotentialDipole` the eager call accepts
+        (direct or range separated, with or without exclusion radius, ``epsilon``, ``prefactor``); half or full lists from
+        ``calculator.full_neighbor_list``
+    :param frames: sequence of ``(dipoles (N_f, 3), cell (3, 3), positions (N_f, 3), neighbor_indices (P_f, 2), neighbor_shifts
+        (P_f, 3))``, one dtype (float32 or float64) and one device throughout; integer cell shifts in [-3, 3]
+    :param cell_gradient: also return ``dE/dcell`` of every frame
+    :param warmup: eager runs before the capture
+    """
+
+    _who = "GraphedDipoleBatch"
+    _table_bytes, _table_build = "mipme_dipole_batch_table_bytes", "mipme_dipole_batch_table_build"
+    _values = property(lambda self: self.mu)
+
+    @staticmethod
+    def _check_system(who, f, dipoles, cell, positions, first):
+        """Shapes, dtype and atom count of frame ``f``: the refusals of :class:`GraphedDipoleStep` with the frame's index."""
+        pre = f"{who}: frame {f}: "
+        if dipoles.dim() != 2 or dipoles.shape[1] != 3:
+            raise ValueError(f"{pre}`dipoles` must be a tensor with shape [n_atoms, 3], got tensor with shape {list(dipoles.shape)}")
+        if positions.dim() != 2 or positions.shape[1] != 3 or positions.shape[0] != dipoles.shape[0]:
+            raise ValueError(f"{pre}`positions` must be a tensor with shape [n_atoms, 3] with n_atoms = {dipoles.shape[0]} (the "
+                             f"dipoles), got tensor with shape {list(positions.shape)}")
+        if tuple(cell.shape) != (3, 3):
+            raise ValueError(f"{pre}`cell` must be a tensor with shape [3, 3], got tensor with shape {list(cell.shape)}")
+        shared = positions.dtype == dipoles.dtype == cell.dtype == first.dtype
+        if not shared or positions.dtype not in (torch.float32, torch.float64):
+            raise ValueError(f"{pre}`positions`, `dipoles` and `cell` of all frames must share one dtype, float32 or float64, got "
+                             f"{positions.dtype}, {dipoles.dtype} and {cell.dtype} (frame 0: {first.dtype})")
+        if positions.shape[0] < 1 or positions.shape[0] > (1 << 22):
+            raise ValueError(f"{pre}a frame holds 1 to 2^22 atoms (the 4-byte pair entries of the row kernel), got "
+                             f"{positions.shape[0]}")
+
+    def __init__(self, calculator, frames, cell_gradient: bool = False, warmup: int = 3):
+        from .dipoles import CalculatorDipole
+
+        who = self._who
+        if not isinstance(calculator, CalculatorDipole):
+            raise TypeError(f"{who} serves a CalculatorDipole, got a {type(calculator).__name__}: use GraphedEwaldBatch or "
+                            "GraphedFrameBatch for charges")
+        frames = [tuple(fr) for fr in frames]
+        F = self.n_frames = len(frames)
+        if F == 0:
+            raise ValueError(f"{who}: `frames` is empty")
+        if F > self.MAX_FRAMES:
+            raise ValueError(f"{who} handles at most 2^20 frames, got {F}")
+        pot = calculator.potential
+        sm, _, eps, pref = pot._host_params()
+        self.lr_wavelength = float(calculator.lr_wavelength) if sm is not None else 0.0
+        first = frames[0][2] if len(frames[0]) == 5 else None
+        grids = []
+        for f, fr in enumerate(frames):
+            if len(fr) != 5:
+                raise ValueError(f"{who}: frame {f} must be (dipoles, cell, positions, neighbor_indices, neighbor_shifts), got "
+                                 f"{len(fr)} items")
+            dipoles, cell, positions, idx, shifts = fr
+            self._check_system(who, f, dipoles, cell, positions, first)
+            _check_explicit_list(who, idx, shifts, frame=f)
+            for t in (dipoles, cell, idx, shifts, positions):
+                if t.device != first.device:
+                    raise ValueError(f"{who}: frame {f}: all tensors of all frames must be on one device, got {t.device} and "
+                                     f"{first.device}")
+            det = float(np.linalg.det(cell.detach().to("cpu", torch.float64).numpy()))
+            if det == 0.0 or not np.isfinite(det):
+                raise ValueError(f"{who}: frame {f}: provided `cell` has a determinant of {det}, i.e. it is not a valid unit cell")
+            if sm is None:  # (a direct potential: no grid to compare with)
+                grids.append(((1, 1, 1), np.zeros((0, 3), dtype=np.int32), np.zeros(0, dtype=np.int32)))
+                continue
+            try:
+                grids.append(_ewald_kgrid(cell, self.lr_wavelength))
+            except ValueError as e:
+                raise ValueError(f"{who}: frame {f}: {e}") from None
+        for f, fr in enumerate(frames):
+            for t, name in zip(fr, ("dipoles", "cell", "positions", "neighbor_indices", "neighbor_shifts")):
+                _lib.require_device(t, f"{name} of frame {f}")
+        self.calc = calculator
+        self.cell_gradient = bool(cell_gradient)
+        self.full = bool(calculator.full_neighbor_list)
+        lib = self._lib = _lib.load()
+        device, dtype = first.device, first.dtype
+        self.device, self.dtype, self._dt = device, dtype, _lib.dtype_code(dtype)
+        self._desc = pot._descriptor()
+        self._self_term, self._background = 0.0, 0.0
+        if sm is not None:
+            alpha = 0.5 / sm**2
+            self._self_term = pref * 4 * math.pi / 3 * (alpha / math.pi) ** 1.5
+            self._background = pref * 4 * math.pi / (2 * eps + 1) if eps != 0.0 else 0.0
+        counts = [fr[2].shape[0] for fr in frames]
+        self._atom_ptr = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+        self.atom_ptr = [int(v) for v in self._atom_ptr]
+        self.ns, f_all, m_all = (list(x) for x in zip(*grids))
+        self.n_k = [int(len(m)) for m in m_all]
+        self._k_ptr = np.concatenate([[0], np.cumsum(self.n_k)]).astype(np.int64)
+        self._ns = np.ascontiguousarray(np.asarray(self.ns, dtype=np.int32).reshape(F, 3))
+        n_work = int(lib.mipme_dipole_batch_work(F, self._atom_ptr.ctypes.data, self._k_ptr.ctypes.data, int(self.cell_gradient)))
+        if n_work == 0:
+            raise ValueError(f"{who}: the batch is beyond the limits of the frame table: the sums of the atoms ({self.atom_ptr[-1]}) "
+                             f"and of the k-vectors ({int(self._k_ptr[-1])}) must stay below 2^31 and every launch below 2^24 "
+                             "workgroups (the atom launch has sum_f N_f x slices_f)")
+        SN, SK = self.atom_ptr[-1], int(self._k_ptr[-1])
+        new = lambda *shape, dt=dtype: torch.empty(shape, dtype=dt, device=device)  # noqa: E731
+        self._freq = self._mult = self._kvec = self._G = self._Sc = self._Ss = self._dG = None
+        if SK > 0:
+            self._freq = torch.tensor(np.concatenate(f_all), device=device)
+            self._mult = torch.tensor(np.concatenate(m_all), device=device)
+            self._kvec, self._G, self._Sc, self._Ss = new(SK, 3), new(SK), new(SK), new(SK)
+            self._dG = new(SK) if self.cell_gradient else None
+        with torch.no_grad():
+            self.pos = torch.cat([fr[2].detach() for fr in frames]).contiguous()
+            self.mu = torch.cat([fr[0].detach() for fr in frames]).contiguous()
+            self.cells = torch.stack([fr[1].detach() for fr in frames]).contiguous()
+        self._rec = new(2 * SN, 4)
+        self.energies, self.forces_flat, self.dipole_grads_flat = new(F), new(SN, 3), new(SN, 3)
+        self.cell_grads = new(F, 3, 3) if self.cell_gradient else None
+        self.status = torch.zeros(F, dtype=torch.int32, device=device)
+        self._work = new(max(1, n_work), dt=torch.float64)
+        cut = lambda t: [t[a:b] for a, b in zip(self.atom_ptr[:-1], self.atom_ptr[1:])]  # noqa: E731
+        self.forces, self.dipole_grads = cut(self.forces_flat), cut(self.dipole_grads_flat)
+        self._warmup = max(1, int(warmup))
+        self._install(self._pack([(fr[3], fr[4]) for fr in frames]))
+
+    def _launch(self):
+        with _lib.on_device(self.device):
+            a = _lib.DipoleBatchArgs(
+                stream=_lib.current_stream(self.device), dtype=self._dt, full_list=int(self.full), pot=C.pointer(self._desc),
+                self_term=self._self_term, background=self._background, n_frames=self.n_frames,
+                cell_gradient=int(self.cell_gradient), lr_wavelength=self.lr_wavelength, atom_ptr=self._atom_ptr.ctypes.data,
+                k_ptr=self._k_ptr.ctypes.data, entry_ptr=self._entry_ptr.ctypes.data, device_table=self._table.data_ptr(),
+                positions=self.pos.data_ptr(), dipoles=self.mu.data_ptr(), cells=self.cells.data_ptr(),
+                frequencies=_lib.ptr(self._freq), multiplicities=_lib.ptr(self._mult), row_ptr=self._row_ptr.data_ptr(),
+                entries=self._ent32.data_ptr(), shift_format=2, records=self._rec.data_ptr(), kvectors=_lib.ptr(self._kvec),
+                G=_lib.ptr(self._G), dG=_lib.ptr(self._dG), s_cos=_lib.ptr(self._Sc), s_sin=_lib.ptr(self._Ss),
+                energies=self.energies.data_ptr(), forces=self.forces_flat.data_ptr(),
+                grad_dipoles=self.dipole_grads_flat.data_ptr(), grad_cells=_lib.ptr(self.cell_grads),
+                status=self.status.data_ptr(), work=self._work.data_ptr())
+            _lib.check(self._lib.mipme_dipole_batch(C.byref(a)))
+
+    def kgrid_matches(self, cells) -> list:
+        """Per frame, whether the eager calculator would sum the frame's k grid for its cell in ``cells`` ((F, 3, 3) or a list):
+        bit 0 of :attr:`status` clear, decided on the host.  A direct potential sums no grid: all ``True``."""
+        if len(cells) != self.n_frames:
+            raise ValueError(f"GraphedDipoleBatch: {self.n_frames} cells wanted, got {len(cells)}")
+        if self.lr_wavelength <= 0.0:
+            return [True] * self.n_frames
+        return [GraphedEwaldStep._ns_of(c, self.lr_wavelength) == ns for c, ns in zip(cells, self.ns)]
+
+    def recapture(self, lists, positions=None, dipoles=None, cells=None) -> None:
+        """New neighbour lists, a sequence of F ``(neighbor_indices, neighbor_shifts)``: pack them, build the frame table again
+        and capture the step again; the k grids and every buffer are kept.  Every list is validated and packed before anything of
+        the object changes: a refused call leaves the object replaying what it replayed."""
+        self._recapture(lists, positions, dipoles, cells)
+
+    def __call__(self, positions=None, dipoles=None, cells=None):
+        """``energies, forces, dE_dmu`` (+ ``dE_dcell`` with ``cell_gradient``) of the current -- or the given -- positions,
+        dipoles and cells of all frames: up to three copies and one graph replay."""
+        self._load(positions, dipoles, cells)
+        self.graph.replay()
+        out = (self.energies, self.forces, self.dipole_grads)
         if self.cell_gradient:
             out += (self.cell_grads,)
         return out
