@@ -1246,6 +1246,136 @@ int64_t mipme_ewald_batch_table_bytes(int n_frames, const int64_t* atom_ptr, con
 int mipme_ewald_batch_table_build(int n_frames, const int64_t* atom_ptr, const int64_t* k_ptr, const int64_t* entry_ptr,
                                   const int32_t* ns, int cell_gradient, void* host_table, int64_t host_table_bytes);
 
+/* mipme_ewald_step for SEVERAL charge channels, 2 <= C = n_channels <= 8, in one step: GraphedEwaldStep(n_channels=C), graphed.py;
+ * csrc/ewald_channels_step.hip, the bodies in csrc/ewald_channels_bodies.h.  The channels are independent systems of charges on the
+ * same atoms, cell, k grid and list; what does not depend on the channel -- the phase of every (atom, k), its sine and cosine, the
+ * shift, distance and pair function of every entry -- is computed once for all of them.  With V the (N, C) potential the eager
+ * calculator returns for (N, C) charges:
+ *   energy        = E = sum_a sum_c q_ac V_ac                   (one value of `dtype`; NaN when status bit 1 is set)
+ *   forces        = -dE/dpositions    (N,3)
+ *   grad_charges  = dE/dcharges       (N,C) row-major           (total, per channel: 2 V for a half list; V plus the transposed half
+ *                                                                for a full one)
+ *   grad_cell     = dE/dcell          (3,3) at fixed Cartesian positions, with cell_gradient
+ *   status        = as in mipme_ewald_step
+ * Formulas, with S^c the structure factor of channel c, Q_c = sum_a q_ac and everything else as above mipme_ewald_step_args_t:
+ *   dE/dq_ac = (1/V) sum_k G (c_a S_c^c + s_a S_s^c) - self q_ac - 2 bg Q_c / V + c sum_e q_oc v_SR(d_e)
+ *   F_a      = -(1/V) sum_k G k (c_a A_s - s_a A_c) + c sum_e (sum_c q_ac q_oc) v_SR'(d_e)/d_e u_e,
+ *              A_s(a, k) = sum_c q_ac S_s^c, A_c likewise;          E = 1/2 sum_a sum_c q_ac dE/dq_ac
+ *   dE/dcell = sum_p S_p (x) dE/du_p - cell^-T W / V - (E_k + E_bg) cell^-T,   W = sum_k gk (x) k,
+ *              gk = dG |S|^2 k + G sum_j r_j sum_c q_jc (c_j S_s^c - s_j S_c^c),  |S|^2 = sum_c (S_c^c^2 + S_s^c^2),
+ *              E_k = (1/2V) sum_k G |S|^2,  E_bg = -bg sum_c Q_c^2 / V   (NOT (sum_c Q_c)^2: a channel sees its own background only)
+ * Layouts.  charges and grad_charges: (N, C) row-major, element (a, c) at a C + c; no alignment beyond that of one real is assumed.
+ * s_cos, s_sin: C n_k reals each, CHANNEL-MAJOR: S^c(k) at c n_k + k (the n_k values of a channel are contiguous: the atoms launch
+ * reads them with k across the lanes).  records: 4 N reals (16-byte aligned), (x, y, z, 0): the charges are read from `charges`.
+ * work: float64[mipme_ewald_channels_step_work(n_atoms, n_k, n_channels, cell_gradient)] (0 for sizes or an n_channels not
+ * served): the layout of mipme_ewald_step with C partials of Q_c per atom block (block b, channel c at b C + c), C + 3 row results
+ * per atom (the C pair potentials, then the pair force) and C + 3 slice partials per (slice, atom) (the C sums phi_c, then the
+ * bracket).  kvectors, G, dG as in mipme_ewald_step.
+ * Launches: the seven of mipme_ewald_step with the same grids, conditions and order, a single chain on `stream` (capturable).  No
+ * atomics, no workgroup waits for another, every cross-block sum is float64 partials added in index order by a later launch.
+ * The kernels are compiled for the capacities 2, 4 and 8 channels; a C between them runs the next capacity, its spare channels
+ * never loaded, never stored and left out of every sum over the channels.
+ * MIPME_EINVAL before anything is launched: everything mipme_ewald_step refuses, and n_channels outside 2..8 (the message points
+ * to mipme_ewald_step for one channel).  Versioned like mipme_ewald_step_args_t: size and version first, fields only ever
+ * appended. */
+#define MIPME_EWALD_CHANNELS_STEP_VERSION 1
+#define MIPME_EWALD_MAX_CHANNELS 8
+typedef struct mipme_ewald_channels_step_args {
+  uint32_t size;
+  uint32_t version;
+  void* stream;
+  int32_t dtype;
+  int32_t full_list;
+  const mipme_potential_t* pot;
+  int64_t n_atoms;
+  int64_t n_k;
+  double lr_wavelength;
+  int32_t ns[3];
+  int32_t cell_gradient;
+  const void* positions;
+  const void* charges;
+  const void* cell;
+  const void* frequencies;
+  const void* multiplicities;
+  const void* row_ptr;
+  const void* entries;
+  int32_t shift_format;
+  int32_t n_channels;
+  void* records;
+  void* kvectors;
+  void* G;
+  void* dG;
+  void* s_cos;
+  void* s_sin;
+  void* energy;
+  void* forces;
+  void* grad_charges;
+  void* grad_cell;
+  void* status;
+  void* work;
+} mipme_ewald_channels_step_args_t;
+int mipme_ewald_channels_step(const mipme_ewald_channels_step_args_t* args);
+int64_t mipme_ewald_channels_step_work(int64_t n_atoms, int64_t n_k, int n_channels, int cell_gradient);
+
+/* mipme_ewald_batch for SEVERAL charge channels, 2 <= C = n_channels <= 8, the same C in every frame:
+ * GraphedEwaldBatch(n_channels=C), graphed.py; csrc/ewald_channels_batch.hip.  For frame f the outputs mean word for word what
+ * those of mipme_ewald_channels_step mean for that system alone, and the bits a frame gets depend on its own inputs only.
+ * Everything is as in mipme_ewald_batch but for the channels:
+ *   charges, grad_charges (sum N, C) row-major: the slice of frame f begins at element atom_ptr[f] C;
+ *   s_cos, s_sin C sum K reals each: the slice of frame f begins at k_ptr[f] C and is channel-major INSIDE the frame, S^c(k) of
+ *   frame f at k_ptr[f] C + c K_f + k;
+ *   records 4 sum N reals, (x, y, z, 0);
+ *   the frame table has the format and the sizes of mipme_ewald_batch's (152 bytes per frame, 8 per workgroup, the same workgroup
+ *   counts) with the work area of a frame that of mipme_ewald_channels_step: C partials per atom block, C + 3 results per atom
+ *   and per (slice, atom).  mipme_ewald_channels_batch_work = the sum over the frames of mipme_ewald_channels_step_work.
+ * The three size and table functions take n_channels and return 0 / MIPME_EINVAL outside 2..8.  Launches, limits and refusals:
+ * those of mipme_ewald_batch, and n_channels outside 2..8 (the message points to mipme_ewald_batch for one channel).  Versioned
+ * like mipme_ewald_step_args_t: size and version first, fields only ever appended. */
+#define MIPME_EWALD_CHANNELS_BATCH_VERSION 1
+typedef struct mipme_ewald_channels_batch_args {
+  uint32_t size;
+  uint32_t version;
+  void* stream;
+  int32_t dtype;
+  int32_t full_list;
+  const mipme_potential_t* pot;
+  int32_t n_frames;
+  int32_t cell_gradient;
+  double lr_wavelength;
+  const int64_t* atom_ptr;
+  const int64_t* k_ptr;
+  const int64_t* entry_ptr;
+  const void* device_table;
+  const void* positions;
+  const void* charges;
+  const void* cells;
+  const void* frequencies;
+  const void* multiplicities;
+  const void* row_ptr;
+  const void* entries;
+  int32_t shift_format;
+  int32_t n_channels;
+  void* records;
+  void* kvectors;
+  void* G;
+  void* dG;
+  void* s_cos;
+  void* s_sin;
+  void* energies;
+  void* forces;
+  void* grad_charges;
+  void* grad_cells;
+  void* status;
+  void* work;
+} mipme_ewald_channels_batch_args_t;
+int mipme_ewald_channels_batch(const mipme_ewald_channels_batch_args_t* args);
+int64_t mipme_ewald_channels_batch_work(int n_frames, const int64_t* atom_ptr, const int64_t* k_ptr, int n_channels, int cell_gradient);
+int64_t mipme_ewald_channels_batch_table_bytes(int n_frames, const int64_t* atom_ptr, const int64_t* k_ptr, int n_channels,
+                                               int cell_gradient);
+int mipme_ewald_channels_batch_table_build(int n_frames, const int64_t* atom_ptr, const int64_t* k_ptr, const int64_t* entry_ptr,
+                                           const int32_t* ns, int n_channels, int cell_gradient, void* host_table,
+                                           int64_t host_table_bytes);
+
 /* mipme_dipole_step with the CELL as an input of every call, the MD form of CalculatorDipole for constant-pressure runs:
  * GraphedDipoleStep(follow_cell=True), graphed.py; csrc/dipole_step.hip.  energy, forces, grad_dipoles and grad_cell mean word for
  * word what they mean in mipme_dipole_step_args_t, evaluated with the CURRENT contents of `cell` and summed over the k grid given

@@ -50,6 +50,9 @@ EXPORTS = (
     "mipme_ewald_batch", "mipme_ewald_batch_work", "mipme_ewald_batch_table_bytes", "mipme_ewald_batch_table_build",
     "mipme_dipole_cell_step", "mipme_dipole_cell_step_work",
     "mipme_dipole_batch", "mipme_dipole_batch_work", "mipme_dipole_batch_table_bytes", "mipme_dipole_batch_table_build",
+    "mipme_ewald_channels_step", "mipme_ewald_channels_step_work",
+    "mipme_ewald_channels_batch", "mipme_ewald_channels_batch_work", "mipme_ewald_channels_batch_table_bytes",
+    "mipme_ewald_channels_batch_table_build",
 )
 
 
@@ -459,6 +462,37 @@ class EwaldBatchArgs(_VersionedArgs):
         C.Structure.__init__(self, size=C.sizeof(type(self)), version=EWALD_BATCH_VERSION, **fields)
 
 
+EWALD_CHANNELS_STEP_VERSION = 1
+EWALD_CHANNELS_BATCH_VERSION = 1
+EWALD_MAX_CHANNELS = 8  # MIPME_EWALD_MAX_CHANNELS
+
+
+class EwaldChannelsStepArgs(_VersionedArgs):
+    """``mipme_ewald_channels_step_args_t`` (version ``MIPME_EWALD_CHANNELS_STEP_VERSION``): the fields of
+    :class:`EwaldStepArgs` with ``n_channels`` where that struct pads"""
+
+    _fields_ = [(name, tp) if name != "_pad" else ("n_channels", tp) for name, tp in EwaldStepArgs._fields_]
+
+    def __init__(self, **fields):
+        unknown = set(fields) - {name for name, _ in self._fields_}
+        if unknown:
+            raise TypeError(f"{type(self).__name__}: unknown field(s) {sorted(unknown)}")
+        C.Structure.__init__(self, size=C.sizeof(type(self)), version=EWALD_CHANNELS_STEP_VERSION, **fields)
+
+
+class EwaldChannelsBatchArgs(_VersionedArgs):
+    """``mipme_ewald_channels_batch_args_t`` (version ``MIPME_EWALD_CHANNELS_BATCH_VERSION``): the fields of
+    :class:`EwaldBatchArgs` with ``n_channels`` where that struct pads"""
+
+    _fields_ = [(name, tp) if name != "_pad" else ("n_channels", tp) for name, tp in EwaldBatchArgs._fields_]
+
+    def __init__(self, **fields):
+        unknown = set(fields) - {name for name, _ in self._fields_}
+        if unknown:
+            raise TypeError(f"{type(self).__name__}: unknown field(s) {sorted(unknown)}")
+        C.Structure.__init__(self, size=C.sizeof(type(self)), version=EWALD_CHANNELS_BATCH_VERSION, **fields)
+
+
 DIPOLE_BATCH_VERSION = 1
 
 
@@ -567,6 +601,9 @@ def _declare(lib):
         "mipme_ewald_step": [C.POINTER(EwaldStepArgs)],
         "mipme_ewald_batch": [C.POINTER(EwaldBatchArgs)],
         "mipme_ewald_batch_table_build": [ci, vp, vp, vp, vp, ci, vp, i64],
+        "mipme_ewald_channels_step": [C.POINTER(EwaldChannelsStepArgs)],
+        "mipme_ewald_channels_batch": [C.POINTER(EwaldChannelsBatchArgs)],
+        "mipme_ewald_channels_batch_table_build": [ci, vp, vp, vp, vp, ci, ci, vp, i64],
         "mipme_dipole_batch": [C.POINTER(DipoleBatchArgs)],
         "mipme_dipole_batch_table_build": [ci, vp, vp, vp, vp, ci, vp, i64],
         "mipme_dot_forward": [vp, ci, i64, vp, vp, vp, vp],
@@ -660,6 +697,12 @@ def _declare(lib):
     lib.mipme_ewald_batch_work.argtypes = [ci, vp, vp, ci]
     lib.mipme_ewald_batch_table_bytes.restype = i64
     lib.mipme_ewald_batch_table_bytes.argtypes = [ci, vp, vp, ci]
+    lib.mipme_ewald_channels_step_work.restype = i64
+    lib.mipme_ewald_channels_step_work.argtypes = [i64, i64, ci, ci]
+    lib.mipme_ewald_channels_batch_work.restype = i64
+    lib.mipme_ewald_channels_batch_work.argtypes = [ci, vp, vp, ci, ci]
+    lib.mipme_ewald_channels_batch_table_bytes.restype = i64
+    lib.mipme_ewald_channels_batch_table_bytes.argtypes = [ci, vp, vp, ci, ci]
     lib.mipme_dipole_batch_work.restype = i64
     lib.mipme_dipole_batch_work.argtypes = [ci, vp, vp, ci]
     lib.mipme_dipole_batch_table_bytes.restype = i64

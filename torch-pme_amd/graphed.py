@@ -1130,14 +1130,38 @@ def _check_ewald_calculator(who, calculator, instead):
                         f"{type(pot).__name__}; call the calculator eagerly")
 
 
-def _check_ewald_system(who, charges, cell, positions, frame=None, first=None):
+MAX_EWALD_CHANNELS = _lib.EWALD_MAX_CHANNELS
+
+
+def _check_n_channels(who, n_channels):
+    """``n_channels`` of an Ewald step: an ``int`` in 1..8."""
+    if isinstance(n_channels, bool) or not isinstance(n_channels, int) or not 1 <= n_channels <= MAX_EWALD_CHANNELS:
+        raise ValueError(f"{who}: `n_channels` must be an int in 1..{MAX_EWALD_CHANNELS} (the charge channels the step kernels keep "
+                         f"in registers), got {n_channels!r}")
+
+
+def _check_channel_charges(who, charges, n_atoms, n_channels, frame=None):
+    """``charges`` handed to a multi-channel object after construction: exactly ``(n_atoms, n_channels)`` -- ``copy_`` would
+    broadcast an (N, 1) tensor into every channel without a word."""
+    if tuple(charges.shape) != (n_atoms, n_channels):
+        pre = f"{who}: " if frame is None else f"{who}: frame {frame}: "
+        raise ValueError(f"{pre}`charges` must be a tensor with shape [n_atoms, n_channels] = [{n_atoms}, {n_channels}] "
+                         f"(n_channels = {n_channels}), got tensor with shape {list(charges.shape)}")
+
+
+def _check_ewald_system(who, charges, cell, positions, frame=None, first=None, n_channels=1):
     """Shapes, dtype and atom count of one system of an Ewald step.  In a batch, ``frame`` is its index and ``first`` the tensor
-    whose dtype all frames share."""
+    whose dtype all frames share.  ``n_channels``: the charge channels of the object (1: the single-channel rules, word for
+    word)."""
     batch = frame is not None
     pre = f"{who}: frame {frame}: " if batch else ""
-    if charges.dim() != 2 or charges.shape[1] != 1:
-        raise ValueError(f"{pre or who + ' handles '}a single charge channel, `charges` of shape [n_atoms, 1], got tensor with "
-                         f"shape {list(charges.shape)}")
+    if n_channels == 1:
+        if charges.dim() != 2 or charges.shape[1] != 1:
+            raise ValueError(f"{pre or who + ' handles '}a single charge channel, `charges` of shape [n_atoms, 1], got tensor with "
+                             f"shape {list(charges.shape)}")
+    elif charges.dim() != 2 or charges.shape[1] != n_channels:
+        raise ValueError(f"{pre or who + ': '}`charges` must be a tensor with shape [n_atoms, n_channels] = [n_atoms, {n_channels}] "
+                         f"(n_channels = {n_channels}), got tensor with shape {list(charges.shape)}")
     if positions.dim() != 2 or positions.shape[1] != 3 or positions.shape[0] != charges.shape[0]:
         raise ValueError(f"{pre}`positions` must be a tensor with shape [n_atoms, 3] with n_atoms = {charges.shape[0]} (the "
                          f"charges), got tensor with shape {list(positions.shape)}")
@@ -1432,13 +1456,21 @@ class GraphedEwaldStep(_ExplicitListStep):
     :param neighbor_indices, neighbor_shifts: an explicit list (P, 2) with integer cell shifts (P, 3) in [-3, 3]; at most 2^22 atoms
     :param cell_gradient: also return ``dE/dcell``
     :param warmup: eager runs before the capture
+    :param n_channels: the charge channels C, an ``int`` in 1..8 (:attr:`n_channels`).  With ``C >= 2`` ``charges`` is (N, C) --
+        latent or learned charges, several per atom, each channel an independent system of charges on the same atoms -- and the
+        object runs ``mipme_ewald_channels_step`` (csrc/ewald_channels_step.hip): with ``V`` the (N, C) potential of the eager
+        call, ``E = sum_a sum_c q_ac V_ac``, ``F`` and ``dE_dcell`` are those of this energy and ``dE_dq`` is (N, C), the total
+        derivative per channel.  The phase of every (atom, k) and the pair function of every list entry are computed once for
+        all channels, so one replay costs far less than C single-channel replays.  A ``charges=`` of a later call must be
+        exactly (N, C).  With the default 1 the object is the single-channel step, entry point and bits.
     """
 
     def __init__(self, calculator, charges, cell, positions, neighbor_indices, neighbor_shifts, cell_gradient: bool = False,
-                 warmup: int = 3):
+                 warmup: int = 3, n_channels: int = 1):
         who = "GraphedEwaldStep"
         _check_ewald_calculator(who, calculator, "GraphedEnergyForces")
-        _check_ewald_system(who, charges, cell, positions)
+        _check_n_channels(who, n_channels)
+        _check_ewald_system(who, charges, cell, positions, n_channels=n_channels)
         _check_explicit_list(who, neighbor_indices, neighbor_shifts)
         self.lr_wavelength = float(calculator.lr_wavelength)
         self.ns, freq, mult = _ewald_kgrid(cell, self.lr_wavelength)
@@ -1452,20 +1484,23 @@ class GraphedEwaldStep(_ExplicitListStep):
         device, dtype = positions.device, positions.dtype
         self.device, self.dtype, self._dt = device, dtype, _lib.dtype_code(dtype)
         N = self.n_atoms = positions.shape[0]
+        nc = self.n_channels = n_channels
         self._desc = calculator.potential._descriptor()
         new = lambda *shape, dt=dtype: torch.empty(shape, dtype=dt, device=device)  # noqa: E731
         self.cell = cell.detach().clone().contiguous()
         K = self.n_k = int(len(mult))
         self._freq, self._mult = torch.tensor(freq, device=device), torch.tensor(mult, device=device)
-        self._kvec, self._G, self._Sc, self._Ss = new(max(K, 1), 3), new(max(K, 1)), new(max(K, 1)), new(max(K, 1))
+        self._kvec, self._G, self._Sc, self._Ss = new(max(K, 1), 3), new(max(K, 1)), new(nc * max(K, 1)), new(nc * max(K, 1))
         self._dG = new(max(K, 1)) if self.cell_gradient else None
         self.pos = positions.detach().clone().contiguous()
         self.q = charges.detach().clone().contiguous()
         self._rec = new(N, 4)
-        self.energy, self.forces, self.charge_grad = new(), new(N, 3), new(N, 1)
+        self.energy, self.forces, self.charge_grad = new(), new(N, 3), new(N, nc)
         self.cell_grad = new(3, 3) if self.cell_gradient else None
         self.status = torch.zeros(1, dtype=torch.int32, device=device)
-        self._work = new(max(1, int(lib.mipme_ewald_step_work(N, K, int(self.cell_gradient)))), dt=torch.float64)
+        n_work = (lib.mipme_ewald_step_work(N, K, int(self.cell_gradient)) if nc == 1 else
+                  lib.mipme_ewald_channels_step_work(N, K, nc, int(self.cell_gradient)))
+        self._work = new(max(1, int(n_work)), dt=torch.float64)
         self._warmup = max(1, int(warmup))
         self._capture(neighbor_indices, neighbor_shifts)
 
@@ -1481,7 +1516,7 @@ class GraphedEwaldStep(_ExplicitListStep):
 
     def _launch(self):
         with _lib.on_device(self.device):
-            a = _lib.EwaldStepArgs(
+            fields = dict(
                 stream=_lib.current_stream(self.device), dtype=self._dt, full_list=int(self.full), pot=C.pointer(self._desc),
                 n_atoms=self.n_atoms, n_k=self.n_k, lr_wavelength=self.lr_wavelength, ns=(C.c_int32 * 3)(*self.ns),
                 cell_gradient=int(self.cell_gradient), positions=self.pos.data_ptr(), charges=self.q.data_ptr(),
@@ -1491,19 +1526,28 @@ class GraphedEwaldStep(_ExplicitListStep):
                 s_sin=self._Ss.data_ptr(), energy=self.energy.data_ptr(), forces=self.forces.data_ptr(),
                 grad_charges=self.charge_grad.data_ptr(), grad_cell=_lib.ptr(self.cell_grad), status=self.status.data_ptr(),
                 work=self._work.data_ptr())
-            _lib.check(self._lib.mipme_ewald_step(C.byref(a)))
+            if self.n_channels == 1:
+                a = _lib.EwaldStepArgs(**fields)
+                _lib.check(self._lib.mipme_ewald_step(C.byref(a)))
+            else:
+                a = _lib.EwaldChannelsStepArgs(n_channels=self.n_channels, **fields)
+                _lib.check(self._lib.mipme_ewald_channels_step(C.byref(a)))
 
     def recapture(self, neighbor_indices, neighbor_shifts, positions: torch.Tensor | None = None,
                   charges: torch.Tensor | None = None, cell: torch.Tensor | None = None) -> None:
         """New neighbour list: rebuild the pair topology and capture the step again; the k grid and every buffer are kept.  The
         list is validated before anything of the object changes."""
         _check_explicit_list("GraphedEwaldStep", neighbor_indices, neighbor_shifts)
+        if charges is not None and self.n_channels > 1:
+            _check_channel_charges("GraphedEwaldStep", charges, self.n_atoms, self.n_channels)
         self._capture(neighbor_indices, neighbor_shifts, [(self.pos, positions), (self.q, charges), (self.cell, cell)])
 
     def __call__(self, positions: torch.Tensor | None = None, charges: torch.Tensor | None = None,
                  cell: torch.Tensor | None = None):
         """``E, F, dE_dq`` (+ ``dE_dcell`` with ``cell_gradient``) of the current -- or the given -- positions, charges and cell:
         up to three small copies and one graph replay."""
+        if charges is not None and self.n_channels > 1:  # (before anything of the object changes)
+            _check_channel_charges("GraphedEwaldStep", charges, self.n_atoms, self.n_channels)
         with torch.no_grad():
             if positions is not None:
                 self.pos.copy_(positions)
@@ -1526,6 +1570,7 @@ class _FrameTableBatch:
 
     MAX_FRAMES = 1 << 20
     _who = _table_bytes = _table_build = None
+    _table_args = ()  # what the two table functions take between the host arrays and `cell_gradient`
 
     def _pack(self, lists):
         """Validate and pack F ``(neighbor_indices, neighbor_shifts)`` into the concatenated row pointers and 4-byte entries and
@@ -1555,10 +1600,10 @@ class _FrameTableBatch:
         if int(entry_ptr[-1]) >= (1 << 31):
             raise ValueError(f"{who}: the lists hold {int(entry_ptr[-1])} entry words, the frame table 2^31 - 1 at most")
         lib, F, cg = self._lib, self.n_frames, int(self.cell_gradient)
-        n_bytes = int(getattr(lib, self._table_bytes)(F, self._atom_ptr.ctypes.data, self._k_ptr.ctypes.data, cg))
+        n_bytes = int(getattr(lib, self._table_bytes)(F, self._atom_ptr.ctypes.data, self._k_ptr.ctypes.data, *self._table_args, cg))
         host = np.zeros(n_bytes, dtype=np.uint8)
         _lib.check(getattr(lib, self._table_build)(F, self._atom_ptr.ctypes.data, self._k_ptr.ctypes.data, entry_ptr.ctypes.data,
-                                                   self._ns.ctypes.data, cg, host.ctypes.data, n_bytes))
+                                                   self._ns.ctypes.data, *self._table_args, cg, host.ctypes.data, n_bytes))
         with torch.no_grad():
             row_ptr = torch.cat(rows).to(torch.int32).contiguous()
             ent32 = torch.cat(ents).contiguous()
@@ -1623,7 +1668,12 @@ class GraphedEwaldBatch(_FrameTableBatch):
     ``lr_wavelength`` along every axis have the grid (1, 1, 1) and ``n_k == 0``; they are served, as are frames with an empty list
     or a single atom.
 
-    Not served: the slab term, several charge channels, ``neighbors=`` streams, frames with different potentials.
+    Several charge channels: with ``n_channels=C``, 2 <= C <= 8, every frame's ``charges`` is (N_f, C) -- the training set of a
+    model with latent charges -- and the batch runs ``mipme_ewald_channels_batch`` (csrc/ewald_channels_batch.hip): per frame
+    what a :class:`GraphedEwaldStep` with ``n_channels=C`` computes, ``dE_dq`` (N_f, C) per frame, :attr:`charge_grads_flat`
+    (sum N, C).  ``charges=`` of a call is one flat (sum N, C) tensor or a list of F (N_f, C) tensors, exactly these shapes.
+
+    Not served: the slab term, ``neighbors=`` streams, frames with different potentials or channel counts.
 
     :param calculator: one :class:`EwaldCalculator` for all frames, under the rules of :class:`GraphedEwaldStep`: the potential
         exactly a :class:`CoulombPotential` or an :class:`InversePowerLawPotential` (exponent 1..6), with or without exclusion
@@ -1632,15 +1682,22 @@ class GraphedEwaldBatch(_FrameTableBatch):
         (P_f, 3))``, one dtype (float32 or float64) and one device throughout; integer cell shifts in [-3, 3]
     :param cell_gradient: also return ``dE/dcell`` of every frame
     :param warmup: eager runs before the capture
+    :param n_channels: the charge channels C of every frame, an ``int`` in 1..8 (:attr:`n_channels`); with the default 1 the
+        object is the single-channel batch, entry point and bits
     """
 
     _who = "GraphedEwaldBatch"
     _table_bytes, _table_build = "mipme_ewald_batch_table_bytes", "mipme_ewald_batch_table_build"
     _values = property(lambda self: self.q)
 
-    def __init__(self, calculator, frames, cell_gradient: bool = False, warmup: int = 3):
+    def __init__(self, calculator, frames, cell_gradient: bool = False, warmup: int = 3, n_channels: int = 1):
         who = "GraphedEwaldBatch"
         _check_ewald_calculator(who, calculator, "GraphedFrameBatch")
+        _check_n_channels(who, n_channels)
+        nc = self.n_channels = n_channels
+        if nc > 1:
+            self._table_bytes, self._table_build = "mipme_ewald_channels_batch_table_bytes", "mipme_ewald_channels_batch_table_build"
+            self._table_args = (nc,)
         frames = [tuple(fr) for fr in frames]
         F = self.n_frames = len(frames)
         if F == 0:
@@ -1655,7 +1712,7 @@ class GraphedEwaldBatch(_FrameTableBatch):
                 raise ValueError(f"{who}: frame {f} must be (charges, cell, positions, neighbor_indices, neighbor_shifts), got "
                                  f"{len(fr)} items")
             charges, cell, positions, idx, shifts = fr
-            _check_ewald_system(who, charges, cell, positions, frame=f, first=first)
+            _check_ewald_system(who, charges, cell, positions, frame=f, first=first, n_channels=nc)
             _check_explicit_list(who, idx, shifts, frame=f)
             for t in (charges, cell, idx, shifts, positions):
                 if t.device != first.device:
@@ -1682,7 +1739,11 @@ class GraphedEwaldBatch(_FrameTableBatch):
         self.n_k = [int(len(m)) for m in m_all]
         self._k_ptr = np.concatenate([[0], np.cumsum(self.n_k)]).astype(np.int64)
         self._ns = np.ascontiguousarray(np.asarray(self.ns, dtype=np.int32).reshape(F, 3))
-        n_work = int(lib.mipme_ewald_batch_work(F, self._atom_ptr.ctypes.data, self._k_ptr.ctypes.data, int(self.cell_gradient)))
+        if nc == 1:
+            n_work = int(lib.mipme_ewald_batch_work(F, self._atom_ptr.ctypes.data, self._k_ptr.ctypes.data, int(self.cell_gradient)))
+        else:
+            n_work = int(lib.mipme_ewald_channels_batch_work(F, self._atom_ptr.ctypes.data, self._k_ptr.ctypes.data, nc,
+                                                             int(self.cell_gradient)))
         if n_work == 0:
             raise ValueError(f"{who}: the batch is beyond the limits of the frame table: the sums of the atoms ({self.atom_ptr[-1]}) "
                              f"and of the k-vectors ({int(self._k_ptr[-1])}) must stay below 2^31 and every launch below 2^24 "
@@ -1693,14 +1754,14 @@ class GraphedEwaldBatch(_FrameTableBatch):
         if SK > 0:
             self._freq = torch.tensor(np.concatenate(f_all), device=device)
             self._mult = torch.tensor(np.concatenate(m_all), device=device)
-            self._kvec, self._G, self._Sc, self._Ss = new(SK, 3), new(SK), new(SK), new(SK)
+            self._kvec, self._G, self._Sc, self._Ss = new(SK, 3), new(SK), new(nc * SK), new(nc * SK)
             self._dG = new(SK) if self.cell_gradient else None
         with torch.no_grad():
             self.pos = torch.cat([fr[2].detach() for fr in frames]).contiguous()
             self.q = torch.cat([fr[0].detach() for fr in frames]).contiguous()
             self.cells = torch.stack([fr[1].detach() for fr in frames]).contiguous()
         self._rec = new(SN, 4)
-        self.energies, self.forces_flat, self.charge_grads_flat = new(F), new(SN, 3), new(SN, 1)
+        self.energies, self.forces_flat, self.charge_grads_flat = new(F), new(SN, 3), new(SN, nc)
         self.cell_grads = new(F, 3, 3) if self.cell_gradient else None
         self.status = torch.zeros(F, dtype=torch.int32, device=device)
         self._work = new(max(1, n_work), dt=torch.float64)
@@ -1711,7 +1772,7 @@ class GraphedEwaldBatch(_FrameTableBatch):
 
     def _launch(self):
         with _lib.on_device(self.device):
-            a = _lib.EwaldBatchArgs(
+            fields = dict(
                 stream=_lib.current_stream(self.device), dtype=self._dt, full_list=int(self.full), pot=C.pointer(self._desc),
                 n_frames=self.n_frames, cell_gradient=int(self.cell_gradient), lr_wavelength=self.lr_wavelength,
                 atom_ptr=self._atom_ptr.ctypes.data, k_ptr=self._k_ptr.ctypes.data, entry_ptr=self._entry_ptr.ctypes.data,
@@ -1722,7 +1783,26 @@ class GraphedEwaldBatch(_FrameTableBatch):
                 s_sin=_lib.ptr(self._Ss), energies=self.energies.data_ptr(), forces=self.forces_flat.data_ptr(),
                 grad_charges=self.charge_grads_flat.data_ptr(), grad_cells=_lib.ptr(self.cell_grads), status=self.status.data_ptr(),
                 work=self._work.data_ptr())
-            _lib.check(self._lib.mipme_ewald_batch(C.byref(a)))
+            if self.n_channels == 1:
+                a = _lib.EwaldBatchArgs(**fields)
+                _lib.check(self._lib.mipme_ewald_batch(C.byref(a)))
+            else:
+                a = _lib.EwaldChannelsBatchArgs(n_channels=self.n_channels, **fields)
+                _lib.check(self._lib.mipme_ewald_channels_batch(C.byref(a)))
+
+    def _check_charges(self, charges):
+        """``charges=`` of a call on a multi-channel batch: exactly (sum N, C) or F tensors (N_f, C), checked before anything of
+        the object changes (the single-channel batch keeps its own rules)."""
+        if charges is None or self.n_channels == 1:
+            return
+        who = "GraphedEwaldBatch"
+        if isinstance(charges, (list, tuple)):
+            if len(charges) != self.n_frames:
+                raise ValueError(f"{who}: a list of {self.n_frames} per-frame tensors wanted, got {len(charges)}")
+            for f, t in enumerate(charges):
+                _check_channel_charges(who, t, self.atom_ptr[f + 1] - self.atom_ptr[f], self.n_channels, frame=f)
+        else:
+            _check_channel_charges(who, charges, self.atom_ptr[-1], self.n_channels)
 
     def kgrid_matches(self, cells) -> list:
         """Per frame, whether the eager calculator would sum the frame's k grid for its cell in ``cells`` ((F, 3, 3) or a list):
@@ -1735,11 +1815,13 @@ class GraphedEwaldBatch(_FrameTableBatch):
         """New neighbour lists, a sequence of F ``(neighbor_indices, neighbor_shifts)``: pack them, build the frame table again
         and capture the step again; the k grids and every buffer are kept.  Every list is validated and packed before anything of
         the object changes: a refused call leaves the object replaying what it replayed."""
+        self._check_charges(charges)
         self._recapture(lists, positions, charges, cells)
 
     def __call__(self, positions=None, charges=None, cells=None):
         """``energies, forces, dE_dq`` (+ ``dE_dcell`` with ``cell_gradient``) of the current -- or the given -- positions, charges
         and cells of all frames: up to three copies and one graph replay."""
+        self._check_charges(charges)
         self._load(positions, charges, cells)
         self.graph.replay()
         out = (self.energies, self.forces, self.charge_grads)
