@@ -9,13 +9,14 @@
 // with S the structure factors of the charges q and T those of the upstream gradient g.  The 1/V factor, self /
 // background / slab terms and the cell dependence of k and V stay with the caller (host layer: autograd through the
 // k-vector generation).  There is no dense contraction worth MFMA at n_channels = 1 (the einsums are matrix-vector).
+//
+// The phase k.r goes through dipole_phase3 (dipole_device.h), as in the graphed steps: in float it is formed and reduced in
+// double, so that cos and sin are good to 1.3e-7 of themselves and not to |k.r| 2^-24 absolute.
 #include "common.h"
+#include "dipole_device.h"
 #include "kpot.h"
 
 namespace mipme {
-
-__device__ __forceinline__ void phase(float a, float& s, float& c) { sincosf(a, &s, &c); }
-__device__ __forceinline__ void phase(double a, double& s, double& c) { sincos(a, &s, &c); }
 
 static constexpr int kEwaldTile = 256;   // atoms staged per LDS tile
 static constexpr int kEwaldCMax = 4;     // channels per pass
@@ -73,7 +74,7 @@ __global__ __launch_bounds__(256) void ewald_structure_kernel(int64_t N, int C, 
       __syncthreads();
       for (int i = al; i < n; i += AL) {
         T s, c;
-        phase(kx * sp[3 * i] + ky * sp[3 * i + 1] + kz * sp[3 * i + 2], s, c);
+        dipole_phase3(kx, ky, kz, sp[3 * i], sp[3 * i + 1], sp[3 * i + 2], s, c);
 #pragma unroll
         for (int ch = 0; ch < kEwaldCMax; ++ch) {
           ac[ch] += sw[i * kEwaldCMax + ch] * c;
@@ -133,7 +134,7 @@ __global__ __launch_bounds__(256) void ewald_potential_kernel(int C, int64_t K, 
     for (int c = 0; c < kEwaldCMax; ++c) acc[c] = T(0);
     for (int64_t k = threadIdx.x; k < K; k += 256) {
       T s, c;
-      phase(kvec[3 * k] * x + kvec[3 * k + 1] * y + kvec[3 * k + 2] * z, s, c);
+      dipole_phase3(kvec[3 * k], kvec[3 * k + 1], kvec[3 * k + 2], x, y, z, s, c);
       const T g = G[k];
       for (int ch = 0; ch < nc; ++ch) acc[ch] += g * (c * Sc[k * C + c0 + ch] + s * Ss[k * C + c0 + ch]);
     }
@@ -181,7 +182,7 @@ __global__ __launch_bounds__(256) void ewald_grad_positions_kernel(int C, int64_
   for (int64_t k = threadIdx.x; k < K; k += 256) {
     const T kx = kvec[3 * k], ky = kvec[3 * k + 1], kz = kvec[3 * k + 2];
     T s, c;
-    phase(kx * x + ky * y + kz * z, s, c);
+    dipole_phase3(kx, ky, kz, x, y, z, s, c);
     const T b = G[k] * ewald_bracket<T>(C, g + i * C, q + i * C, Sc + k * C, Ss + k * C, Tc + k * C, Ts + k * C, s, c);
     ax += b * kx;
     ay += b * ky;
@@ -255,7 +256,7 @@ __global__ __launch_bounds__(256) void ewald_grad_kvectors_kernel(int64_t N, int
       for (int i = al; i < n; i += AL) {
         const T x = sp[3 * i], y = sp[3 * i + 1], z = sp[3 * i + 2];
         T s, c;
-        phase(kx * x + ky * y + kz * z, s, c);
+        dipole_phase3(kx, ky, kz, x, y, z, s, c);
         const T b = ewald_bracket<T>(kEwaldCMax, sg + i * kEwaldCMax, sq + i * kEwaldCMax, lSc, lSs, lTc, lTs, s, c);
         ax += b * x;
         ay += b * y;

@@ -76,9 +76,9 @@ __device__ __forceinline__ void es_prep_body(const KPot& kp, int64_t N, int64_t 
 
 // ---- 2. structure factors: 32 lanes per k-vector, the records streamed through LDS -------------------------------------------
 // The mapping of ewald_structure_kernel (ewald.hip) for one channel, with the phase of the atom and cell bodies below
-// (dipole_phase3: in float the phase is formed and reduced in double).  That kernel itself rounds a float phase before sincosf,
-// and then S and the (c, s) of the later launches disagree by |k.r| ulps per term: c S_s - s S_c of an atom with its own
-// contribution to S no longer cancels, which is the whole force on a single atom.
+// (dipole_phase3: in float the phase is formed and reduced in double).  With a float phase rounded before sincosf, S and the
+// (c, s) of the later launches disagree by |k.r| ulps per term: c S_s - s S_c of an atom with its own contribution to S no
+// longer cancels, which is the whole force on a single atom.
 template <typename T>
 __device__ __forceinline__ void es_structure_body(int64_t N, int64_t K, int64_t blk, const AtomRecord<T>* __restrict__ rec,
                                                   const T* __restrict__ kvec, T* __restrict__ Sc, T* __restrict__ Ss) {
