@@ -2,7 +2,8 @@
 the construction cell and at other cells from ONE graph, against the reference's own outputs
 (tests/golden/dipole_cell_step.npz), against the eager CalculatorDipole and against central differences of its own energy; the
 status word; bit reproducibility; a direct potential; edge sizes; a new list.  And the object without the keyword: the same
-golden, and the bits of the parent commit (profiles/step_skeleton_bits.txt)."""
+golden, and the bits of the parent commit (profiles/step_skeleton_bits.txt); the object with the keyword has recorded bits too
+(profiles/dipole_one_body_bits.txt)."""
 
 import hashlib
 import importlib.util
@@ -181,6 +182,19 @@ def test_the_object_without_the_keyword_has_the_bits_of_the_parent(dtype, cell_g
     head = " ".join(lines[0].split()[:3])
     got = f"## {head}: {len(lines)} lines, sha256 {hashlib.sha256(chr(10).join(lines).encode()).hexdigest()}"
     recorded = open(os.path.join(ROOT, "profiles", "step_skeleton_bits.txt")).read().splitlines()
+    assert got in recorded, got
+
+
+@pytest.mark.parametrize("cell_gradient", [True, False], ids=["cg1", "cg0"])
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_the_cell_step_has_the_bits_of_the_parent(dtype, cell_gradient):
+    """The same systems through the object WITH the keyword, each at its construction cell and at the strained one from the same
+    graph (tools/step_bits.py --cell-step): the lines hash to what profiles/dipole_one_body_bits.txt records for the commit whose
+    kernels of csrc/dipole_step.hip were written out in full."""
+    lines = _step_bits().run_dipole(dtype, cell_gradient, follow_cell=True)
+    head = " ".join(lines[0].split()[:3])
+    got = f"## {head}: {len(lines)} lines, sha256 {hashlib.sha256(chr(10).join(lines).encode()).hexdigest()}"
+    recorded = open(os.path.join(ROOT, "profiles", "dipole_one_body_bits.txt")).read().splitlines()
     assert got in recorded, got
 
 

@@ -28,6 +28,23 @@ def test_the_systems_of_the_tool_exist():
         assert {"q", "pos", "cell", "pairs", "shifts", "spacing"} <= set(s) and len(members) == len(weights), name
 
 
+def test_the_cell_step_variant_of_the_tool():
+    """``run_dipole(..., follow_cell=True)``: the strain is the golden script's, the names it builds the step from exist, and the
+    class takes the two keywords and has the status word."""
+    import numpy as np
+
+    tool = _tool()
+    assert "follow_cell" in inspect.signature(tool.run_dipole).parameters
+    m = tool.strain()
+    gold = np.load(os.path.join(ROOT, "tests", "golden", "dipole_cell_step.npz"))
+    assert m.shape == (3, 3) and np.array_equal(m, np.eye(3) + gold["strain"]) and np.abs(gold["strain"]).max() > 0
+    assert callable(tool.D._t) and hasattr(tool.D, "DEV")
+    params = inspect.signature(tool.tpa.GraphedDipoleStep.__init__).parameters
+    assert "follow_cell" in params and "cell_gradient" in params
+    assert "cell" in inspect.signature(tool.tpa.GraphedDipoleStep.__call__).parameters
+    assert "self.status" in inspect.getsource(tool.tpa.GraphedDipoleStep)
+
+
 def test_the_names_the_tool_uses_behind_them():
     tool = _tool()
     assert callable(tool.D._build) and "cell_gradient" in inspect.signature(tool.D._build).parameters

@@ -13,11 +13,19 @@ one ``##`` line per configuration -- the number of its lines and the SHA-256 of 
 ``tests/test_step_bits_host.py`` walks them without a GPU, so a rename there shows up in the suite.
 
     python tools/step_bits.py [output file]
+
+``--cell-step``: ``GraphedDipoleStep(follow_cell=True)`` alone, on the same dipole systems in the same four configurations, each
+system at its construction cell and, from the same graph, at cell (I + eps) with the eps of
+``tests/golden/make_dipole_cell_step_golden.py``: E, F, dE/dmu, dE/dcell and the status word.  ``profiles/dipole_one_body_bits.txt``
+keeps that text as the commit before the kernels of ``csrc/dipole_step.hip`` became wrappers of ``csrc/dipole_step_bodies.h`` gave it.
+
+    python tools/step_bits.py --cell-step [output file]
 """
 import hashlib
 import os
 import sys
 
+import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -52,14 +60,32 @@ def dipole_systems():
         yield p, calc, (F[f"{p}_dipoles"], F[f"{p}_positions"], F[f"{p}_cell"], F[f"{p}_pairs"], F[f"{p}_shifts"])
 
 
-def run_dipole(dtype, cell_gradient):
-    head = f"dipole {str(dtype)[6:]} cg={int(cell_gradient)}"
-    keys = ("E", "F", "dE/dmu", "dE/dcell")
+def strain():
+    """I + eps of tests/golden/make_dipole_cell_step_golden.py: the second cell of the step that follows its cell"""
+    gold = np.load(os.path.join(ROOT, "tests", "golden", "dipole_cell_step.npz"))
+    return np.eye(3) + gold["strain"]
+
+
+def run_dipole(dtype, cell_gradient, follow_cell=False):
+    """follow_cell: ``GraphedDipoleStep(follow_cell=True)`` of the same systems, each at its construction cell (c0) and then, from
+    the same graph, at cell (I + eps) with the positions scaled along (c1); the status word is a line of its own"""
+    head = f"dipole{'_cell' if follow_cell else ''} {str(dtype)[6:]} cg={int(cell_gradient)}"
+    keys = ("E", "F", "dE/dmu", "dE/dcell")[:4 if cell_gradient else 3]
     lines = []
     for name, calc, system in dipole_systems():
-        out = D._build(calc, dtype, *system, cell_gradient=cell_gradient)()
-        torch.cuda.synchronize()
-        lines += [f"{head} {name} {key} {sha(o)}" for key, o in zip(keys, out)]
+        if not follow_cell:
+            out = D._build(calc, dtype, *system, cell_gradient=cell_gradient)()
+            torch.cuda.synchronize()
+            lines += [f"{head} {name} {key} {sha(o)}" for key, o in zip(keys, out)]
+            continue
+        mu, pos, cell, pairs, shifts = system
+        ti = torch.tensor(np.asarray(pairs, dtype=np.int64), device=D.DEV)
+        step = tpa.GraphedDipoleStep(calc, D._t(mu, dtype), D._t(cell, dtype), D._t(pos, dtype), ti, D._t(shifts, dtype),
+                                     cell_gradient=cell_gradient, follow_cell=True)
+        for ctag, m in (("c0", np.eye(3)), ("c1", strain())):
+            out = step(D._t(np.asarray(pos) @ m, dtype), cell=D._t(np.asarray(cell) @ m, dtype))
+            torch.cuda.synchronize()
+            lines += [f"{head} {name} {ctag} {key} {sha(o)}" for key, o in zip(keys + ("status",), (*out, step.status))]
     return lines
 
 
@@ -93,7 +119,9 @@ def run_combined(dtype, weight_gradient):
 def main(argv):
     lines, summary = [], []
     digest = lambda ls: hashlib.sha256("\n".join(ls).encode()).hexdigest()  # noqa: E731
-    for run in (run_dipole, run_combined):
+    cell_step = "--cell-step" in argv
+    argv = [a for a in argv if a != "--cell-step"]
+    for run in ((lambda dtype, grad: run_dipole(dtype, grad, follow_cell=True)),) if cell_step else (run_dipole, run_combined):
         for dtype in (torch.float64, torch.float32):
             for grad in (True, False):
                 got = run(dtype, grad)

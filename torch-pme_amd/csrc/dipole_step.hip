@@ -23,12 +23,16 @@
 // mipme_dipole_cell_step is the same step with the CELL as an input of every call: dipole_cell_step_prep_kernel in the place of
 // records (and of the caller's tables: k, G, dG, A^-1, 1/V from the nine values of the device cell), dipole_cell_step_finish_kernel
 // and dipole_cell_step_final_kernel in the place of finish and final; see the section behind the final kernel.
+//
+// The kernels of this file are wrappers: each passes its arguments and blockIdx to the body of dipole_step_bodies.h that
+// dipole_batch.hip calls for the same launch (the form of ewald_step.hip), so every formula of the step is written once for the
+// three entry points.  The two finish kernels are the exception and keep their own text; the comment above each says why.
 #include <cmath>
 
 #include "dipole_device.h"
-#include "ewald_step_device.h"  // kEsGeom, es_invert_cell, lr_kernel_dev: what the step that follows its cell shares with the Ewald step
+#include "dipole_step_bodies.h"
+#include "ewald_step_device.h"  // kEsGeom: the geometry record the step that follows its cell shares with the Ewald step
 #include "host.h"
-#include "rows_body.h"
 #include "step_device.h"
 
 namespace mipme {
@@ -46,20 +50,7 @@ template <typename T>
 __global__ __launch_bounds__(kDsBlock) void dipole_step_records_kernel(int64_t N, const T* __restrict__ pos, const T* __restrict__ mu,
                                                                       AtomRecord<T>* __restrict__ recp,
                                                                       AtomRecord<T>* __restrict__ recm, double* __restrict__ mu_part) {
-  __shared__ double red[kStepWaves];
-  const int64_t a = int64_t(blockIdx.x) * kDsBlock + threadIdx.x;
-  double m[3] = {0.0, 0.0, 0.0};
-  if (a < N) {
-    const T mx = mu[3 * a], my = mu[3 * a + 1], mz = mu[3 * a + 2];
-    recp[a] = AtomRecord<T>{pos[3 * a], pos[3 * a + 1], pos[3 * a + 2], T(0)};
-    recm[a] = AtomRecord<T>{mx, my, mz, T(0)};
-    m[0] = double(mx), m[1] = double(my), m[2] = double(mz);
-  }
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    const double s = block_sum<kStepWaves>(m[c], red);
-    if (threadIdx.x == 0) mu_part[3 * int64_t(blockIdx.x) + c] = s;
-  }
+  ds_records_body<T>(N, blockIdx.x, pos, mu, recp, recm, mu_part);
 }
 
 // ---- 2. fused atom kernel: block (i, slice), atom i against the k-vectors [slice * chunk, (slice + 1) * chunk) ---------------
@@ -70,41 +61,7 @@ __global__ __launch_bounds__(kDsBlock) void dipole_step_atom_kernel(int64_t K, i
                                                                    const T* __restrict__ kvec, const T* __restrict__ G,
                                                                    const T* __restrict__ Sc, const T* __restrict__ Ss,
                                                                    T* __restrict__ part) {
-  __shared__ T red[kStepWaves][6];
-  const int64_t i = blockIdx.x, N = gridDim.x;
-  const int64_t k0 = int64_t(blockIdx.y) * chunk, k1 = min<int64_t>(K, k0 + chunk);
-  const AtomRecord<T> p = recp[i], m = recm[i];
-  T fx = T(0), fy = T(0), fz = T(0), bx = T(0), by = T(0), bz = T(0);
-  for (int64_t k = k0 + threadIdx.x; k < k1; k += kDsBlock) {
-    const T gk = G[k];
-    if (gk == T(0)) continue;  // exact: the term is G(k) times a finite sum
-    const T kx = kvec[3 * k], ky = kvec[3 * k + 1], kz = kvec[3 * k + 2];
-    const T sc = Sc[k], ss = Ss[k];
-    T s, c;
-    dipole_phase3(kx, ky, kz, p.x, p.y, p.z, s, c);
-    const T f = gk * (c * sc + s * ss);
-    const T b = gk * (m.x * kx + m.y * ky + m.z * kz) * (c * ss - s * sc);
-    fx += f * kx;
-    fy += f * ky;
-    fz += f * kz;
-    bx += b * kx;
-    by += b * ky;
-    bz += b * kz;
-  }
-  fx = wave_sum(fx), fy = wave_sum(fy), fz = wave_sum(fz);
-  bx = wave_sum(bx), by = wave_sum(by), bz = wave_sum(bz);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) {
-    red[wave][0] = fx, red[wave][1] = fy, red[wave][2] = fz;
-    red[wave][3] = bx, red[wave][4] = by, red[wave][5] = bz;
-  }
-  __syncthreads();
-  if (threadIdx.x < 6) {
-    T s = T(0);
-#pragma unroll
-    for (int w = 0; w < kStepWaves; ++w) s += red[w][threadIdx.x];
-    part[(int64_t(blockIdx.y) * N + i) * 6 + threadIdx.x] = s;
-  }
+  ds_atom_body<T>(blockIdx.x, blockIdx.y, gridDim.x, K, chunk, recp, recm, kvec, G, Sc, Ss, part);
 }
 
 // ---- 3. dipole pair rows -------------------------------------------------------------------------------------------------
@@ -119,68 +76,7 @@ __global__ __launch_bounds__(kDsBlock) void dipole_step_rows_kernel(DipPot<T> P,
                                                                    const AtomRecord<T>* __restrict__ recp,
                                                                    const AtomRecord<T>* __restrict__ recm, const T* __restrict__ cell,
                                                                    T scale, T* __restrict__ row_out, double* __restrict__ cell_part) {
-  __shared__ AtomRecord<T> shift_tab[kShiftTableSize];
-  __shared__ double red[kStepWaves][9];
-  step_fill_shift_table(shift_tab, cell);
-  __syncthreads();
-  const StepRow row = step_row(N, blockIdx.x, row_ptr);
-  const AtomRecord<T> pa = recp[row.a], ma = recm[row.a];
-  T fx = T(0), fy = T(0), fz = T(0), gx = T(0), gy = T(0), gz = T(0);
-  T w00 = T(0), w01 = T(0), w02 = T(0), w10 = T(0), w11 = T(0), w12 = T(0), w20 = T(0), w21 = T(0), w22 = T(0);
-  for (int base = row.beg; base < row.end; base += 16) {
-    const int e = base + row.sub;
-    const StepEntry en = step_entry(ent32, e, row);
-    const AtomRecord<T> po = recp[en.o], mo = recm[en.o];
-    const AtomRecord<T> sh = shift_tab[en.code];
-    const T vx = (po.x - pa.x) + sh.x, vy = (po.y - pa.y) + sh.y, vz = (po.z - pa.z) + sh.z;
-    const T r2 = vx * vx + vy * vy + vz * vz;
-    const T ri = T(1) / fsqrt(r2);
-    T B, C, dB, dC;
-    dipole_bc<T, true, EXCL>(P, r2, ri, B, C, dB, dC);
-    const T cr = C * (mo.x * vx + mo.y * vy + mo.z * vz);
-    T ex = T(0), ey = T(0), ez = T(0);
-    dipole_pair_grad<T>(vx, vy, vz, C, dB, dC, ma.x, ma.y, ma.z, mo.x, mo.y, mo.z, ex, ey, ez);
-    if (en.ok) {
-      fx += B * mo.x - cr * vx;
-      fy += B * mo.y - cr * vy;
-      fz += B * mo.z - cr * vz;
-      gx += ex;
-      gy += ey;
-      gz += ez;
-      if (CELL && e < row.mid) {  // role i: the listed pair, its own shift
-        T sx, sy, sz;
-        step_shift_of_code(en.code, sx, sy, sz);
-        w00 += sx * ex, w01 += sx * ey, w02 += sx * ez;
-        w10 += sy * ex, w11 += sy * ey, w12 += sy * ez;
-        w20 += sz * ex, w21 += sz * ey, w22 += sz * ez;
-      }
-    }
-  }
-  fx = row_sum(fx), fy = row_sum(fy), fz = row_sum(fz);
-  gx = row_sum(gx), gy = row_sum(gy), gz = row_sum(gz);
-  if (row.sub == 0 && row.valid) {
-    T* o = row_out + 6 * row.a;
-    o[0] = scale * fx, o[1] = scale * fy, o[2] = scale * fz;
-    o[3] = scale * gx, o[4] = scale * gy, o[5] = scale * gz;
-  }
-  if (CELL) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const double s0 = wave_sum(double(w00)), s1 = wave_sum(double(w01)), s2 = wave_sum(double(w02));
-    const double s3 = wave_sum(double(w10)), s4 = wave_sum(double(w11)), s5 = wave_sum(double(w12));
-    const double s6 = wave_sum(double(w20)), s7 = wave_sum(double(w21)), s8 = wave_sum(double(w22));
-    if (lane == 0) {
-      red[wave][0] = s0, red[wave][1] = s1, red[wave][2] = s2;
-      red[wave][3] = s3, red[wave][4] = s4, red[wave][5] = s5;
-      red[wave][6] = s6, red[wave][7] = s7, red[wave][8] = s8;
-    }
-    __syncthreads();
-    if (tid < 9) {
-      double s = 0.0;
-#pragma unroll
-      for (int w = 0; w < kStepWaves; ++w) s += red[w][tid];
-      cell_part[9 * int64_t(blockIdx.x) + tid] = double(scale) * s;
-    }
-  }
+  ds_rows_body<T, EXCL, CELL>(P, N, blockIdx.x, row_ptr, ent32, recp, recm, cell, scale, row_out, cell_part);
 }
 
 // ---- 4. per-k cell gradient: 32 lanes per k-vector, positions and dipoles streamed through LDS ------------------------------
@@ -192,71 +88,15 @@ __global__ __launch_bounds__(kDsBlock) void dipole_step_cellk_kernel(int64_t N, 
                                                                     const T* __restrict__ G, const T* __restrict__ dG,
                                                                     const T* __restrict__ Sc, const T* __restrict__ Ss,
                                                                     double* __restrict__ k_part) {
-  __shared__ T sp[kStepTile * 3];
-  __shared__ T sm[kStepTile * 3];
-  __shared__ double red[kStepKPerBlock][kStepCellK];
-  const int al = threadIdx.x % kStepKLanes, kl = threadIdx.x / kStepKLanes;
-  const int64_t k = int64_t(blockIdx.x) * kStepKPerBlock + kl;
-  const bool live = k < K && (G[k] != T(0) || dG[k] != T(0));
-  const int64_t kc = k < K ? k : 0;
-  const T kx = kvec[3 * kc], ky = kvec[3 * kc + 1], kz = kvec[3 * kc + 2];
-  const T lSc = Sc[kc], lSs = Ss[kc];
-  T ax = T(0), ay = T(0), az = T(0);
-  for (int64_t base = 0; base < N; base += kStepTile) {
-    const int n = int(min<int64_t>(kStepTile, N - base));
-    __syncthreads();
-    for (int t = threadIdx.x; t < 3 * n; t += kDsBlock) {
-      sp[t] = pos[3 * base + t];
-      sm[t] = mu[3 * base + t];
-    }
-    __syncthreads();
-    if (live)
-      for (int i = al; i < n; i += kStepKLanes) {
-        const T x = sp[3 * i], y = sp[3 * i + 1], z = sp[3 * i + 2];
-        const T mx = sm[3 * i], my = sm[3 * i + 1], mz = sm[3 * i + 2];
-        T s, c;
-        dipole_phase3(kx, ky, kz, x, y, z, s, c);
-        const T a1 = c * lSc + s * lSs;
-        const T b = (mx * kx + my * ky + mz * kz) * (c * lSs - s * lSc);
-        ax += mx * a1 + b * x;
-        ay += my * a1 + b * y;
-        az += mz * a1 + b * z;
-      }
-  }
-#pragma unroll
-  for (int off = kStepKLanes / 2; off > 0; off >>= 1) {
-    ax += __shfl_xor(ax, off, kStepKLanes);
-    ay += __shfl_xor(ay, off, kStepKLanes);
-    az += __shfl_xor(az, off, kStepKLanes);
-  }
-  if (al == 0) {
-    double g[3] = {0.0, 0.0, 0.0}, e = 0.0;
-    const double kd[3] = {double(kx), double(ky), double(kz)};
-    if (live) {
-      const double gk = double(G[kc]), s2 = double(lSc) * double(lSc) + double(lSs) * double(lSs), d = double(dG[kc]) * s2;
-      g[0] = gk * double(ax) + d * kd[0];
-      g[1] = gk * double(ay) + d * kd[1];
-      g[2] = gk * double(az) + d * kd[2];
-      e = 0.5 * gk * s2;
-    }
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-      for (int n = 0; n < 3; ++n) red[kl][3 * a + n] = g[a] * kd[n];
-    red[kl][9] = e;
-  }
-  __syncthreads();
-  if (threadIdx.x < kStepCellK) {
-    double s = 0.0;
-#pragma unroll
-    for (int q = 0; q < kStepKPerBlock; ++q) s += red[q][threadIdx.x];
-    k_part[kStepCellK * int64_t(blockIdx.x) + threadIdx.x] = s;
-  }
+  ds_cellk_body<T>(N, K, blockIdx.x, pos, mu, kvec, G, dG, Sc, Ss, k_part);
 }
 
 // ---- 5. finish -----------------------------------------------------------------------------------------------------------
 // 16 lanes per atom: lane l adds the slices l, l + 16, ... in that order, then the 16 lanes are added by the shuffle tree of the
 // rows (with few atoms there are hundreds of slices: one thread per atom would walk them one dependent load after the other)
+// Own text, not a body: as a wrapper of one shared finish body its fp32 instance failed the BITS condition.  The compiler fuses
+// other products of inv_vol f - self mu + bg/V M into multiply-adds in the inlined body (502 instructions for 499), and 38 of the
+// 105 fp32 lines of tools/step_bits.py (12 E, 26 dE/dmu) were no longer the parent's; fp64 was equal (docs/HISTORY.md).
 template <typename T>
 __global__ __launch_bounds__(kDsBlock) void dipole_step_finish_kernel(int64_t N, int n_slices, T inv_vol, T self_term, T bg_over_v,
                                                                      const AtomRecord<T>* __restrict__ recm,
@@ -308,37 +148,16 @@ __global__ __launch_bounds__(kDsBlock) void dipole_step_final_kernel(int64_t n_e
                                                                     const double* __restrict__ k_cell, int64_t n_mu_blocks,
                                                                     const double* __restrict__ mu_part, double inv_vol, double bg,
                                                                     const T* __restrict__ inv_cell, T* __restrict__ grad_cell) {
-  __shared__ double red[kStepWaves];
-  __shared__ double tot[9 + kStepCellK + 3];
-  const double E = step_strided_sum(e_part, n_e_blocks, 1, 0, red);
-  if (threadIdx.x == 0) energy[0] = T(E);
-  if (CELL) {
-    step_cell_totals(row_cell, n_row_blocks, k_cell, n_k_blocks, tot, red);
-    for (int j = 0; j < 3; ++j) {
-      const double s = step_strided_sum(mu_part, n_mu_blocks, 3, j, red);
-      if (threadIdx.x == 0) tot[9 + kStepCellK + j] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < 9) {
-      const int m = threadIdx.x / 3, n = threadIdx.x % 3;
-      const double* Wr = tot;
-      const double* Wk = tot + 9;
-      const double Ek = tot[9 + 9];
-      const double* M = tot + 9 + kStepCellK;
-      const double e_v = inv_vol * (Ek + 0.5 * bg * (M[0] * M[0] + M[1] * M[1] + M[2] * M[2]));  // what scales with 1/V
-      double chain = 0.0;
-      for (int a = 0; a < 3; ++a) chain += double(inv_cell[3 * a + m]) * Wk[3 * a + n];
-      grad_cell[3 * m + n] = T(Wr[3 * m + n] - inv_vol * chain - e_v * double(inv_cell[3 * n + m]));
-    }
-  }
+  ds_final_core<T, CELL, T>(n_e_blocks, e_part, energy, n_row_blocks, row_cell, n_k_blocks, k_cell, n_mu_blocks, mu_part, &inv_vol, bg,
+                            inv_cell, false, grad_cell);
 }
 
 // ---- the step that follows its cell (mipme_dipole_cell_step) ------------------------------------------------------------------
 // Everything that depends on the cell's values comes from the nine values of the device cell in every call: prep takes the place
 // of the records launch and also writes the k table, the geometry record (the head of the work area: the record of the Ewald
 // step, kEsGeom doubles) and the status word; finish and final read 1/V and A^-1 from that record.  Structure, atoms, rows and
-// cell k are the kernels above.  The three kernels are written out in full: a body shared with the kernels above through a helper
-// is not compiled as the text it replaces (docs/HISTORY.md, the step_device.h entry).
+// cell k are the kernels above.  Prep and final are wrappers of ds_prep_body and ds_final_body (the latter shares ds_final_core
+// with the final kernel above); finish keeps its own text.
 
 // work: ds_work_layout behind the geometry record
 static StepWork dcs_work_layout(int64_t N, int64_t K, bool cell, void* base) {
@@ -360,64 +179,14 @@ __global__ __launch_bounds__(kDsBlock) void dipole_cell_step_prep_kernel(KPot kp
                                                                         AtomRecord<T>* __restrict__ recp,
                                                                         AtomRecord<T>* __restrict__ recm, double* __restrict__ mu_part,
                                                                         double* __restrict__ geom, int* __restrict__ status) {
-  __shared__ double red[kStepWaves];
-  const int blk = int(blockIdx.x);
-  if (blk >= n_table_blocks) {  // (uniform per block) what dipole_step_records_kernel does
-    const int64_t a = int64_t(blk - n_table_blocks) * kDsBlock + threadIdx.x;
-    double m[3] = {0.0, 0.0, 0.0};
-    if (a < N) {
-      const T mx = mu[3 * a], my = mu[3 * a + 1], mz = mu[3 * a + 2];
-      recp[a] = AtomRecord<T>{pos[3 * a], pos[3 * a + 1], pos[3 * a + 2], T(0)};
-      recm[a] = AtomRecord<T>{mx, my, mz, T(0)};
-      m[0] = double(mx), m[1] = double(my), m[2] = double(mz);
-    }
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const double s = block_sum<kStepWaves>(m[c], red);
-      if (threadIdx.x == 0) mu_part[3 * int64_t(blk - n_table_blocks) + c] = s;
-    }
-    return;
-  }
-  double A[9];
-  const EsCell g = es_invert_cell(cell, A);
-  if (blk == 0 && threadIdx.x == 0) {
-    // A^-1 = (A^-T)^T, row-major
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-      for (int c = 0; c < 3; ++c) geom[3 * r + c] = g.recip[3 * c + r];
-    geom[9] = g.inv_vol;
-    geom[10] = g.bad ? 1.0 : 0.0;
-    // bit 0: the eager call would choose another k grid for this cell, ns_d = ceil(|a_d| / lr_wavelength)
-    const int ns[3] = {ns0, ns1, ns2};
-    int st = g.bad ? 2 : 0;
-    if (lr_wavelength > 0.0) {
-#pragma unroll
-      for (int d = 0; d < 3; ++d) {
-        const double norm = sqrt(A[3 * d] * A[3 * d] + A[3 * d + 1] * A[3 * d + 1] + A[3 * d + 2] * A[3 * d + 2]);
-        if (!(ceil(norm / lr_wavelength) == double(ns[d]))) st |= 1;
-      }
-    }
-    status[0] = st;
-  }
-  const int64_t k = int64_t(blk) * kDsBlock + threadIdx.x;
-  if (k >= K) return;
-  double kv[3] = {0.0, 0.0, 0.0}, v = 0.0, dv = 0.0;
-  if (!g.bad) {  // (a singular cell: a table of zeros, and the final launch writes NaN as the energy)
-    const double f0 = double(freq[3 * k]), f1 = double(freq[3 * k + 1]), f2 = double(freq[3 * k + 2]);
-#pragma unroll
-    for (int n = 0; n < 3; ++n) kv[n] = (2.0 * kPi) * (f0 * g.recip[n] + f1 * g.recip[3 + n] + f2 * g.recip[6 + n]);
-    lr_kernel_dev(kp, kv[0] * kv[0] + kv[1] * kv[1] + kv[2] * kv[2], v, dv);
-    const double m = double(mult[k]);
-    v *= m;
-    dv *= m;
-  }
-  kvec[3 * k] = T(kv[0]), kvec[3 * k + 1] = T(kv[1]), kvec[3 * k + 2] = T(kv[2]);
-  G[k] = T(v);
-  if (dG) dG[k] = T(dv);
+  ds_prep_body<T>(kp, N, K, n_table_blocks, int(blockIdx.x), cell, freq, mult, ns0, ns1, ns2, lr_wavelength, pos, mu, kvec, G, dG, recp,
+                  recm, mu_part, geom, status);
 }
 
 // ---- 5'. finish: dipole_step_finish_kernel with 1/V and bg/V from the geometry record ----------------------------------------------
+// Own text, not a wrapper of ds_finish_body (which holds the same text for the batch): inlined, its fp32 instance failed the BITS
+// condition for the reason given above dipole_step_finish_kernel (508 instructions for 501): 74 of the 270 fp32 lines of
+// tools/step_bits.py --cell-step (22 E, 52 dE/dmu) were no longer the parent's; fp64 was equal.
 template <typename T>
 __global__ __launch_bounds__(kDsBlock) void dipole_cell_step_finish_kernel(int64_t N, int n_slices, T self_term, double background,
                                                                           const double* __restrict__ geom,
@@ -472,30 +241,8 @@ __global__ __launch_bounds__(kDsBlock) void dipole_cell_step_final_kernel(int64_
                                                                          const double* __restrict__ k_cell, int64_t n_mu_blocks,
                                                                          const double* __restrict__ mu_part, double bg,
                                                                          const double* __restrict__ geom, T* __restrict__ grad_cell) {
-  __shared__ double red[kStepWaves];
-  __shared__ double tot[9 + kStepCellK + 3];
-  const bool bad = geom[10] != 0.0;
-  const double E = step_strided_sum(e_part, n_e_blocks, 1, 0, red);
-  if (threadIdx.x == 0) energy[0] = bad ? T(NAN) : T(E);
-  if (CELL) {
-    step_cell_totals(row_cell, n_row_blocks, k_cell, n_k_blocks, tot, red);
-    for (int j = 0; j < 3; ++j) {
-      const double s = step_strided_sum(mu_part, n_mu_blocks, 3, j, red);
-      if (threadIdx.x == 0) tot[9 + kStepCellK + j] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < 9) {
-      const int m = threadIdx.x / 3, n = threadIdx.x % 3;
-      const double* Wr = tot;
-      const double* Wk = tot + 9;
-      const double Ek = tot[9 + 9], inv_vol = geom[9];
-      const double* M = tot + 9 + kStepCellK;
-      const double e_v = inv_vol * (Ek + 0.5 * bg * (M[0] * M[0] + M[1] * M[1] + M[2] * M[2]));  // what scales with 1/V
-      double chain = 0.0;
-      for (int a = 0; a < 3; ++a) chain += geom[3 * a + m] * Wk[3 * a + n];
-      grad_cell[3 * m + n] = bad ? T(NAN) : T(Wr[3 * m + n] - inv_vol * chain - e_v * geom[3 * n + m]);
-    }
-  }
+  ds_final_body<T, CELL>(n_e_blocks, e_part, energy, n_row_blocks, row_cell, n_k_blocks, k_cell, n_mu_blocks, mu_part, bg, geom,
+                         grad_cell);
 }
 
 // ---- host --------------------------------------------------------------------------------------------------------------------

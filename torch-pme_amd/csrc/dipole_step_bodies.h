@@ -1,10 +1,14 @@
-// The seven computations of the dipole step that follows its cell (mipme_dipole_cell_step, dipole_step.hip), each as a body that
-// sees ONE system: its sizes, ITS slices of the buffers and the index of the block inside that system's launch -- the form of
-// ewald_step_bodies.h.  The kernels of dipole_batch.hip call them with the sizes, the slices and the local block index of the
-// frame table; the bodies see nothing of the table.  Each does what the kernel named above it does, the same arithmetic in the
-// same order; what is computed is described at the head of dipole_step.hip.  The kernels of dipole_step.hip and dipole.hip are
-// written out in full and do not call these bodies (a body shared through a helper is not compiled as the text it replaces:
-// docs/HISTORY.md).  The LDS arrays are declared in the bodies: every body is inlined into the one kernel that calls it.
+// The computations of the dipole step (dipole_step.hip), each ONCE, as a body that sees ONE system: its sizes, ITS slices of the
+// buffers and the index of the block inside that system's launch -- the form of ewald_step_bodies.h.  The kernels of
+// dipole_step.hip call them with their arguments and blockIdx (mipme_dipole_step and mipme_dipole_cell_step), the kernels of
+// dipole_batch.hip with the sizes, the slices and the local block index of the frame table; the bodies see nothing of the table.
+// What is computed is described at the head of dipole_step.hip.  The final launch of the step with a fixed cell and of the step that
+// follows its cell differ in where 1/V and A^-1 come from and in nothing else: ds_final_core takes them as pointers,
+// ds_final_body reads them from the geometry record.  Three kernels do NOT call a body and keep their own text
+// (docs/HISTORY.md, "one body for each dipole step kernel"): dipole_step_finish_kernel and dipole_cell_step_finish_kernel of
+// dipole_step.hip -- called through a body, the fp32 instances contract other products of dE/dmu into fused multiply-adds and give
+// other bits -- so ds_finish_body serves the batch alone; and dipole_structure_kernel of dipole.hip, whose G is nullable.  The
+// LDS arrays are declared in the bodies: every body is inlined into the one kernel that calls it.
 #pragma once
 
 #include <cmath>
@@ -17,6 +21,28 @@
 
 namespace mipme {
 
+// ---- 0. records (dipole_step_records_kernel, and the atom blocks of prep): (x, y, z, -) / (mu_x, mu_y, mu_z, -) of every atom and
+// the float64 block partials of sum_j mu_j
+template <typename T>
+__device__ __forceinline__ void ds_records_body(int64_t N, int64_t blk, const T* __restrict__ pos, const T* __restrict__ mu,
+                                                AtomRecord<T>* __restrict__ recp, AtomRecord<T>* __restrict__ recm,
+                                                double* __restrict__ mu_part) {
+  __shared__ double red[kStepWaves];
+  const int64_t a = blk * kStepBlock + threadIdx.x;
+  double m[3] = {0.0, 0.0, 0.0};
+  if (a < N) {
+    const T mx = mu[3 * a], my = mu[3 * a + 1], mz = mu[3 * a + 2];
+    recp[a] = AtomRecord<T>{pos[3 * a], pos[3 * a + 1], pos[3 * a + 2], T(0)};
+    recm[a] = AtomRecord<T>{mx, my, mz, T(0)};
+    m[0] = double(mx), m[1] = double(my), m[2] = double(mz);
+  }
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const double s = block_sum<kStepWaves>(m[c], red);
+    if (threadIdx.x == 0) mu_part[3 * blk + c] = s;
+  }
+}
+
 // ---- 1. prep (dipole_cell_step_prep_kernel): k table and geometry (blocks blk < n_table_blocks), the two records of every atom
 // and the dipole partials (the blocks behind them).  status: the ONE word of this system.  lr_wavelength <= 0 (a potential
 // without smearing): bit 0 is never set
@@ -27,21 +53,8 @@ __device__ __forceinline__ void ds_prep_body(const KPot& kp, int64_t N, int64_t 
                                              const T* __restrict__ mu, T* __restrict__ kvec, T* __restrict__ G, T* __restrict__ dG,
                                              AtomRecord<T>* __restrict__ recp, AtomRecord<T>* __restrict__ recm,
                                              double* __restrict__ mu_part, double* __restrict__ geom, int* __restrict__ status) {
-  __shared__ double red[kStepWaves];
   if (blk >= n_table_blocks) {  // (uniform per block)
-    const int64_t a = int64_t(blk - n_table_blocks) * kStepBlock + threadIdx.x;
-    double m[3] = {0.0, 0.0, 0.0};
-    if (a < N) {
-      const T mx = mu[3 * a], my = mu[3 * a + 1], mz = mu[3 * a + 2];
-      recp[a] = AtomRecord<T>{pos[3 * a], pos[3 * a + 1], pos[3 * a + 2], T(0)};
-      recm[a] = AtomRecord<T>{mx, my, mz, T(0)};
-      m[0] = double(mx), m[1] = double(my), m[2] = double(mz);
-    }
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const double s = block_sum<kStepWaves>(m[c], red);
-      if (threadIdx.x == 0) mu_part[3 * int64_t(blk - n_table_blocks) + c] = s;
-    }
+    ds_records_body<T>(N, int64_t(blk - n_table_blocks), pos, mu, recp, recm, mu_part);
     return;
   }
   double A[9];
@@ -313,8 +326,9 @@ __device__ __forceinline__ void ds_cellk_body(int64_t N, int64_t K, int64_t blk,
   }
 }
 
-// ---- 6. finish (dipole_cell_step_finish_kernel): 16 lanes per atom, lane l adds the slices l, l + 16, ... in that order, then the
-// 16 lanes are added by the shuffle tree of the rows; 1/V and bg/V from the geometry record
+// ---- 6. finish (the text of dipole_cell_step_finish_kernel, for the batch alone: see the head): 16 lanes per atom, lane l adds the
+// slices l, l + 16, ... in that order, then the 16 lanes are added by the shuffle tree of the rows; 1/V and bg/V from the geometry
+// record
 template <typename T>
 __device__ __forceinline__ void ds_finish_body(int64_t N, int n_slices, int64_t blk, T self_term, double background,
                                                const double* __restrict__ geom, const AtomRecord<T>* __restrict__ recm,
@@ -359,16 +373,17 @@ __device__ __forceinline__ void ds_finish_body(int64_t N, int n_slices, int64_t 
   if (threadIdx.x == 0) e_part[blk] = e;
 }
 
-// ---- 7. final (dipole_cell_step_final_kernel): one block per system; 1/V and A^-1 from the geometry record; NaN for a bad cell --
-template <typename T, bool CELL>
-__device__ __forceinline__ void ds_final_body(int64_t n_e_blocks, const double* __restrict__ e_part, T* __restrict__ energy,
+// ---- 7. final (dipole_step_final_kernel, dipole_cell_step_final_kernel): one block per system: E, and
+// dE/dcell = rows - A^-T W / V - (E_k + E_bg) A^-T with W = sum_k (dE_raw/dk) (x) k.  inv_cell: A^-1 row-major, in T (the caller's
+// table) or in double (the geometry record); inv_vol is read with the cell gradient only; bad (uniform): NaN for a singular cell
+template <typename T, bool CELL, typename Inv>
+__device__ __forceinline__ void ds_final_core(int64_t n_e_blocks, const double* __restrict__ e_part, T* __restrict__ energy,
                                               int64_t n_row_blocks, const double* __restrict__ row_cell, int64_t n_k_blocks,
                                               const double* __restrict__ k_cell, int64_t n_mu_blocks,
-                                              const double* __restrict__ mu_part, double bg, const double* __restrict__ geom,
-                                              T* __restrict__ grad_cell) {
+                                              const double* __restrict__ mu_part, const double* __restrict__ inv_vol_p, double bg,
+                                              const Inv* __restrict__ inv_cell, bool bad, T* __restrict__ grad_cell) {
   __shared__ double red[kStepWaves];
   __shared__ double tot[9 + kStepCellK + 3];
-  const bool bad = geom[10] != 0.0;
   const double E = step_strided_sum(e_part, n_e_blocks, 1, 0, red);
   if (threadIdx.x == 0) energy[0] = bad ? T(NAN) : T(E);
   if (CELL) {
@@ -382,14 +397,25 @@ __device__ __forceinline__ void ds_final_body(int64_t n_e_blocks, const double* 
       const int m = threadIdx.x / 3, n = threadIdx.x % 3;
       const double* Wr = tot;
       const double* Wk = tot + 9;
-      const double Ek = tot[9 + 9], inv_vol = geom[9];
+      const double Ek = tot[9 + 9], inv_vol = inv_vol_p[0];
       const double* M = tot + 9 + kStepCellK;
       const double e_v = inv_vol * (Ek + 0.5 * bg * (M[0] * M[0] + M[1] * M[1] + M[2] * M[2]));  // what scales with 1/V
       double chain = 0.0;
-      for (int a = 0; a < 3; ++a) chain += geom[3 * a + m] * Wk[3 * a + n];
-      grad_cell[3 * m + n] = bad ? T(NAN) : T(Wr[3 * m + n] - inv_vol * chain - e_v * geom[3 * n + m]);
+      for (int a = 0; a < 3; ++a) chain += double(inv_cell[3 * a + m]) * Wk[3 * a + n];
+      grad_cell[3 * m + n] = bad ? T(NAN) : T(Wr[3 * m + n] - inv_vol * chain - e_v * double(inv_cell[3 * n + m]));
     }
   }
+}
+
+// the step that follows its cell: A^-1, 1/V and the bad-cell flag from the geometry record
+template <typename T, bool CELL>
+__device__ __forceinline__ void ds_final_body(int64_t n_e_blocks, const double* __restrict__ e_part, T* __restrict__ energy,
+                                              int64_t n_row_blocks, const double* __restrict__ row_cell, int64_t n_k_blocks,
+                                              const double* __restrict__ k_cell, int64_t n_mu_blocks,
+                                              const double* __restrict__ mu_part, double bg, const double* __restrict__ geom,
+                                              T* __restrict__ grad_cell) {
+  ds_final_core<T, CELL, double>(n_e_blocks, e_part, energy, n_row_blocks, row_cell, n_k_blocks, k_cell, n_mu_blocks, mu_part,
+                                 geom + 9, bg, geom, geom[10] != 0.0, grad_cell);
 }
 
 }  // namespace mipme
